@@ -28,13 +28,21 @@ work is fixed); the only collectives are the barriers around the timed region an
 checksum) to rank 0.  The timed region is a window of K steps per rank out of that job (the list is cyclic, a window never
 runs dry); --drain instead runs the whole job once from a non-cyclic list (value = all ranks' frames / the slowest rank's
 seconds: tail and imbalance included).  Reference frames that fall inside the timed region are executed but not counted.
+`ms_per_step` in the line is the timed region's wall time / --steps.
 Inside a clip the ResNet-50 encoder runs 2 frames ahead of the LSTT on a side stream (frames do not depend on each other before
 the memory read): one launch per encoder layer covers 2 frames x 8 clips, every frame is still encoded exactly once
 (config.encoder_lookahead; config.frames_encoded_in_timed_region counts the frames whose encoder was enqueued inside the window:
 it equals config.frames_counted_in_timed_region up to one look-ahead batch per group -- the encoder pipeline is equally far
 ahead at both ends of the window, so no encoder work is moved out of it).  Inputs are resident in HBM when the timed region starts.
 
-The single JSON line also carries
+A plain run does only what the headline figure needs: set-up, warm-up, the K timed steps, --dump-outputs, the line.
+
+--dump-outputs DIR: right after the timed region, the masks the timed path delivered in its last step (the latest propagated
+frame of every clip in flight, as the label maps a caller receives) go to DIR/labels.npy as float32 [clips, H, W]; inputs and
+weights are seeded, so two builds run with the same arguments can be compared output for output.  See dump_outputs().
+
+With --full the single JSON line also carries (all of it measured after the timed region; without --full `roofline` holds no
+measurement and `cpu_baseline` is null)
   roofline     -- the dominant kernel (the long-term memory read, rmem_mem_read_attn_clips): AFTER the timed region (so
                   it cannot perturb `value`, and independent of --steps) the layer-0 memory read of one group is
                   launched --roofline-launches times (default 32) at bank size T = 8 (the steady state of the
@@ -137,6 +145,27 @@ def check_against_oracle(slot, frames_dev, mask_dev, num_objs, oracle_labels, or
             'bank_indexes': list(slot.engine.long_memories_indexes(0)), 'bank_indexes_equal_the_oracles': list(slot.engine.long_memories_indexes(0)) == oracle_indexes}
 
 
+DUMP_BUDGET_BYTES = 60 << 20      # --dump-outputs writes at most 64 MB, .npy headers included
+
+
+def dump_outputs(out_dir, slots, rank=0, world=1):
+    """--dump-outputs: the latest delivered frame of every slot's clips (GroupSlot labels [B, n, H, W], ClipSlot [n, H, W], frame
+    cursor - 1), slot by slot, as float32 [clips, H, W] in out_dir/labels.npy (rank r > 0: labels_rank<r>.npy).  Above this rank's
+    share of the 64 MB budget the file holds a fixed sample of the flattened maps instead: sorted positions drawn with seed 0, so
+    runs with the same arguments sample the same pixels.  Call it after a device synchronise."""
+    import numpy as np
+    last = [s.labels[:, s.cursor - 1] if s.labels.dim() == 4 else s.labels[s.cursor - 1:s.cursor] for s in slots]
+    out = torch.cat(last).cpu().float()
+    keep = DUMP_BUDGET_BYTES // world // out.element_size()
+    if out.numel() > keep:
+        idx = torch.randperm(out.numel(), generator=torch.Generator().manual_seed(0))[:keep].sort().values
+        out = out.flatten()[idx]
+    os.makedirs(out_dir, exist_ok=True)
+    name = 'labels.npy' if rank == 0 else f'labels_rank{rank}.npy'
+    np.save(os.path.join(out_dir, name), out.numpy())
+    return name
+
+
 def attention_source_sha256() -> str:
     with open(os.path.join(ROOT, 'rmem_ocu_amd', 'csrc', 'attention.hip'), 'rb') as f:
         return hashlib.sha256(f.read()).hexdigest()
@@ -187,7 +216,12 @@ def parse_args(argv=None):
                          'from an idle GPU, a fill / drain transient rather than a rate)')
     ap.add_argument('--clips-in-flight', type=int, default=None,
                     help='clips advancing together on this GPU (default: RMEM_CLIPS_IN_FLIGHT, else the workload\'s own, else 24 = three groups of 8)')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
+    ap.add_argument('--full', action='store_true',
+                    help='also run what the headline figure does not need, after the timed region: the roofline leg, the CPU baseline '
+                         'and the check of the timed path against it')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write the masks the timed path delivered in its last step to DIR/labels.npy (float32)')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='with --full: leave out the CPU baseline and the check')
     ap.add_argument('--workload', default='davis17_480p_r50_N8', choices=sorted(WORKLOADS))
     ap.add_argument('--no-graphs', action='store_true')
     ap.add_argument('--clips-per-group', type=int, default=int(os.environ.get('RMEM_CLIPS_PER_GROUP', 8)),
@@ -200,7 +234,7 @@ def parse_args(argv=None):
                     help='how the clip list reaches the ranks: job-wide ticket queue (default for N > 1) or static longest-first split')
     ap.add_argument('--dtype', default=None, choices=['bf16', 'fp16'],
                     help="16-bit operand type of the kernels (cfg.MODEL_DTYPE); default: the workload's (bf16; fp16 for the cfg-5 workload)")
-    ap.add_argument('--roofline-launches', type=int, default=32, help='isolated T = 8 memory-read launches timed after the timed region')
+    ap.add_argument('--roofline-launches', type=int, default=32, help='with --full: isolated T = 8 memory-read launches timed after the timed region')
     ap.add_argument('--drain', action='store_true',
                     help='run the WHOLE job once instead of a --steps window (non-cyclic clip list: a rank that finds the list empty '
                          'idles): value = propagated frames of all ranks / the slowest rank\'s seconds, tail and imbalance included')
@@ -400,6 +434,8 @@ def main():
             dist.barrier()
         elapsed = time.perf_counter() - t0
     enc_in_window = sum(s.frames_encoded for s in slots) - enc0
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, slots, rank, world)
 
     checksum = float(sum(int(s.labels.sum().item()) for s in slots))
     from rmem_ocu_amd.clip_runner import gather_stats
@@ -410,7 +446,7 @@ def main():
     L = _lib.lib()
     roof = {'achieved': None, 'frac': None, 'launches_timed': 0, 'avg_launch_us': None, 't_mix': {}}
     by_T = {}
-    if rank == 0 and args.roofline_launches > 0:
+    if args.full and rank == 0 and args.roofline_launches > 0:
         inner = inner_of(slots[0])
         inner.stream.synchronize()
         torch.cuda.synchronize()
@@ -452,7 +488,7 @@ def main():
 
     if rank == 0:
         total_frames, elapsed, _ = agg
-        traffic, traffic_src = pmc_traffic(G) if args.workload.startswith('davis17_480p_r50_N8') else (None, None)
+        traffic, traffic_src = pmc_traffic(G) if args.full and args.workload.startswith('davis17_480p_r50_N8') else (None, None)
         L16 = (net_hw[0] // 16 if wl['net'] else (net_hw[0] - 1) // 16 + 1) * (net_hw[1] // 16 if wl['net'] else (net_hw[1] - 1) // 16 + 1)
         out = {
             'metric': 'frames/sec (whole node) 480p VOS, N=8 memory bank' if args.workload == 'davis17_480p_r50_N8'
@@ -478,7 +514,7 @@ def main():
                          'clips_per_launch': G, 'sampled': 'after the timed region, isolated direct launches',
                          **({'by_T': by_T} if len(by_T) > 1 else {})},
         }
-        if world == 1 and not args.no_cpu_baseline and args.workload == 'davis17_480p_r50_N8':
+        if args.full and world == 1 and not args.no_cpu_baseline and args.workload == 'davis17_480p_r50_N8':
             out['cpu_baseline'], oracle_labels, oracle_indexes = cpu_baseline(*clips_host[0], VIDEO_HW)
             if G > 1 and not args.host_frames:
                 out['check'] = check_against_oracle(slots[0], clips[0][0], clips[0][1], NUM_OBJS, oracle_labels, oracle_indexes)

@@ -165,3 +165,23 @@ def test_deaot_group_key_table_rows_per_frame():
             assert 1 <= r <= 4 and r * T <= 32
             if r > 1:                                # cut only while the launch is short of ~512 workgroups
                 assert ((L + 127) // 128) * T * clips * (r - 1) < 512
+
+
+def test_bench_dump_outputs_last_frame_and_budget(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: the latest delivered frame of every clip in flight, group slots ([B, n, H, W] labels) and per-clip
+    slots ([n, H, W]) in slot order, as float32; over the budget a fixed sample that is the same in every run."""
+    from types import SimpleNamespace
+    import bench
+    g = torch.Generator().manual_seed(3)
+    group = SimpleNamespace(labels=torch.randint(0, 4, (8, 10, 6, 7), generator=g, dtype=torch.uint8), cursor=5)
+    clip = SimpleNamespace(labels=torch.randint(0, 4, (10, 6, 7), generator=g, dtype=torch.uint8), cursor=10)
+    assert bench.dump_outputs(str(tmp_path / 'a'), [group, clip]) == 'labels.npy'
+    got = np.load(tmp_path / 'a' / 'labels.npy')
+    assert got.dtype == np.float32 and got.shape == (9, 6, 7)
+    assert np.array_equal(got[:8], group.labels[:, 4].numpy()) and np.array_equal(got[8], clip.labels[9].numpy())
+    assert bench.dump_outputs(str(tmp_path / 'a'), [clip], rank=1, world=2) == 'labels_rank1.npy'
+    monkeypatch.setattr(bench, 'DUMP_BUDGET_BYTES', 4 * 100)
+    for d in ('b', 'c'):
+        bench.dump_outputs(str(tmp_path / d), [group, clip])
+    b, c = np.load(tmp_path / 'b' / 'labels.npy'), np.load(tmp_path / 'c' / 'labels.npy')
+    assert b.dtype == np.float32 and b.shape == (100,) and np.array_equal(b, c)
