@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define RMEM_ABI_VERSION 8
+#define RMEM_ABI_VERSION 9
 
 int rmem_abi_version(void);
 const char* rmem_last_error_string(void);
@@ -387,6 +387,88 @@ int rmem_conv3x3_c64_direct(const void* x, int images, int H, int W, const void*
  * ImageNet normalise -> fp32 [3][Hd][Wd] (the engine API's input) and/or bf16 [Hd][Wd][8] (the encoder's input).
  * Replaces dataloaders/video_transforms.py:648-652 (cv2.resize) + 676-680 (normalise) on the host. */
 int rmem_ingest_rgb8(const unsigned char* rgb_hwc, int Hs, int Ws, int Hd, int Wd, float* out_chw, void* out_nhwc8, void* stream);
+/* ------------------------------------------------------------------ baseline JPEG decode (jpeg_host.cpp, jpeg.hip)
+ * Compressed frames in, the exact uint8 RGB libjpeg-turbo (Pillow) produces out.  Supported: 8-bit baseline / extended Huffman,
+ * one interleaved scan, grayscale or YCbCr at 4:4:4, 4:2:2 (h2v1) and 4:2:0 (h2v2), optional restart intervals, any size.
+ * The host side (parse, pack) needs no GPU; the device side runs on the caller's stream with no host synchronisation. */
+#define RMEM_JPEG_SUBSEQ_BITS 1024      /* one lane of the entropy decoder owns this many bits of a unit */
+
+typedef struct rmem_jpeg_info {
+  int width, height, components;
+  int h_samp[3], v_samp[3], quant_id[3];   /* as written in SOF (components >= 1) */
+  int restart_interval;                    /* MCUs per restart interval (DRI), 0 = none */
+  int quant_mask;                          /* bit t set: quant[t] was defined by a DQT */
+  unsigned short quant[4][64];             /* quantisation tables in natural (row-major) order */
+  long long scan_begin, scan_end;          /* byte range of the entropy-coded segment in the file */
+  long long packed_bound;                  /* upper bound of the bytes rmem_jpeg_pack appends for this file */
+} rmem_jpeg_info;
+
+/* Huffman decode table: a 9-bit lookup for short codes and the canonical-code slow path for lengths 10..16. */
+typedef struct rmem_jpeg_huff {
+  unsigned short lut[512];                 /* next 9 bits -> (code length << 8) | symbol; 0 = code longer than 9 bits */
+  int maxcode[18];                         /* largest code of each length, -1 if none */
+  int valoff[18];                          /* symbol index of a code of length l = code + valoff[l] */
+  unsigned char vals[256];
+} rmem_jpeg_huff;
+
+/* Per-frame descriptor written by rmem_jpeg_pack (fixed size, copied to the device as an array).
+ * A frame's chunk in the clip buffer is: (nunits + 1) x {uint32 bit offset, uint32 first subsequence} (the last entry closes the
+ * list), zero padding to data_off, the entropy bytes without byte stuffing and RSTn markers, then >= 16 zero bytes.
+ * A unit is a restart interval, or the whole scan without DRI; it starts on a byte boundary and is cut into
+ * ceil(bits / RMEM_JPEG_SUBSEQ_BITS) subsequences. */
+typedef struct rmem_jpeg_desc {
+  long long offset;                        /* byte offset of the chunk in the clip buffer (16-byte aligned) */
+  long long bytes;                         /* chunk length */
+  int width, height, ncomp, hmax, vmax;
+  int mcus_x, mcus_y, bpm;                 /* MCU grid and blocks per MCU (a one-component scan has 1x1-block MCUs) */
+  int restart_mcus, nunits, nsub, total_blocks;
+  int data_off, data_bits;                 /* entropy bytes: chunk offset and length in bits */
+  int comp_h[3], comp_v[3];                /* sampling factors (1 for a one-component scan) */
+  int comp_bw[3], comp_bh[3];              /* coefficient plane of a component in blocks (the MCU grid's, padded) */
+  int comp_block0[3];                      /* first block of the component's plane in the [total_blocks][64] buffer */
+  int comp_dw[3], comp_dh[3];              /* downsampled_width / height: ceil(width * h / hmax), ceil(height * v / vmax) */
+  int mcu_comp[10], mcu_sub[10];           /* block b of an MCU: component, and index inside that component's h x v group */
+  unsigned short quant[3][64];             /* per component, natural order */
+  rmem_jpeg_huff dc[3], ac[3];             /* per component */
+} rmem_jpeg_desc;
+
+/* Sizes of a decode call, from rmem_jpeg_workspace_bytes; pass the struct to the device entry points unchanged except for
+ * sync_rounds / flags. */
+typedef struct rmem_jpeg_plan {
+  int batch;                               /* frames per call at most */
+  int max_width, max_height, max_sub, max_blocks, max_units;
+  int sync_rounds;                         /* bounded cross-workgroup sync launches (default 8; 0 = none) */
+  int flags;                               /* RMEM_JPEG_FORCE_FALLBACK: every unit goes to the sequential decoder (tests) */
+  long long slot_bytes;                    /* workspace per frame */
+  long long off_state, off_unit, off_dc, off_coef, off_plane, off_misc;   /* offsets inside a slot */
+} rmem_jpeg_plan;
+#define RMEM_JPEG_FORCE_FALLBACK 1
+/* status word of a frame (0 = decoded) */
+#define RMEM_JPEG_ST_COUNT   1                  /* a unit did not decode to its MCU count */
+#define RMEM_JPEG_ST_CODE    2                  /* invalid Huffman code or coefficient index on the decode path */
+#define RMEM_JPEG_ST_DESC    4                  /* descriptor outside the plan */
+
+/* Headers only: 0, or non-zero with the reason in rmem_last_error_string() (progressive, arithmetic, 12-bit, multi-scan,
+ * 4 components, unsupported sampling, truncated, ...).  No GPU needed. */
+int rmem_jpeg_parse(const unsigned char* data, size_t n, rmem_jpeg_info* out);
+/* Appends one frame's chunk to the caller's (pinned) buffer at the 16-byte aligned offset >= *used and advances *used;
+ * fills *desc.  Fails if cap is too small (info.packed_bound bytes always suffice).  No GPU needed. */
+int rmem_jpeg_pack(const unsigned char* data, size_t n, unsigned char* buf, size_t cap, size_t* used, rmem_jpeg_desc* desc);
+/* Workspace for decoding up to `batch` frames at once of any of the ndesc host descriptors; fills *plan. */
+size_t rmem_jpeg_workspace_bytes(const rmem_jpeg_desc* descs, int ndesc, int batch, rmem_jpeg_plan* plan);
+/* Entropy decode of frames first .. first+n-1 of the device descriptor table: int16 coefficients [total_blocks][64] in natural
+ * order with DC values (not differences) at workspace + i * plan->slot_bytes + plan->off_coef.  bits = clip buffer (device).
+ * status[n] (device) receives the per-frame status word; stats (device, may be NULL) accumulates {sync launches that ran,
+ * units sent to the sequential fallback}. */
+int rmem_jpeg_entropy_decode(const unsigned char* bits, const rmem_jpeg_desc* descs, int first, int n, const rmem_jpeg_plan* plan,
+                             void* workspace, int* status, int* stats, void* stream);
+/* Dequantise + ISLOW IDCT + fancy upsampling + YCbCr->RGB of the coefficients left by rmem_jpeg_entropy_decode:
+ * out[i] (device array of n device pointers) = uint8 [height][width][3]. */
+int rmem_jpeg_coef_to_rgb(const rmem_jpeg_desc* descs, int first, int n, const rmem_jpeg_plan* plan, void* workspace,
+                          unsigned char* const* out, void* stream);
+/* Both of the above. */
+int rmem_jpeg_decode_batch(const unsigned char* bits, const rmem_jpeg_desc* descs, int first, int n, const rmem_jpeg_plan* plan,
+                           void* workspace, unsigned char* const* out, int* status, int* stats, void* stream);
 /* 3x3 stride-2 pad-1 max-pool (encoders/resnet.py:105, 182). */
 int rmem_maxpool3x3s2_nhwc(const void* x, void* y, int H, int W, int C, void* stream);
 int rmem_maxpool3x3s2_nhwc_images(const void* x, void* y, int images, int H, int W, int C, void* stream);

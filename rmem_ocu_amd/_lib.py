@@ -11,7 +11,7 @@ import subprocess
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('RMEM_LIB_PATH') or os.path.join(_HERE, 'librmem_hip.so')   # override: kernel experiments only
-ABI_VERSION = 8
+ABI_VERSION = 9
 
 
 class RmemError(RuntimeError):
@@ -34,6 +34,33 @@ class AttnChunk(C.Structure):
 
 
 _vp, _i, _ll, _f = C.c_void_p, C.c_int, C.c_longlong, C.c_float
+
+
+class JpegInfo(C.Structure):
+    _fields_ = [('width', C.c_int), ('height', C.c_int), ('components', C.c_int), ('h_samp', C.c_int * 3), ('v_samp', C.c_int * 3),
+                ('quant_id', C.c_int * 3), ('restart_interval', C.c_int), ('quant_mask', C.c_int), ('quant', (C.c_ushort * 64) * 4),
+                ('scan_begin', C.c_longlong), ('scan_end', C.c_longlong), ('packed_bound', C.c_longlong)]
+
+
+class JpegHuff(C.Structure):
+    _fields_ = [('lut', C.c_ushort * 512), ('maxcode', C.c_int * 18), ('valoff', C.c_int * 18), ('vals', C.c_ubyte * 256)]
+
+
+class JpegDesc(C.Structure):
+    _fields_ = ([('offset', C.c_longlong), ('bytes', C.c_longlong)]
+                + [(n, C.c_int) for n in ('width', 'height', 'ncomp', 'hmax', 'vmax', 'mcus_x', 'mcus_y', 'bpm', 'restart_mcus', 'nunits',
+                                          'nsub', 'total_blocks', 'data_off', 'data_bits')]
+                + [(n, C.c_int * 3) for n in ('comp_h', 'comp_v', 'comp_bw', 'comp_bh', 'comp_block0', 'comp_dw', 'comp_dh')]
+                + [('mcu_comp', C.c_int * 10), ('mcu_sub', C.c_int * 10), ('quant', (C.c_ushort * 64) * 3), ('dc', JpegHuff * 3),
+                   ('ac', JpegHuff * 3)])
+
+
+class JpegPlan(C.Structure):
+    _fields_ = ([(n, C.c_int) for n in ('batch', 'max_width', 'max_height', 'max_sub', 'max_blocks', 'max_units', 'sync_rounds', 'flags')]
+                + [(n, C.c_longlong) for n in ('slot_bytes', 'off_state', 'off_unit', 'off_dc', 'off_coef', 'off_plane', 'off_misc')])
+
+
+JPEG_FORCE_FALLBACK = 1
 
 
 def _desc(name, ints, ptrs):
@@ -125,6 +152,12 @@ SIGNATURES = {
     'rmem_local_gated_attn_clips': (_i, [_vp, _i, _vp, _i, _vp, _i, _vp, _i, _i, _i, _i, _vp, _i, _vp, _i, _i, _vp, _i, _vp, _i, _vp, _vp]),
     'rmem_gated_profile_start': (_i, []),
     'rmem_gated_profile_stop': (_i, [C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(_i)]),
+    'rmem_jpeg_parse': (_i, [_vp, C.c_size_t, C.POINTER(JpegInfo)]),
+    'rmem_jpeg_pack': (_i, [_vp, C.c_size_t, _vp, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(JpegDesc)]),
+    'rmem_jpeg_workspace_bytes': (C.c_size_t, [C.POINTER(JpegDesc), _i, _i, C.POINTER(JpegPlan)]),
+    'rmem_jpeg_entropy_decode': (_i, [_vp, _vp, _i, _i, C.POINTER(JpegPlan), _vp, _vp, _vp, _vp]),
+    'rmem_jpeg_coef_to_rgb': (_i, [_vp, _i, _i, C.POINTER(JpegPlan), _vp, _vp, _vp]),
+    'rmem_jpeg_decode_batch': (_i, [_vp, _vp, _i, _i, C.POINTER(JpegPlan), _vp, _vp, _vp, _vp, _vp]),
     'rmem_graph_begin': (_i, [_vp]),
     'rmem_graph_end': (_i, [_vp, C.POINTER(_vp)]),
     'rmem_graph_launch': (_i, [_vp, _vp]),

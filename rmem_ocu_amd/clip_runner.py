@@ -15,6 +15,17 @@ from typing import List, Optional, Sequence
 import torch
 
 from . import ops
+from .jpeg import JpegClip
+
+
+def _load_frames(dst: torch.Tensor, frames, i: int, m: int, stream: int):
+    """Frames i .. i+m-1 of a clip into the uint8 staging rows dst[0:m] on ``stream``: an H2D copy of pinned uint8 frames, or
+    for a JpegClip the copy of their compressed bytes and the GPU decode straight into those rows."""
+    if isinstance(frames, JpegClip):
+        frames.decode_into(list(dst[:m]), i, m, stream)
+    else:
+        hs, ws = int(frames.shape[1]), int(frames.shape[2])
+        ops.copy_async(dst, frames[i:i + m], m * hs * ws * 3)(stream)
 
 
 def shard_clips(num_clips: int, rank: int, world: int, lengths: Optional[Sequence[int]] = None) -> List[int]:
@@ -170,8 +181,11 @@ class ClipSlot:
 
     def start(self, frames: torch.Tensor, first_mask: torch.Tensor, num_objs: int):
         """frames [n,3,H,W] fp32 device at network size, or decoded uint8 RGB [n,Hs,Ws,3] in PINNED HOST memory (then every
-        frame crosses PCIe as uint8 and is resized + normalised on the device, rmem_ingest_rgb8);
+        frame crosses PCIe as uint8 and is resized + normalised on the device, rmem_ingest_rgb8), or a JpegClip (only the
+        compressed frames cross PCIe; they are decoded on the device into the same uint8 rows; start() raises RmemError if a
+        frame of the PREVIOUS JpegClip did not decode cleanly, check_frames() checks the current one);
         first_mask [1,1,H,W] at network size."""
+        self.check_frames()
         n = frames.shape[0]
         self.frames = frames
         self.host_u8 = frames.dtype == torch.uint8
@@ -194,7 +208,7 @@ class ClipSlot:
             # order this clip's first-frame copy + ingest behind them (a device-side wait, no host stall)
             for e in eng.aot_engines + getattr(eng, '_pool', []):
                 cur.wait_stream(e.stream)
-            ops.copy_async(self._stage[0], frames[0], hs * ws * 3)(cur.cuda_stream)
+            _load_frames(self._stage, frames, 0, 1, cur.cuda_stream)
             ops.run(ops.ingest_rgb8(self._stage[0], Hs=hs, Ws=ws, Hd=H, Wd=W, out_chw=self._first[0]), cur.cuda_stream)
             cur.synchronize()        # once per clip: the engine works on its own stream
             eng.add_reference_frame(self._first, first_mask, obj_nums=[num_objs], frame_step=0)
@@ -203,6 +217,14 @@ class ClipSlot:
         self.frames_encoded += 1
         self.cursor = 1
         self.done = n <= 1
+
+    def check_frames(self):
+        """Once per JPEG clip: wait for the clip's work and raise RmemError if one of its frames did not decode cleanly (a
+        corrupt entropy-coded segment behind valid headers).  A no-op for other frame sources."""
+        if isinstance(self.frames, JpegClip):
+            self.engine.synchronize()
+            torch.cuda.current_stream(self.device).synchronize()
+            self.frames.check(self.device)
 
     def _ingest_group(self, i: int):
         """Host -> device copy of the next look-ahead group of uint8 frames and their resize + normalise into the encoder's
@@ -213,7 +235,7 @@ class ClipSlot:
         m = min(la, self.frames.shape[0] - i)
         hs, ws = int(self.frames.shape[1]), int(self.frames.shape[2])
         H, W = self._net_hw
-        ops.copy_async(self._stage, self.frames[i:i + m], m * hs * ws * 3)(s)
+        _load_frames(self._stage, self.frames, i, m, s)
         dst = eng.encode_inputs(la) if la > 1 else self._first
         ops.run([ops.ingest_rgb8(self._stage[b], Hs=hs, Ws=ws, Hd=H, Wd=W, out_chw=dst[b]) for b in range(m)], s)
 
@@ -264,12 +286,15 @@ class GroupSlot:
 
     def start(self, frames: Sequence[torch.Tensor], first_masks: Sequence[torch.Tensor], num_objs: int, new_objects=None):
         """frames: B tensors [n, 3, H, W] fp32 device (equal n), or B uint8 [n, Hs, Ws, 3] tensors in PINNED HOST memory (every
-        frame then crosses PCIe as uint8 and is resized + normalised on the device); first_masks: B tensors [1, 1, H, W] at the
+        frame then crosses PCIe as uint8 and is resized + normalised on the device), or B JpegClips (decoded on the device into
+        the same uint8 staging rows, look-ahead group by look-ahead group; start() raises RmemError if a frame of the PREVIOUS
+        clips did not decode cleanly, check_frames() checks the current ones); first_masks: B tensors [1, 1, H, W] at the
         network size.  new_objects: {clip index: (frame index, uint8 [Ho, Wo] device map: the new object's label on its pixels, 0
         elsewhere)} -- the evaluator's protocol for an object that appears mid-clip (managers/evaluator.py:484-508): the frame is
         propagated, the new label is laid over the prediction and the frame is re-added as a reference frame for that clip."""
         assert len(frames) == self.B and len({int(f.shape[0]) for f in frames}) == 1
         n = int(frames[0].shape[0])
+        self.check_frames()                       # JPEG clips: waits for their decodes, so they can be let go of
         if getattr(self, '_frames_by_pointer', False):
             self.engine.enc_stream.synchronize()  # queued encoder launches read the previous clips' frames in place: let go of them after
         self.frames = list(frames)
@@ -295,7 +320,7 @@ class GroupSlot:
                 for c in range(self.B):
                     if not frames[c].is_pinned():
                         raise ValueError('uint8 host frames must be in pinned memory')
-                    ops.copy_async(self._stage[c], frames[c][0], hs * ws * 3)(s)
+                    _load_frames(self._stage[c:c + 1], frames[c], 0, 1, s)
                 ops.run([ops.ingest_rgb8(self._stage[c], Hs=hs, Ws=ws, Hd=H, Wd=W, out_chw=self._first[c]) for c in range(self.B)], s)
                 imgs = self._first
             else:
@@ -307,6 +332,16 @@ class GroupSlot:
         self.done = n <= 1
         if eng.lookahead > 1 and n > 1:
             self._kick_encoder(0, 1)                            # frames 1 .. lookahead: batch 0
+
+    def check_frames(self):
+        """Once per group of JPEG clips: wait for the group's work and raise RmemError if a frame did not decode cleanly.  A
+        no-op for other frame sources."""
+        clips = [f for f in (self.frames or []) if isinstance(f, JpegClip)]
+        if clips:
+            self.engine.synchronize()
+            torch.cuda.current_stream(self.device).synchronize()
+            for c in clips:
+                c.check(self.device)
 
     def _kick_encoder(self, buf: int, i: int):
         """Encode frames i .. i + lookahead - 1 of every clip into look-ahead buffer ``buf`` on the engine's side stream."""
@@ -340,7 +375,7 @@ class GroupSlot:
             hs, ws = int(self.frames[0].shape[1]), int(self.frames[0].shape[2])
             H, W = int(dst.shape[-2]), int(dst.shape[-1])
             for c in range(B):
-                ops.copy_async(stage[c * m:(c + 1) * m], self.frames[c][i:i + m], m * hs * ws * 3)(s)
+                _load_frames(stage[c * m:(c + 1) * m], self.frames[c], i, m, s)
             ops.run([ops.ingest_rgb8(stage[c * m + k], Hs=hs, Ws=ws, Hd=H, Wd=W, out_chw=dst[k * B + c]) for c in range(B)
                      for k in range(m)], s)
         else:

@@ -78,6 +78,34 @@ def region_similarity(pred_u8: torch.Tensor, gt_u8: torch.Tensor, num_ids: int =
     return {i: (1.0 if c[i, 1] == 0 else float(c[i, 0]) / float(c[i, 1])) for i in range(1, num_ids) if c[i, 1] > 0}
 
 
+def frames_from_jpegs(paths_or_bytes: Sequence, device, scale: float = 1.0) -> torch.Tensor:
+    """A clip's JPEG files (paths or bytes, one size) -> fp32 [n, 3, H, W] normalised frames at the network size
+    synth.network_size(h, w, scale=scale): GPU decode (rmem_jpeg_decode_batch, jpeg.CHUNK frames per call) then bicubic resize + normalise
+    (rmem_ingest_rgb8), the input SequenceEvaluator.run takes."""
+    from .jpeg import CHUNK, JpegClip
+    from .synth import network_size
+    device = torch.device(device)
+    datas = []
+    for p in paths_or_bytes:
+        if isinstance(p, (bytes, bytearray, memoryview)):
+            datas.append(bytes(p))
+        else:
+            with open(p, 'rb') as f:
+                datas.append(f.read())
+    clip = JpegClip(datas)
+    n, (hs, ws) = len(clip), clip.sizes[0]
+    H, W = network_size(hs, ws, scale=scale)
+    out = torch.empty(n, 3, H, W, dtype=torch.float32, device=device)
+    rgb = torch.empty(min(n, CHUNK), hs, ws, 3, dtype=torch.uint8, device=device)     # one chunk of decoded frames at a time
+    stream = torch.cuda.current_stream(device).cuda_stream
+    for k in range(0, n, CHUNK):
+        m = min(CHUNK, n - k)
+        clip.decode_into(list(rgb[:m]), k, m, stream)
+        ops.run([ops.ingest_rgb8(rgb[b], Hs=hs, Ws=ws, Hd=H, Wd=W, out_chw=out[k + b]) for b in range(m)], stream)
+    clip.check(device, stream=stream)
+    return out
+
+
 class SequenceEvaluator:
     """Runs one sequence through the engine(s) exactly as the reference evaluator would."""
 
