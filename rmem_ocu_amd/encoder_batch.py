@@ -2,10 +2,9 @@
 
 Clips are independent but share the frozen encoder (encoders/resnet.py:10-196; models/aot.py:116-134), and one 481x849
 frame gives GEMMs of only 1.7 k - 26 k rows.  ``BatchEncoder`` runs every encoder layer once for B frames (the conv
-kernel's ``batch`` dimension: rows are [image][ho][wo]), writing the three stage outputs into [B, ...] buffers whose slice b
-IS clip b's ``enc1 / enc2 / enc3`` (ClipRuntime.adopt_encoder_outputs), so each clip's own launch lists -- projector, LSTT,
-decoder -- continue from there unchanged.  Results are bit-identical to the per-clip encoder: the same kernel computes
-every output row from the same operands in the same order.
+kernel's ``batch`` dimension: rows are [image][ho][wo]), writing the three stage outputs into [B, ...] buffers ``enc_out``
+(enc1, enc2, enc3) that the runtime's launch lists -- projector, LSTT, decoder -- continue from (GroupRuntime._enc).  A frame's
+results do not depend on B: the same kernel computes every output row from the same operands in the same order.
 """
 from __future__ import annotations
 
@@ -195,12 +194,12 @@ class BatchEncoder(_PtrInput):
 
 
 class SwinBatchEncoder(_PtrInput):
-    """Swin-B (cfg 5; encoders/swin/swin_transformer.py:500-716) over B frames: the look-ahead counterpart of
-    ClipRuntime._prog_encode_swin.  One 720x1280 frame leaves only 3600 tokens for the 18 blocks of stage 3, so its linears are
-    GEMMs of 3600 rows and its LayerNorms launches of 3.7 MB; with B frames stacked as rows [frame][token] every linear and
-    LayerNorm is ONE launch over B times the rows (weights are shared, rows independent); window attention and patch merging
-    depend on the image geometry and take the frame as a grid dimension.  Same kernels, same
-    operands per row as the per-frame encoder; interface of BatchEncoder (img_in, prog(), enc_out)."""
+    """Swin-B (cfg 5; encoders/swin/swin_transformer.py:500-716) over B frames: patch embed (patch 4) + LN, 3 stages of
+    (shifted-)window blocks with patch merging between them (500-545, 684-716), per-stage output norms.  One 720x1280 frame
+    leaves only 3600 tokens for the 18 blocks of stage 3, so its linears are GEMMs of 3600 rows and its LayerNorms launches of
+    3.7 MB; with B frames stacked as rows [frame][token] every linear and LayerNorm is ONE launch over B times the rows (weights
+    are shared, rows independent); window attention and patch merging depend on the image geometry and take the frame as a grid
+    dimension.  Interface of BatchEncoder (img_in, prog(), enc_out)."""
 
     def __init__(self, P: Dict[str, torch.Tensor], in_hw: Tuple[int, int], batch: int, device):
         if 'pe.w' not in P:

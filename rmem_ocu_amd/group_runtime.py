@@ -1,9 +1,24 @@
-"""Device state and launch lists for a GROUP of clips that advance in lockstep (R50-AOTL and SwinB-AOTL paths).
+"""Device state and launch lists of a frame (R50-AOTL and SwinB-AOTL paths), for one clip (the per-clip engines) or a GROUP of
+clips that advance in lockstep (GroupEngine).
+
+``GroupRuntime`` owns everything an engine needs on the GPU for one network size: activation buffers (NHWC bf16; the LSTT
+residual stream is fp32), the long-term memory bank as a slot ring per layer (an index table instead of the reference's
+torch.cat / slice, layers/transformer.py:319, 432-433), the short-term memory, and the prepared launch lists (``ops.Op``) for
+
+    encode      image -> ResNet-50 / Swin-B (encoder_batch)    (models/aot.py:116-134)
+    project     1x1 encoder projector                          (models/aot.py:25-29)
+    lstt ref    3 LSTT layers, reference-frame mode            (layers/transformer.py:582-588)
+    lstt prop   3 LSTT layers, propagate mode, bank size T     (layers/transformer.py:589-692)
+    decode      FPN head -> logits at 1/4 resolution           (decoders/fpn.py:36-68)
+    id_emb      label map -> one-hot -> identity bank conv     (engines/aot_engine.py:208-232)
+    update      short/long-term memory update                  (layers/transformer.py:269-322)
+
+The lists are pure functions of the buffers' addresses, so each one is built once and replayed (directly or as a captured
+hipGraph).  Everything that changes from frame to frame (slot table, temporal-PE slots, append slots) lives in device memory.
 
 At HW = 1674 tokens a launch costs about as much as its arithmetic and only four kernels are in flight on the GPU
 (DESIGN.md §7b), so the throughput path does not run one clip per launch list: B clips of equal length share one
-``GroupRuntime``.  Every activation buffer of runtime.ClipRuntime gets a leading clip dimension ([B * rows, C], clip-major),
-which turns
+``GroupRuntime``.  Every activation buffer has a leading clip dimension ([B * rows, C], clip-major), which turns
 
     every linear / LayerNorm / add      into the same launch over B * HW rows,
     every convolution                   into one launch over a batch of B images (rmem_conv_desc.batch),
@@ -15,8 +30,6 @@ the bank is [B * slots, HW, 256] per layer, clip c owns slots c * S .. c * S + S
 per clip, and appends go through a device table of destination slots (rmem_scatter_blocks), so ONE captured hipGraph per
 bank size serves the whole group.  Frame counters, append schedule and bank size T are the same for all clips of a group
 (equal length => same gap, evaluator.py:330-335); the eviction decision is per clip (engines/group_engine.py).
-
-The per-op arithmetic is exactly ClipRuntime's (same kernels, same operands per clip), cf. the citations there.
 """
 from __future__ import annotations
 
@@ -43,15 +56,15 @@ class GroupRuntime:
         if ('g0.qvu.w' in P) != self.deaot:
             raise ops.RmemError('GroupRuntime covers the AOTL paths (ResNet-50 / Swin-B), group_runtime_deaot.GroupRuntimeDeAOT the R50-DeAOTL path')
         self.swin = 'pe.w' in P
-        self.chain = not __import__('os').environ.get('RMEM_NO_CHAIN')      # 1: the unfused launch list (A/B runs, identity tests)
-        self.pair_attn = not __import__('os').environ.get('RMEM_NO_PAIR_ATTN')   # 1: memory read and short-term attention as two launches
+        self.chain = not os.environ.get('RMEM_NO_CHAIN')      # 1: the unfused launch list (A/B runs, identity tests)
+        self.pair_attn = not os.environ.get('RMEM_NO_PAIR_ATTN')   # 1: memory read and short-term attention as two launches
         self.P, self.dev, self.NL, self.B = P, device, num_lstt, clips
         self.dt = P['proj.w'].dtype
         self.align, self.nc = align_corners, num_classes
         H, W = in_hw
         self.H, self.W = H, W
         B = clips
-        if self.swin:     # Swin-B (cfg 5): patch 4 and two patch mergings (runtime.ClipRuntime has the citations)
+        if self.swin:     # Swin-B (cfg 5): patch 4, then two patch mergings (encoders/swin/swin_transformer.py:500-545, 684-716)
             if H % 4 or W % 4:
                 raise ops.RmemError('Swin-B path: network size must be a multiple of 4 (the evaluator makes it a multiple of 16)')
             self.H4, self.W4 = H // 4, W // 4
@@ -68,25 +81,25 @@ class GroupRuntime:
         L, M4, M8 = self.L, self.H4 * self.W4, self.H8 * self.W8
         self.M4, self.M8 = M4, M8
         e = lambda *shape, dt=None: torch.empty(*shape, dtype=dt or self.dt, device=device)  # noqa: E731
-        # ---- encoders: one for the frame in flight (reference frames), one running `lookahead` frames ahead; image = e * B + c
-        Enc = SwinBatchEncoder if self.swin else BatchEncoder
-        self.enc_now = Enc(P, in_hw, B, device)
-        self.lookahead = lookahead
-        # two look-ahead encoders: while the frames of one batch are being propagated, the next batch is encoded on the engine's
-        # side stream (group_engine.py); look-ahead slot s = buffer * lookahead + frame
-        self.enc_bufs = [Enc(P, in_hw, B * lookahead, device) for _ in range(2)] if lookahead > 1 else []
-        self.enc_ahead = self.enc_bufs[0] if self.enc_bufs else None
+        # ---- encoders: one for the frame in flight (reference frames), and on request look-ahead encoders; image = e * B + c
+        self.enc_now = (SwinBatchEncoder if self.swin else BatchEncoder)(P, in_hw, B, device)
+        self.lookahead, self.enc_bufs = lookahead, []
+        self._prog: Dict[str, list] = {}
+        if lookahead > 1:
+            # two look-ahead encoders: while the frames of one batch are being propagated, the next batch is encoded on the engine's
+            # side stream (group_engine.py); look-ahead slot s = buffer * lookahead + frame
+            self.build_lookahead(2, lookahead)
         # ---- LSTT buffers, [B * L, .] clip-major ----
         R = B * L
-        self.dec_in = e(R, self.dec_cin)
+        self.dec_in = e(R, self.dec_cin)             # AOT: cat(enc256, 3 x normed LSTT out), decoders/fpn.py:38-39
         self.id_emb = e(R, D_MODEL)
         self.onehot = e(B * H * W, 16)
         self._alloc_lstt(R, num_lstt)
         self.gn_ws = ops.groupnorm_workspace(32, device, images=B)
         # GroupNorm partial sums of the FFN hidden written by the chained linear1 (one entry per 32-row block, the rest stays zero)
         self.ffn_stats = torch.zeros(B * 32 * 64 * 2, dtype=F32, device=device)
-        self.chain_stats = self.chain and (self.L + 31) // 32 <= 64 and not __import__('os').environ.get('RMEM_NO_CHAIN_STATS')
-        self.conv_ws = torch.empty(16 * R * D_MODEL, dtype=F32, device=device)
+        self.chain_stats = self.chain and (self.L + 31) // 32 <= 64 and not os.environ.get('RMEM_NO_CHAIN_STATS')
+        self.conv_ws = torch.empty(16 * R * D_MODEL, dtype=F32, device=device)      # split-K slabs (<= 16 slices of [B * HW, 256])
         self.mass = torch.zeros(B * L * MAX_CHUNKS, dtype=F32, device=device)          # [B][L][T] compact for the current T
         self.scores = torch.zeros(B, 32 + 64 * 32, dtype=F32, device=device)
         self.scores_host = torch.zeros(B, MAX_CHUNKS, dtype=F32).pin_memory()
@@ -105,13 +118,20 @@ class GroupRuntime:
         self.chunks_ring = ops.PinnedRing(4, (B * self.max_rows, 8), torch.int32, device)
         self.append_slots = torch.full((B,), -1, dtype=torch.int32, device=device)   # global destination slot per clip
         self.append_ring = ops.PinnedRing(4, (B,), torch.int32, device)
-        self._prog: Dict[str, list] = {}
+
+    def build_lookahead(self, buffers: int, frames: int):
+        """The frames of a clip do not depend on each other before the LSTT, so the encoder (ResNet-50 or Swin-B) may run ``frames``
+        frames ahead as ONE launch per layer (rmem_ocu_amd.encoder_batch): (re)build ``buffers`` look-ahead encoders of B * frames
+        images each; slot e of their outputs then feeds prog_project(e) / prog_decode(e) of the frame that is propagated."""
+        self.lookahead = frames
+        self.enc_bufs = [type(self.enc_now)(self.P, (self.H, self.W), self.B * frames, self.dev) for _ in range(buffers)]
+        self._prog = {k: v for k, v in self._prog.items() if not k.startswith(('project_', 'decode_'))}
 
     def _alloc_lstt(self, R: int, num_lstt: int):
         """LSTT activations, [B * L, .] clip-major."""
         device, L, B = self.dev, self.L, self.B
         e = lambda *shape, dt=None: torch.empty(*shape, dtype=dt or self.dt, device=device)  # noqa: E731
-        self.x = e(R, D_MODEL, dt=F32)
+        self.x = e(R, D_MODEL, dt=F32)              # residual stream
         self.t1b = e(R, D_MODEL)
         self.qkv = e(R, 3 * D_MODEL)
         self.att = e(R, D_MODEL)
@@ -119,8 +139,8 @@ class GroupRuntime:
         self.t3 = e(R, D_MODEL)
         self.k4, self.v4 = e(R, D_MODEL), e(R, D_MODEL)
         self.h1, self.h3 = e(R, FFN), e(R, FFN)
-        self.curr_Q = [e(R, D_MODEL) for _ in range(num_lstt)]
-        self.curr_V = [e(R, D_MODEL) for _ in range(num_lstt)]
+        self.curr_Q = [e(R, D_MODEL) for _ in range(num_lstt)]      # = curr_K
+        self.curr_V = [e(R, D_MODEL) for _ in range(num_lstt)]      # LN2 output
         self.new_V = [e(R, D_MODEL) for _ in range(num_lstt)]       # linear_V(curr_V + id): the bank entry before it is scattered
         self.tgt3 = [e(R, D_MODEL) for _ in range(num_lstt)]
         self.short_K = [e(R, D_MODEL) for _ in range(num_lstt)]
@@ -129,6 +149,7 @@ class GroupRuntime:
         self.tmpB = [e(R, D_MODEL) for _ in range(num_lstt)]
         pos = sine_pos_emb(self.H16, self.W16).to(device)
         self.posb = pos.to(self.dt).repeat(B, 1).contiguous()
+        # pos @ [Wq; Wk]^T per layer (fp32, V columns zero): the residual operand of the fused self-attention QKV GEMM
         self.pos_qk = [torch.zeros(R, 3 * D_MODEL, dtype=F32, device=device) for _ in range(num_lstt)]
         self._pos_ready = False
         self.attn_ws = ops.attn_workspace(L, HEADS, MAX_CHUNKS, device, nclips=B)
@@ -145,6 +166,7 @@ class GroupRuntime:
         return max(len(s) for s in self.slots)
 
     def chunk_plan(self, T: int) -> Tuple[int, int]:
+        """(splits per memory frame, chunk count): keep >= ~8 key chunks in flight for small T."""
         if T > MAX_CHUNKS:
             raise ops.RmemError(f'memory bank of {T} frames exceeds the {MAX_CHUNKS}-chunk table')
         splits = max(1, min(8 // T, MAX_CHUNKS // T))
@@ -219,6 +241,7 @@ class GroupRuntime:
         return ops.scatter_blocks(src, bank, self.append_slots, nclips=self.B, block_bytes=nb, slot_bytes=nb)
 
     def prepare_pos(self, stream: int):
+        """One-off per runtime: pos_qk[i][:, :512] = bf16(pos) @ [Wq; Wk]^T (no bias; the QKV GEMM adds it)."""
         if self._pos_ready:
             return
         for i in range(self.NL):
@@ -240,6 +263,7 @@ class GroupRuntime:
         return self.enc_now.prog()
 
     def prog_project(self, e: Optional[int]) -> list:
+        """encoder_projector (models/aot.py:25-29): fp32 residual stream + bf16 copy into the decoder's concat buffer."""
         key = f'project_{e}'
         if key not in self._prog:
             self._prog[key] = [ops.conv2d(self._enc(e)[2], self.P['proj.w'], self.P['proj.b'], self.x, H=self.B * self.L, W=1,
@@ -247,8 +271,9 @@ class GroupRuntime:
         return self._prog[key]
 
     def prog_lstt(self, ref_mode: bool, T: int, want_mass: bool = True) -> list:
-        """ClipRuntime.prog_lstt over B clips (layers/transformer.py:553-692).  ref_mode: the frame's own K / V are computed
-        into curr_Q / new_V and scattered into each clip's first bank slot before the long-term read."""
+        """The 3-layer LSTT on self.x over B clips (layers/transformer.py:553-692).  ref_mode: reference frame (id_emb already in
+        self.id_emb): the frame's own K / V are computed into curr_Q / new_V and scattered into each clip's first bank slot before
+        the long-term read; else propagate against banks of T frames."""
         key = 'lstt_ref' if ref_mode else f'lstt_prop{T}{"m" if want_mass else ""}'
         if key in self._prog:
             return self._prog[key]
@@ -261,15 +286,17 @@ class GroupRuntime:
             return self._prog[key]
         for i in range(self.NL):
             d = f'l{i}'
+            # --- self attention (transformer.py:565-571)
             o.append(ops.layernorm256(self.x, P[d + '.ln1.g'], P[d + '.ln1.b'], M=R, y=self.t1b))
             o.append(self._lin(self.t1b, d + '.self_qkv', self.qkv, C, 3 * C, residual=self.pos_qk[i]))
             o.append(self._attn(self.qkv, 3 * C, self.qkv.view(-1)[C:], self.qkv.view(-1)[2 * C:], 3 * C, self.att,
                                 nchunks=PLAIN_CHUNKS, lk_single=L, kv_cs=L * 3 * C))
             o.append(self._lin(self.att, d + '.self_proj', self.x, C, C, residual=self.x))
+            # --- long/short-term attention (573-680)
             o.append(ops.layernorm256(self.x, P[d + '.ln2.g'], P[d + '.ln2.b'], M=R, y=self.curr_V[i]))
             cq = self.curr_Q[i]
             o.append(self._lin(self.curr_V[i], d + '.linear_Q', cq, C, C))
-            if ref_mode:
+            if ref_mode:                                            # curr_K is the bank's first entry
                 o.append(ops.add16(self.curr_V[i], self.id_emb, self.tmpB[i], R * C))
                 o.append(self._lin(self.tmpB[i], d + '.linear_V', self.new_V[i], C, C))
                 o.append(self._scatter(cq, self.bank_K[i]))
@@ -288,11 +315,13 @@ class GroupRuntime:
                 o.append(self._lin(self.tgt3[i], d + '.linear_QMem', self.short_K[i], C, C))
                 o.append(ops.add16(self.tgt3[i], self.id_emb, self.tmpA[i], R * C))
                 o.append(self._lin(self.tmpA[i], d + '.linear_VMem', self.short_V[i], C, C))
+            # --- feed-forward (683-687)
             o.append(ops.layernorm256(self.x, P[d + '.ln3.g'], P[d + '.ln3.b'], M=R, y=self.t3))
             o.append(self._lin(self.t3, d + '.linear1', self.h1, C, FFN))
             o.append(ops.gn_act_dwconv5x5(self.h1, P[d + '.gn.g'], P[d + '.gn.b'], P[d + '.dw.w'], self.h3, self.gn_ws, H=self.H16,
                                           W=self.W16, C=FFN, groups=32, act=2, images=B))
             o.append(self._lin(self.h3, d + '.linear2', self.x, FFN, C, residual=self.x))
+            # --- decoder norm of this layer's output into the concat buffer (248-259)
             o.append(ops.layernorm256(self.x, P[f'dec_norm{i}.g'], P[f'dec_norm{i}.b'], M=R,
                                       y=self.dec_in.view(-1)[(i + 1) * C:], ldy=4 * C))
         self._prog[key] = o
@@ -349,6 +378,7 @@ class GroupRuntime:
         return o
 
     def prog_decode(self, e: Optional[int]) -> list:
+        """FPN head (decoders/fpn.py:36-68) over the encoder outputs of _enc(e) -> self.logits at 1/4 resolution."""
         key = f'decode_{e}'
         if key in self._prog:
             return self._prog[key]
@@ -366,7 +396,6 @@ class GroupRuntime:
         o.append(self._conv(self.d16a, P['dec.conv_16x.w'], P['dec.conv_16x.b'], self.d16b, H=self.H16, W=self.W16, Cin=256, Cout=256,
                             KH=3, KW=3, pad=1))
         o.append(gn(self.d16b, 'dec.conv_16x', self.d16a, L, 256))
-        import os
         fuse_up = not os.environ.get('RMEM_NO_UPFUSE')      # timing experiments only
         # F.interpolate(x, size) + adapter(shortcut) (decoders/fpn.py:49-52): the resize happens in the GEMM's residual read
         if fuse_up:
@@ -422,13 +451,15 @@ class GroupRuntime:
         return o
 
     def prog_update(self, append: bool) -> list:
-        """Memory update of the frame just propagated for all clips (layers/transformer.py:269-322); with ``append`` the new bank
-        entries are scattered to the per-clip slots named by the device table."""
+        """Memory update of the frame just propagated for all clips (layers/transformer.py:269-322); self.id_emb holds the identity
+        embedding of the predicted masks.  With ``append`` the new bank entries (curr_K, linear_V(curr_V + id)) are scattered to
+        the per-clip slots named by the device table."""
         key = f'update_{int(append)}'
         if key in self._prog:
             return self._prog[key]
         P, NL, L, C, B = self.P, self.NL, self.L, D_MODEL, self.B
         R = B * L
+        # the layers' updates are independent: one launch per kind of op for all layers
         o = [ops.add16_grouped(self.tgt3 + (self.curr_V if append else []), [self.id_emb] * (NL * (2 if append else 1)),
                                   self.tmpA + (self.tmpB if append else []), R * C)]
         w = lambda nm: [P[f'l{i}.{nm}.w'] for i in range(NL)]   # noqa: E731

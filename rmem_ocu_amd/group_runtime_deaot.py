@@ -1,21 +1,32 @@
-"""Device state and launch lists for a GROUP of clips on the R50-DeAOTL path (throughput mode of runtime_deaot.DeAOTRuntime).
+"""Device state and launch lists of the R50-DeAOTL path (the model eval_vost.sh:11 runs), for one clip (the per-clip engines)
+or a GROUP of clips that advance in lockstep (GroupEngine).
 
-Same idea as group_runtime.GroupRuntime: B clips of equal length advance in lockstep and share one set of launch lists, so a
-frame of the whole group costs the host one hipGraph launch.  What is batched and what is not:
+``GroupRuntimeDeAOT`` keeps GroupRuntime's encoder, FPN decoder, identity-bank and memory-ring machinery and replaces the
+propagation stack by DualBranchGPM (layers/transformer.py:700-1008; one GatedPropagationModule per layer, 1011-1249):
 
-    every linear / LayerNorm / copy        one launch over B * HW rows (weights are shared, rows are independent);
+    per layer   LN(tgt) -> one GEMM [Q | SiLU V | SiLU U] (linear_QV + linear_U)             transformer.py:1102-1111
+                layers >= 1: LN(tgt_id) (= curr_ID_V), SiLU(linear_ID_U)                      1120-1124
+                long-term gated attention over the bank (K 128 wide, [V | ID_V] 1024 wide)    1141-1184
+                15x15 local gated attention over the previous frame                            1199-1200
+                each followed by depth-wise 5x5 + projection into BOTH residual streams        attention.py:208-211
+                LN(tgt), LN(tgt_id) -> one block-diagonal GEMM -> gated self-attention         1222-1232
+    final       GroupNorm1D(512, 2) over [tgt | tgt_id] -> the decoder's only LSTT input       760-808, models/deaot.py:56-62
+
+The two residual streams live side by side in one fp32 [B * HW, 512] buffer, so every projection (1024 -> 512) adds into both
+with one GEMM.  The bank stores what the reference concatenates at read time: K [B * S, HW, 128] and [V | ID_V]
+[B * S, HW, 1024] per layer (transformer.py:1179), clip c owns slots c * S ..; the 15x15 window memory is the same pair for the
+previous frame.  Appends go through the device table of destination slots (rmem_scatter_blocks) exactly as in GroupRuntime, so
+one captured graph per bank size serves every frame.
+
+As in group_runtime.GroupRuntime, B clips of equal length share one set of launch lists, so a frame of the whole group costs the
+host one hipGraph launch:
+
+    every linear / LayerNorm / copy         one launch over B * HW rows (weights are shared, rows are independent);
     convolutions, GroupNorm of the decoder  one launch over a batch of B images (statistics per clip);
-    the three gated attentions of a layer   ONE LAUNCH SEQUENCE PER CLIP (rmem_gated_attn / rmem_local_gated_attn have no clip
-                                            dimension: their split-K slabs and probability matrix are a per-call workspace) --
-                                            they run back to back on the group's stream over the clip's rows of the shared
-                                            buffers, against the clip's slots of the shared bank and its block of the key table;
+    the three gated attentions of a layer   one launch per kernel with a clip dimension (rmem_gated_attn_clips,
+                                            rmem_local_gated_attn_clips) over the clips' slots of the shared bank and their
+                                            blocks of the key table;
     the final GroupNorm1D over fp32 rows    per clip (statistics per clip, fp32 input form of the kernel).
-
-Bank layout: K [B * S, HW, 128] and [V | ID_V] [B * S, HW, 1024] per layer, clip c owns slots c * S ..; appends go through the
-device table of destination slots (rmem_scatter_blocks) exactly as in GroupRuntime, so one captured graph per bank size serves
-every frame.  All clips of a group hold banks of the same length (no mid-clip reference frames on this path: the engine refuses).
-
-The per-op arithmetic is DeAOTRuntime's (layers/transformer.py:1011-1249; citations there).
 """
 from __future__ import annotations
 
@@ -27,7 +38,12 @@ import torch
 from . import ops
 from .group_runtime import GroupRuntime
 from .runtime import D_MODEL, F32
-from .runtime_deaot import D_ATT, E1, E2, GP_ROWS, QVU, REL_LD, SQVU
+
+D_ATT, E1, E2 = 128, 512, 1024          # d_att, expand_d_model, expand_d_vu (transformer.py:1027-1034, attention.py:106-117)
+QVU = D_ATT + 2 * E1                     # [Q | V | U] columns of the fused GEMM
+SQVU = D_ATT + 2 * E2                    # [QK | V | U] columns of the fused self-attention GEMM
+REL_LD = 256                             # 225 relative-embedding logits padded to a 16-byte friendly row
+GP_ROWS = 64                             # chunk-table capacity of rmem_gated_attn
 
 
 def rows_per_frame(L: int, T: int, clips: int) -> int:
@@ -49,11 +65,11 @@ class GroupRuntimeDeAOT(GroupRuntime):
     def _alloc_lstt(self, R: int, num_lstt: int):
         dev, L = self.dev, self.L
         e = lambda *shape, dt=None: torch.empty(*shape, dtype=dt or self.dt, device=dev)  # noqa: E731
-        self.xc0 = torch.zeros(R, 2 * D_MODEL, dtype=F32, device=dev)   # [encoder projection | 0]
+        self.xc0 = torch.zeros(R, 2 * D_MODEL, dtype=F32, device=dev)   # [encoder projection | 0]: tgt and "tgt_id = 0" of layer 0
         self.xc = e(R, 2 * D_MODEL, dt=F32)                             # [tgt | tgt_id]
         self.n1 = e(R, D_MODEL)
-        self.qvu = [e(R, QVU) for _ in range(num_lstt)]
-        self.idcat = [None] + [e(R, 2 * D_MODEL) for _ in range(1, num_lstt)]
+        self.qvu = [e(R, QVU) for _ in range(num_lstt)]                 # Q = curr_K and SiLU(V) = curr_V stay until the update
+        self.idcat = [None] + [e(R, 2 * D_MODEL) for _ in range(1, num_lstt)]   # [LN(tgt_id) = curr_ID_V | id_emb]
         self.idu = e(R, E1)
         self.g2 = e(R, E2)
         self.rel = torch.zeros(R, REL_LD, dtype=F32, device=dev)
@@ -65,6 +81,7 @@ class GroupRuntimeDeAOT(GroupRuntime):
         self.gp_ws = None               # sized with the bank (needs self.S): see _gp()
 
     def _gp(self) -> torch.Tensor:
+        """probabilities [HW, slots * roundup(HW, 64)] bf16 + split-K slabs, sized for a full ring"""
         if self.gp_ws is None:
             self.gp_ws = ops.gated_workspace(self.L, E2, self.S, self.L, GP_ROWS, self.dev, nclips=self.B)
         return self.gp_ws
@@ -72,8 +89,10 @@ class GroupRuntimeDeAOT(GroupRuntime):
     def prepare_pos(self, stream: int):
         """GatedPropagationModule never adds the spatial positional embedding (with_pos_embed is unused, 1084-1089)."""
 
-    # ------------------------------------------------------------------ key table (same plan as DeAOTRuntime.chunk_plan)
+    # ------------------------------------------------------------------ key table
     def chunk_plan(self, T: int) -> Tuple[int, int]:
+        """rows_per_frame rows per memory frame (row boundaries cost nothing in the P.V kernel, and the score kernels get one
+        workgroup per (query tile, row)); key ranges start on 64-key tile boundaries."""
         if T > 32:
             raise ops.RmemError(f'memory bank of {T} frames exceeds the 32 frames the gated attention records mass for')
         splits = rows_per_frame(self.L, T, self.B)
@@ -89,7 +108,8 @@ class GroupRuntimeDeAOT(GroupRuntime):
         return t.view(-1)[c * self.L * ld + col:]
 
     def _long_attn(self, i: int, chunks: torch.Tensor, nchunks: int, frames: int, mass: Optional[torch.Tensor]):
-        """The long-term gated attention of layer i for ALL clips of the group: one launch per kernel (clip dimension)."""
+        """The long-term gated attention of layer i for ALL clips of the group: one launch per kernel (clip dimension).  The gate is
+        cat_curr_U = [SiLU(U) | ones] in layer 0, [SiLU(U) | SiLU(ID_U)] after (1115-1124)."""
         P, L = self.P, self.L
         ub = self.idu if i > 0 else None
         return ops.gated_attn(self.qvu[i], self.bank_K[i], self.bank_V[i], self.qvu[i].view(-1)[D_ATT + E1:],
@@ -123,7 +143,7 @@ class GroupRuntimeDeAOT(GroupRuntime):
         return self._prog[key]
 
     def prog_lstt(self, ref_mode: bool, T: int, want_mass: bool = True) -> list:
-        """DeAOTRuntime.prog_lstt over B clips.  ref_mode: every clip's frame is its own memory (1126-1136): the entry is written
+        """DualBranchGPM over B clips.  ref_mode: every clip's frame is its own memory (1126-1136): the entry is written
         to the window memory and scattered to the clip's first bank slot before the long-term read."""
         key = 'lstt_ref' if ref_mode else f'lstt_prop{T}{"m" if want_mass else ""}'
         if key in self._prog:

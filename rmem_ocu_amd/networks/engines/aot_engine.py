@@ -3,8 +3,9 @@
 ``AOTEngine`` mirrors networks/engines/aot_engine.py:18-568 (inference half) and
 ``AOTInferEngine`` mirrors 571-725: same method names, arguments, attributes
 (``long_term_mem_gap, input_size_2d, enc_size_2d, enc_hw, long_memories_indexes``) and
-error behaviour; the math runs as HIP launch lists (rmem_ocu_amd.runtime).  What stays on
-the host is exactly what the reference keeps in Python: the frame counter, the
+error behaviour; the math runs as the HIP launch lists of a one-clip
+rmem_ocu_amd.group_runtime.GroupRuntime (the class GroupEngine runs with clips = B).  What
+stays on the host is exactly what the reference keeps in Python: the frame counter, the
 "append every ``gap`` frames" rule (338-343), and the restricted-memory eviction policy
 (layers/transformer.py:324-436), restated in ``MemoryPolicy``.
 
@@ -23,7 +24,9 @@ import numpy as np
 import torch
 
 from ... import ops
-from ...runtime import ClipRuntime
+from ...group_runtime import GroupRuntime
+from ...group_runtime_deaot import GroupRuntimeDeAOT
+from ...runtime import MAX_CHUNKS
 
 F32 = torch.float32
 
@@ -76,7 +79,7 @@ class AOTEngine:
         # the reference's default-stream semantics
         self.stream = torch.cuda.Stream(self.device)
         self.sync_caller = True
-        self.rt: Optional[ClipRuntime] = None
+        self.rt: Optional[GroupRuntime] = None
         self.use_graphs = False
         self._graphs: Dict[str, ops.Graph] = {}
         self.restart_engine()
@@ -131,15 +134,15 @@ class AOTEngine:
     def _ensure_runtime(self, img):
         H, W = int(img.shape[-2]), int(img.shape[-1])
         n = self.cfg.FORMER_MEM_LEN + self.cfg.LATTER_MEM_LEN
-        slots = n + 1 if n < 64 else 16            # +1: the bank holds N+1 entries between append and eviction
+        # +1: a restricted bank holds N + 1 entries between append and eviction; unbounded: as many as the key table has rows
+        slots = n + 1 if n < MAX_CHUNKS else MAX_CHUNKS
         if self.rt is None or (self.rt.H, self.rt.W) != (H, W):
             P = self.AOT.packed()
-            if 'g0.qvu.w' in P:
-                from ...runtime_deaot import DeAOTRuntime as Runtime
-            else:
-                Runtime = ClipRuntime
-            self.rt = Runtime(P, (H, W), slots, self.device, self.cfg.MODEL_LSTT_NUM, self.align_corners, self.max_obj_num + 1)
-            self.img_in = torch.empty(3, H, W, dtype=F32, device=self.device)
+            Runtime = GroupRuntimeDeAOT if 'g0.qvu.w' in P else GroupRuntime
+            # one clip, no look-ahead encoder until encode_ahead asks for one
+            self.rt = Runtime(P, (H, W), slots, self.device, 1, self.cfg.MODEL_LSTT_NUM, self.align_corners, self.max_obj_num + 1,
+                              lookahead=1)
+            self.img_in = self.rt.enc_now.img_in[0]         # fixed address: what the encoder's pointer table names
             self.label_in = torch.empty(H, W, dtype=F32, device=self.device)
             self._graphs = {}
         return self.rt
@@ -151,7 +154,6 @@ class AOTEngine:
         if ab:
             prog = [o for o in prog if not any(t in o.name + ':' + getattr(o, 'tag', '') for t in ab.split(','))]
         if self.use_graphs:
-            key = f'{key}@{self.rt.bank_generation}'
             g = self._graphs.get(key)
             if g is None:
                 ops.run(prog, s)               # warm run (first-touch, lazy module load) outside capture
@@ -203,11 +205,12 @@ class AOTEngine:
             # (re)initialise the bank to this frame only (aot_engine.py:322; quirk: long_memories_indexes keeps growing, 323)
             rt.prepare_pos(self._stream())
             rt.reset_bank()
-            slot = rt.take_slot()
-            rt.slots.append(slot)
+            slot = rt.free[0].pop(0)
+            rt.slots[0].append(slot)
             rt.upload_chunks(self._stream())
-            self._run(f'ref{slot}', rt.prog_encode(self.img_in) + rt.prog_id_emb(self.label_in, rt.H, rt.W) +
-                      rt.prog_lstt(True, 1, slot) + rt.prog_decode())
+            rt.upload_append_slots([slot], self._stream())
+            self._run('ref', rt.prog_encode() + rt.prog_id_emb(self.label_in, rt.H, rt.W) + rt.prog_project(None) +
+                      rt.prog_lstt(True, 1) + rt.prog_decode(None))
             self.last_mem_step = frame_step
             self.policy = MemoryPolicy()
             self._indexes.append(self.frame_step)
@@ -222,10 +225,10 @@ class AOTEngine:
         self._resolve_pending()
         with self._scope() as cur:
             self._copy_in(self.img_in, img.reshape(3, rt.H, rt.W))
-            T = len(rt.slots)
+            T = len(rt.slots[0])
             self._T_at_propagate = T
             wm = self._mass_needed(T)
-            self._run(f'prop{T}{int(wm)}', rt.prog_encode(self.img_in) + rt.prog_lstt(False, T, want_mass=wm) + rt.prog_decode())
+            self._run(f'prop{T}{int(wm)}', rt.prog_encode() + rt.prog_project(None) + rt.prog_lstt(False, T, wm) + rt.prog_decode(None))
             self.pred_id_logits = rt.logits
             out = self._logits_out(output_size)
             out.record_stream(cur)
@@ -235,8 +238,7 @@ class AOTEngine:
         """Run the ResNet-50 encoder for the next ``imgs.shape[0] <= frames`` frames of the clip as one launch per layer
         (frames do not depend on each other before the LSTT; the reference's loader has them ready,
         dataloaders/eval_datasets.py:57-64).  propagate_to_label(..., enc_slot=e) then consumes frame e."""
-        rt = self.rt
-        be = rt.batch_encoder(frames)
+        rt, be = self.rt, self._ahead(frames)
         with self._scope():
             if imgs is not None:                      # None: the caller already put the frames into encode_inputs(frames)
                 n = int(imgs.shape[0])
@@ -248,7 +250,16 @@ class AOTEngine:
     def encode_inputs(self, frames: int = 4):
         """fp32 [frames, 3, H, W] input buffer of encode_ahead (e.g. the target of rmem_ingest_rgb8, so decoded uint8 frames
         go host -> device -> resize + normalise -> encoder without an extra copy)."""
-        return self.rt.batch_encoder(frames).img_in
+        return self._ahead(frames).img_in
+
+    def _ahead(self, frames: int):
+        """The engine's one look-ahead encoder of ``frames`` frames (look-ahead buffer 0 of the runtime), built on first use."""
+        rt = self.rt
+        if not rt.enc_bufs or rt.lookahead != frames:
+            rt.build_lookahead(1, frames)
+            # captured lists that run or read the previous look-ahead buffers
+            self._graphs = {k: g for k, g in self._graphs.items() if not k.startswith(('encB', 'propl'))}
+        return rt.enc_bufs[0]
 
     def propagate_to_label(self, img, label_u8, enc_slot=None):
         """Fused fast path of one frame: propagate, then argmax labels (uint8 [Ho, Wo], caller's device
@@ -261,7 +272,7 @@ class AOTEngine:
         Ho, Wo = int(label_u8.shape[-2]), int(label_u8.shape[-1])
         keep = self.obj_nums[0] if self.obj_nums else self.max_obj_num
         with self._scope():
-            T = len(rt.slots)
+            T = len(rt.slots[0])
             self._T_at_propagate = T
             pk = f'post_{label_u8.data_ptr()}_{Ho}_{Wo}'
             if pk not in rt._prog:
@@ -271,10 +282,10 @@ class AOTEngine:
             if enc_slot is None:
                 ops.copy_async(self.img_in, img, 3 * rt.H * rt.W * 4)(self._stream())
                 key = f'propl{T}{int(wm)}_{label_u8.data_ptr()}_{Ho}_{Wo}'
-                self._run(key, rt.prog_encode(self.img_in) + rt.prog_lstt(False, T, want_mass=wm) + rt.prog_decode() + rt._prog[pk])
+                self._run(key, rt.prog_encode() + rt.prog_project(None) + rt.prog_lstt(False, T, wm) + rt.prog_decode(None) + rt._prog[pk])
             else:
                 key = f'propl{T}{int(wm)}e{enc_slot}_{label_u8.data_ptr()}_{Ho}_{Wo}'
-                self._run(key, rt.prog_project(enc_slot) + rt.prog_lstt(False, T, want_mass=wm) + rt.prog_decode(enc_slot) + rt._prog[pk])
+                self._run(key, rt.prog_project(enc_slot) + rt.prog_lstt(False, T, wm) + rt.prog_decode(enc_slot) + rt._prog[pk])
             self.pred_id_logits = rt.logits
 
     def _mass_needed(self, T: int) -> bool:
@@ -340,26 +351,29 @@ class AOTEngine:
         rt, s = self.rt, self._stream()
         update_long = (not getattr(self.cfg, 'NO_LONG_MEMORY', False)) and \
             (self.frame_step - self.last_mem_step >= self.long_term_mem_gap)
-        slot = None
         if update_long:
+            if not rt.free[0]:
+                raise ops.RmemError(f'the memory bank outgrew the {rt.S} slots of the runtime '
+                                    f'(unbounded banks are limited by the {MAX_CHUNKS}-row key table)')
             self.last_mem_step = self.frame_step
-            slot = rt.take_slot()
-        self._run(f'upd_{slot}_{id_key}', id_prog + rt.prog_update(slot))
+            slot = rt.free[0].pop(0)
+            rt.upload_append_slots([slot], s)
+        self._run(f'upd{int(update_long)}_{id_key}', id_prog + rt.prog_update(update_long))
         if not update_long:
             return
-        rt.slots.append(slot)
+        rt.slots[0].append(slot)
         self._indexes.append(self.frame_step)
         n_keep = self.cfg.FORMER_MEM_LEN + self.cfg.LATTER_MEM_LEN
-        overflow = len(rt.slots) > n_keep
+        overflow = len(rt.slots[0]) > n_keep
         if overflow or self.policy_every_update:
             if not getattr(self, '_mass_valid', False):
                 raise RuntimeError('long_term_mem_gap / memory length changed between match_propogate_one_frame and update_memory: '
                                    'the attention mass of this frame was not recorded')
             Tp = self._T_at_propagate
             keep = self.obj_nums[0] if self.obj_nums else self.max_obj_num
-            ops.run([ops.evict_scores(rt.logits, rt.mass, rt.scores, ldl=16, nc=rt.nc, keep=keep, Hi=rt.H4, Wi=rt.W4,
+            ops.run([ops.evict_scores(rt.logits, rt.mass, rt.scores[0], ldl=16, nc=rt.nc, keep=keep, Hi=rt.H4, Wi=rt.W4,
                                       He=rt.H16, We=rt.W16, T=Tp),
-                     ops.copy_async(rt.scores_host, rt.scores, 4 * Tp)], s)
+                     ops.copy_async(rt.scores_host[0], rt.scores[0], 4 * Tp)], s)
             ev = torch.cuda.Event()
             ev.record(self.stream)
             self._pending_evict = (Tp, ev, overflow)
@@ -375,11 +389,11 @@ class AOTEngine:
         self._pending_evict = None
         ev.synchronize()                      # the one host wait of the policy (the reference syncs here too, transformer.py:353)
         rt = self.rt
-        drop = self.policy.choose(rt.scores_host[:Tp].clone(), self._indexes)
+        drop = self.policy.choose(rt.scores_host[0, :Tp].clone(), self._indexes)
         if not overflow:                      # DeAOT: the scores moved, nothing is dropped yet
             return
         self.drop_trace.append(drop)
-        rt.free.append(rt.slots.pop(drop))
+        rt.free[0].append(rt.slots[0].pop(drop))
         del self._indexes[drop]
         rt.upload_chunks(self._stream())
 

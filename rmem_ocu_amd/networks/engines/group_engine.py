@@ -29,7 +29,7 @@ import torch
 from ... import ops
 from ...group_runtime import GroupRuntime
 from ...group_runtime_deaot import GroupRuntimeDeAOT
-from ...runtime import MAX_CHUNKS, ClipRuntime
+from ...runtime import MAX_CHUNKS
 from .aot_engine import MemoryPolicy
 
 F32 = torch.float32
@@ -58,7 +58,7 @@ class GroupEngine:
         self._enc_free = [None, None]
         self.use_graphs = True
         self.rt: Optional[GroupRuntime] = None
-        self._side: Optional[ClipRuntime] = None
+        self._side: Optional[GroupRuntime] = None
         self._graphs: Dict[str, ops.Graph] = {}
         self.restart_engine()
 
@@ -88,14 +88,17 @@ class GroupEngine:
     def n_keep(self) -> int:
         return self.cfg.FORMER_MEM_LEN + self.cfg.LATTER_MEM_LEN
 
+    def _runtime(self, H: int, W: int, slots: int, clips: int, lookahead: int) -> GroupRuntime:
+        cls = GroupRuntimeDeAOT if self.deaot else GroupRuntime
+        return cls(self.AOT.packed(), (H, W), slots, self.device, clips, self.cfg.MODEL_LSTT_NUM, self.align_corners,
+                   self.max_obj_num + 1, lookahead)
+
     def _ensure_runtime(self, H: int, W: int):
         n = self.n_keep
         # +1: a restricted bank holds N + 1 entries between append and eviction; unbounded: as many as the key table has rows
         slots = n + 1 if n < MAX_CHUNKS else MAX_CHUNKS
         if self.rt is None or (self.rt.H, self.rt.W) != (H, W) or self.rt.S != slots:
-            cls = GroupRuntimeDeAOT if self.deaot else GroupRuntime
-            self.rt = cls(self.AOT.packed(), (H, W), slots, self.device, self.B, self.cfg.MODEL_LSTT_NUM, self.align_corners,
-                          self.max_obj_num + 1, self.lookahead)
+            self.rt = self._runtime(H, W, slots, self.B, self.lookahead)
             self.label_in = torch.empty(self.B, H, W, dtype=F32, device=self.device)
             self._graphs = {}
             self._side = None
@@ -145,38 +148,33 @@ class GroupEngine:
         """Mid-clip reference frame for ONE clip of the group (a new object's mask arrived, evaluator.py:484-508 ->
         aot_engine.py:675-702, 241-325): img fp32 [3, H, W] at the network size, label_u8 uint8 [Ho, Wo] (the merged label map;
         resized to the network size by nearest neighbour inside the one-hot kernel) at a FIXED address.  The frame runs through a
-        single-clip runtime in reference mode (same kernels); its K / V become the clip's only bank entry and its short-term
-        memory, the clip's long-term schedule restarts here, ``long_memories_indexes`` keeps growing (the reference's quirk, 323),
-        the eviction policy's state is reset (init_memory, transformer.py:438-443)."""
+        one-clip runtime of the group's class in reference mode (the same launch lists with clips = 1); its K / V become the clip's
+        only bank entry and its short-term memory, the clip's long-term schedule restarts here, ``long_memories_indexes`` keeps
+        growing (the reference's quirk, 323), the eviction policy's state is reset (init_memory, transformer.py:438-443)."""
         rt, c = self.rt, clip
         self._resolve_pending()
         if self._side is None:
-            if self.deaot:
-                from ...runtime_deaot import DeAOTRuntime as Side
-            else:
-                Side = ClipRuntime
-            self._side = Side(self.AOT.packed(), (rt.H, rt.W), 1, self.device, self.cfg.MODEL_LSTT_NUM, self.align_corners,
-                              self.max_obj_num + 1)
-            self._side_img = torch.empty(3, rt.H, rt.W, dtype=F32, device=self.device)
+            self._side = self._runtime(rt.H, rt.W, 1, 1, 1)         # one bank slot, one clip, no look-ahead
         side = self._side
         hs, ws = int(label_u8.shape[-2]), int(label_u8.shape[-1])
         L = rt.L
         with torch.cuda.stream(self.stream):
             s = self._s()
-            ops.copy_async(self._side_img, img.contiguous(), 3 * rt.H * rt.W * 4)(s)
+            ops.copy_async(side.enc_now.img_in, img.contiguous(), 3 * rt.H * rt.W * 4)(s)
             side.prepare_pos(s)
             side.reset_bank()
-            side.slots.append(side.take_slot())
+            side.slots[0].append(side.free[0].pop(0))
             side.upload_chunks(s)
-            ops.run(side.prog_encode(self._side_img) + side.prog_id_emb(label_u8, hs, ws) + side.prog_lstt(True, 1, side.slots[0]), s)
+            side.upload_append_slots(side.slots[0], s)
+            ops.run(side.prog_encode() + side.prog_id_emb(label_u8, hs, ws) + side.prog_project(None) + side.prog_lstt(True, 1), s)
             # the clip's bank := this frame only (aot_engine.py:322), short-term memory := this frame's (transformer.py:675-678)
             rt.free[c] = sorted(rt.free[c] + rt.slots[c])
             new = rt.free[c].pop(0)
             rt.slots[c] = [new]
             for i in range(rt.NL):
                 nk, nv = L * rt.bank_kw * 2, L * rt.bank_vw * 2          # bytes of one bank entry's keys / values
-                ops.copy_async(rt.bank_K[i][c * rt.S + new], side.bank_K[i][side.slots[0]], nk)(s)
-                ops.copy_async(rt.bank_V[i][c * rt.S + new], side.bank_V[i][side.slots[0]], nv)(s)
+                ops.copy_async(rt.bank_K[i][c * rt.S + new], side.bank_K[i][side.slots[0][0]], nk)(s)
+                ops.copy_async(rt.bank_V[i][c * rt.S + new], side.bank_V[i][side.slots[0][0]], nv)(s)
                 ops.copy_async(rt.short_K[i][c * L:(c + 1) * L], side.short_K[i], nk)(s)
                 ops.copy_async(rt.short_V[i][c * L:(c + 1) * L], side.short_V[i], nv)(s)
             rt.upload_chunks(s)

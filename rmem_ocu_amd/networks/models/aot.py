@@ -5,7 +5,7 @@ Mirrors networks/models/aot.py:12-105 at the interface level: the same attribute
 mem_pos_emb, cfg, max_obj_num``) and the same 362 ``state_dict`` keys, so a reference
 checkpoint loads with ``load_state_dict`` / utils/checkpoint.py:75-104 unchanged.
 The modules are parameter containers only: no torch op runs in ``forward``; the
-per-frame math is the launch lists of rmem_ocu_amd.runtime.ClipRuntime over
+per-frame math is the launch lists of rmem_ocu_amd.group_runtime.GroupRuntime over
 ``packed()`` (BN-folded, bf16, NHWC weights).  Unlike the reference (which keeps the
 clip's LSTT memory inside the shared model, layers/transformer.py:455-463), clip
 state lives in the engine, so one weight set serves many clips per GPU.

@@ -3,7 +3,7 @@
 Same construction as .aot.AOT with the DualBranchGPM stack in place of the LSTT: 356 ``state_dict`` keys
 (``LSTT.layers.i.{linear_QV, linear_U, linear_ID_V, linear_ID_U, long_term_attn, short_term_attn, self_attn, ...}``,
 ``LSTT.decoder_norms.0.gn``, ``id_norm``, 128-wide ``cur_pos_emb`` / ``mem_pos_emb``), so a reference R50-DeAOTL checkpoint
-(eval_vost.sh:26) loads with ``load_state_dict`` unchanged.  Per-frame math: rmem_ocu_amd.runtime_deaot.DeAOTRuntime.
+(eval_vost.sh:26) loads with ``load_state_dict`` unchanged.  Per-frame math: rmem_ocu_amd.group_runtime_deaot.GroupRuntimeDeAOT.
 """
 from __future__ import annotations
 

@@ -73,6 +73,8 @@ def _run(name, teacher_forced, use_graphs=False, dtype='bf16'):
         labels.append(label[0, 0].to(torch.uint8).cpu().numpy())
         samples.append(logit[0][:, ys, xs].cpu().numpy())
         trace.append(list(eng.long_memories_indexes))
+    # an engine that was never asked to look ahead holds no look-ahead encoder
+    assert all(e.rt.enc_bufs == [] for e in eng.aot_engines)
     return g, np.stack(labels), np.stack(samples), trace
 
 
@@ -135,7 +137,7 @@ def test_new_object_injection_clip():
 
 
 def test_unbounded_memory_clip():
-    """cfg-4 protocol: the bank grows past its initial ring (grow_bank), T up to 20, chunk table of 20 frames."""
+    """cfg-4 protocol: the bank grows by one entry per gap on the 32-slot ring, T up to 20, chunk table of 20 frames."""
     g, labels, samples, trace = _run('clip_unbounded.npz', True, use_graphs=True)
     ref = g['logit_samples']
     err = np.abs(samples - ref).max()
@@ -183,7 +185,7 @@ def test_swin_encoder_and_clip(dtype):
     the 'fp16' case runs every kernel through its _f16 entry point and is held to 8x tighter bounds."""
     tol_stage, tol_logit = (0.04, 0.045) if dtype == 'bf16' else (0.006, 0.008)
     from rmem_ocu_amd import build_engine, build_vos_model, get_config, ops
-    from rmem_ocu_amd.runtime import ClipRuntime
+    from rmem_ocu_amd.encoder_batch import SwinBatchEncoder
     from rmem_ocu_amd.weights import synth_state_dict
     dev = torch.device('cuda', 0)
     cfg = get_config('pre_vost', 'test', 'swinb_aotl')
@@ -196,11 +198,11 @@ def test_swin_encoder_and_clip(dtype):
     g = np.load(os.path.join(GOLDEN, 'swin_ops.npz'))
     rng = np.random.Generator(np.random.PCG64([2100, 0xC0FFEE]))
     img = torch.from_numpy(rng.standard_normal((1, 3, 96, 128)).astype(np.float32))
-    rt = ClipRuntime(model.packed(), (96, 128), 4, dev, 3, False, 11)
-    imgd = img[0].to(dev).contiguous()
-    ops.run(rt.prog_encode(imgd))
+    enc = SwinBatchEncoder(model.packed(), (96, 128), 1, dev)
+    enc.img_in[0].copy_(img[0].to(dev))
+    ops.run(enc.prog())
     torch.cuda.synchronize()
-    for i, (buf, (h, w, c)) in enumerate(zip((rt.enc1, rt.enc2, rt.enc3), ((24, 32, 128), (12, 16, 256), (6, 8, 512)))):
+    for i, (buf, (h, w, c)) in enumerate(zip(enc.enc_out, ((24, 32, 128), (12, 16, 256), (6, 8, 512)))):
         got = buf.view(-1)[: h * w * c].float().view(h, w, c).permute(2, 0, 1).cpu().numpy()
         ref = g[f'swin_x{i}']
         got = got[:, ::2, ::2] if i < 2 else got
@@ -546,6 +548,8 @@ def test_encoder_lookahead_matches_per_frame_path():
         while not slot.done:
             slot.step()
         eng.synchronize()
+        # look-ahead 4: exactly one look-ahead encoder, of 4 frames; none without look-ahead
+        assert [enc.B for enc in eng.aot_engines[0].rt.enc_bufs] == ([4] if la == 4 else [])
         out.append((slot.labels[:14].cpu().numpy().copy(), list(eng.long_memories_indexes)))
     (l1, t1), (l4, t4) = out
     agree = (l1[1:] == l4[1:]).mean()

@@ -95,6 +95,7 @@ def test_stage_error_budget(name, dtype):
     rt = inner.rt
     assert inner.long_memories_indexes == ora.long_memories_indexes
     L, C = rt.L, 256
+    enc = rt._enc(None)                                  # (enc1, enc2, enc3) of the frame in flight
     xs = ora.rec_xs                                      # [enc1, enc2, enc3, projector out]
     ref_dec_in = torch.cat([_nhwc(xs[-1])] + [o.reshape(L, C) for o in ora.rec_outs], dim=1)      # [L, 1024]
     ref_logits4 = _nhwc(ora.pred_id_logits)              # [M4, 11]
@@ -105,7 +106,7 @@ def test_stage_error_budget(name, dtype):
         table.setdefault(stage, {})[kind] = {'max': round(mx, 5), 'rms': round(rms, 5)}
 
     # ---- cumulative: the real pipeline's buffers at this frame ----
-    for k, (got, ref) in enumerate(zip((rt.enc1, rt.enc2, rt.enc3), xs[:3])):
+    for k, (got, ref) in enumerate(zip(enc, xs[:3])):
         row(f'encoder stage {k + 1}', 'cumulative', got.reshape(-1, ref.shape[1]), _nhwc(ref))
         row(f'encoder stage {k + 1}', 'intrinsic', got.reshape(-1, ref.shape[1]), _nhwc(ref))        # same image on both sides
     di = rt.dec_in.view(L, 4 * C)
@@ -119,17 +120,17 @@ def test_stage_error_budget(name, dtype):
 
     s = inner.stream.cuda_stream
     # ---- intrinsic, projector: oracle's encoder stage 3 in, projector out ----
-    enc3_save = rt.enc3.clone()
-    rt.enc3.copy_(_nhwc(xs[2]).to(dev).to(e16).view_as(rt.enc3))
-    ops.run([rt._proj_op(rt.enc_ch[2])], s)
+    enc3_save = enc[2].clone()
+    enc[2].copy_(_nhwc(xs[2]).to(dev).to(e16).view_as(enc[2]))
+    ops.run(rt.prog_project(None), s)
     inner.stream.synchronize()
     row('projector', 'intrinsic', rt.dec_in.view(L, 4 * C)[:, :C], ref_dec_in[:, :C])
     # ---- intrinsic, LSTT stack: oracle's projector output + oracle's memories ----
     rt.x.copy_(_nhwc(xs[-1]).to(dev))
-    T = len(rt.slots)
+    T = len(rt.slots[0])
     for i in range(3):
         lk, lv = ora.rec_long[i]
-        for t, slot in enumerate(rt.slots):
+        for t, slot in enumerate(rt.slots[0]):
             rt.bank_K[i][slot].copy_(lk[t].reshape(L, C).to(dev).to(e16))
             rt.bank_V[i][slot].copy_(lv[t].reshape(L, C).to(dev).to(e16))
         sk, sv = ora.rec_short[i]
@@ -143,13 +144,13 @@ def test_stage_error_budget(name, dtype):
             ref_dec_in[:, (i + 1) * C:(i + 2) * C])
     # ---- intrinsic, decoder: oracle's concat input and encoder shortcuts ----
     rt.dec_in.copy_(ref_dec_in.to(dev).to(e16).view_as(rt.dec_in))
-    for buf, ref in zip((rt.enc1, rt.enc2, rt.enc3), xs[:3]):
+    for buf, ref in zip(enc, xs[:3]):
         buf.copy_(_nhwc(ref).to(dev).to(e16).view_as(buf))
     torch.cuda.synchronize()
-    ops.run(rt.prog_decode(), s)
+    ops.run(rt.prog_decode(None), s)
     inner.stream.synchronize()
     row('logits (1/4 res)', 'intrinsic', rt.logits.view(-1, 16)[:, :11], ref_logits4)
-    rt.enc3.copy_(enc3_save)
+    enc[2].copy_(enc3_save)
 
     print(f'\n{name} [{dtype}]: frame {n_run - 1}, bank T = {T}, logit std {ref_logits4.std().item():.3f}, label flips {100 * flips_cum:.4f} %')
     print(f'{"stage":34s} {"cumulative max / rms":>24s} {"intrinsic max / rms":>24s}')
