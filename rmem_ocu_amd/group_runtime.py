@@ -473,3 +473,12 @@ class GroupRuntime:
                 o.append(self._scatter(self.new_V[i], self.bank_V[i]))
         self._prog[key] = o
         return o
+
+
+def runtime_for(model, in_hw: Tuple[int, int], bank_slots: int, device, clips: int, lookahead: int) -> GroupRuntime:
+    """The runtime of ``clips`` clips for a model: the class follows the packed weights (the R50-DeAOTL pack has the gated
+    propagation's ``qvu`` projections), which is what GroupRuntime.__init__ checks."""
+    from .group_runtime_deaot import GroupRuntimeDeAOT
+    P, cfg = model.packed(), model.cfg
+    cls = GroupRuntimeDeAOT if 'g0.qvu.w' in P else GroupRuntime
+    return cls(P, in_hw, bank_slots, device, clips, cfg.MODEL_LSTT_NUM, cfg.MODEL_ALIGN_CORNERS, model.max_obj_num + 1, lookahead)

@@ -7,7 +7,7 @@ error behaviour; the math runs as the HIP launch lists of a one-clip
 rmem_ocu_amd.group_runtime.GroupRuntime (the class GroupEngine runs with clips = B).  What
 stays on the host is exactly what the reference keeps in Python: the frame counter, the
 "append every ``gap`` frames" rule (338-343), and the restricted-memory eviction policy
-(layers/transformer.py:324-436), restated in ``MemoryPolicy``.
+(layers/transformer.py:324-436): both live in rmem_ocu_amd.bank_schedule.BankSchedule, which the engine holds with clips = 1.
 
 Differences by design: clip state is engine-owned (the reference stores it in
 the shared model); bs = 1 per engine (the reference asserts it in eval,
@@ -17,47 +17,16 @@ layers/transformer.py:641); the attention-weight top-32 D2H of every layer
 from __future__ import annotations
 
 import contextlib
-import os
-from typing import Dict, List, Optional
+from typing import List, Optional
 
 import numpy as np
 import torch
 
 from ... import ops
-from ...group_runtime import GroupRuntime
-from ...group_runtime_deaot import GroupRuntimeDeAOT
-from ...runtime import MAX_CHUNKS
+from ...bank_schedule import BankSchedule, MemoryPolicy, bank_slots       # noqa: F401  (MemoryPolicy: part of this module's surface)
+from ...group_runtime import GroupRuntime, runtime_for
 
 F32 = torch.float32
-
-
-class MemoryPolicy:
-    """Which bank entry to evict (layers/transformer.py:338-411, eval branch).
-
-    Inputs are the per-memory-frame attention mass of layer 0 weighted by the
-    foreground probability (already reduced over tokens on the device); the EMA (0.8) with the
-    stored score of the same frame index, the UCB bonus 1.5*sqrt(log(sum n)/(n_i+8)) with
-    n_0 := T', and the argmin over entries >= 1 are evaluated here in fp32 torch CPU ops,
-    the same arithmetic the reference runs.
-    """
-
-    def __init__(self):
-        self.ema: Dict[int, torch.Tensor] = {}
-        self.visits: Dict[int, int] = {}
-
-    def choose(self, scores: torch.Tensor, indexes: List[int]) -> int:
-        a = (scores / scores.sum()).clone()
-        cur = {indexes[i]: a[i].clone() for i in range(a.shape[0])}
-        cur = {k: ((1 - 0.8) * self.ema[k] + 0.8 * v) if k in self.ema else v for k, v in cur.items()}
-        self.ema = cur
-        for i in range(a.shape[0]):
-            a[i] = cur[indexes[i]]
-        self.visits = {k: 1 + self.visits.get(k, 0) for k in indexes}
-        n = torch.tensor([float(self.visits[k]) for k in indexes[:-1]])
-        n[0] = len(n)
-        a = a + 1.5 * torch.sqrt(torch.log(n.sum()) / (n + 8))
-        rest = a[1:]
-        return int(torch.argmin(rest).item()) + 1 if rest.shape[0] > 0 else 1
 
 
 class AOTEngine:
@@ -81,7 +50,8 @@ class AOTEngine:
         self.sync_caller = True
         self.rt: Optional[GroupRuntime] = None
         self.use_graphs = False
-        self._graphs: Dict[str, ops.Graph] = {}
+        self._graphs = ops.GraphCache()
+        self.bank = BankSchedule(self, 1)
         self.restart_engine()
 
     # ------------------------------------------------------------------ state
@@ -90,19 +60,12 @@ class AOTEngine:
             raise NotImplementedError('inference engine: batch_size 1, no id shuffle (layers/transformer.py:641)')
         self.batch_size = 1
         self.frame_step = 0
-        self.last_mem_step = -1
         self.obj_nums = None
         self.input_size_2d = None
         self.enc_size_2d = None
         self.enc_hw = None
-        self._indexes: List[int] = []
-        self._pending_evict = None
-        self.policy = MemoryPolicy()
-        self.drop_trace: List[int] = []
         self.pred_id_logits = None
-        self._T_at_propagate = 0
-        if self.rt is not None:
-            self.rt.reset_bank()
+        self.bank.restart(self.rt)
 
     def eval(self):
         return self
@@ -110,8 +73,15 @@ class AOTEngine:
     @property
     def long_memories_indexes(self) -> List[int]:
         """Frame indexes of the bank entries (aot_engine.py:323, 351); resolves a deferred eviction first."""
-        self._resolve_pending()
-        return self._indexes
+        return self.bank.long_memories_indexes(0)
+
+    @property
+    def drop_trace(self) -> List[int]:
+        return self.bank.drop_trace[0]
+
+    @property
+    def last_mem_step(self) -> int:
+        return self.bank.last_mem_step[0]
 
     def update_size(self, input_size, enc_size):
         self.input_size_2d = tuple(int(v) for v in input_size)
@@ -133,35 +103,17 @@ class AOTEngine:
 
     def _ensure_runtime(self, img):
         H, W = int(img.shape[-2]), int(img.shape[-1])
-        n = self.cfg.FORMER_MEM_LEN + self.cfg.LATTER_MEM_LEN
-        # +1: a restricted bank holds N + 1 entries between append and eviction; unbounded: as many as the key table has rows
-        slots = n + 1 if n < MAX_CHUNKS else MAX_CHUNKS
         if self.rt is None or (self.rt.H, self.rt.W) != (H, W):
-            P = self.AOT.packed()
-            Runtime = GroupRuntimeDeAOT if 'g0.qvu.w' in P else GroupRuntime
             # one clip, no look-ahead encoder until encode_ahead asks for one
-            self.rt = Runtime(P, (H, W), slots, self.device, 1, self.cfg.MODEL_LSTT_NUM, self.align_corners, self.max_obj_num + 1,
-                              lookahead=1)
+            self.rt = runtime_for(self.AOT, (H, W), bank_slots(self.bank.n_keep), self.device, 1, lookahead=1)
             self.img_in = self.rt.enc_now.img_in[0]         # fixed address: what the encoder's pointer table names
             self.label_in = torch.empty(H, W, dtype=F32, device=self.device)
-            self._graphs = {}
+            self._graphs = ops.GraphCache()
         return self.rt
 
     def _run(self, key: str, prog: list):
         """Enqueue a launch list on the engine's stream: directly, or (use_graphs) as ONE hipGraph per key."""
-        s = self._stream()
-        ab = os.environ.get('RMEM_ABLATE')           # timing experiments only: drop every launch whose name contains the tag
-        if ab:
-            prog = [o for o in prog if not any(t in o.name + ':' + getattr(o, 'tag', '') for t in ab.split(','))]
-        if self.use_graphs:
-            g = self._graphs.get(key)
-            if g is None:
-                ops.run(prog, s)               # warm run (first-touch, lazy module load) outside capture
-                g = self._graphs[key] = ops.Graph(prog, s)
-            else:
-                g(s)
-        else:
-            ops.run(prog, s)
+        self._graphs.run(key, prog, self._stream(), self.use_graphs)
 
     def _set_label(self, mask):
         m = mask.reshape(mask.shape[-2], mask.shape[-1])
@@ -192,10 +144,6 @@ class AOTEngine:
         if mask is None:
             print('No mask for reference frame!')
             exit()
-        # a deferred eviction belongs to the bank that is about to be reset, but its effect on long_memories_indexes
-        # (the reference keeps that list across the reset, aot_engine.py:323) and on the policy state must still happen --
-        # against the runtime it was issued on: a frame of another size replaces self.rt below
-        self._resolve_pending()
         rt = self._ensure_runtime(img)
         if self.input_size_2d is None:
             self.update_size(img.shape[2:], (rt.H16, rt.W16))
@@ -204,16 +152,9 @@ class AOTEngine:
             self._set_label(mask)
             # (re)initialise the bank to this frame only (aot_engine.py:322; quirk: long_memories_indexes keeps growing, 323)
             rt.prepare_pos(self._stream())
-            rt.reset_bank()
-            slot = rt.free[0].pop(0)
-            rt.slots[0].append(slot)
-            rt.upload_chunks(self._stream())
-            rt.upload_append_slots([slot], self._stream())
+            self.bank.start_reference(rt, mem_step=frame_step)
             self._run('ref', rt.prog_encode() + rt.prog_id_emb(self.label_in, rt.H, rt.W) + rt.prog_project(None) +
                       rt.prog_lstt(True, 1) + rt.prog_decode(None))
-            self.last_mem_step = frame_step
-            self.policy = MemoryPolicy()
-            self._indexes.append(self.frame_step)
             self.pred_id_logits = rt.logits
 
     # ------------------------------------------------------------------ propagate
@@ -222,12 +163,9 @@ class AOTEngine:
         if img is None:
             raise ValueError('match_propogate_one_frame needs the frame (offline encoding is a training-only path)')
         rt = self.rt
-        self._resolve_pending()
+        T, wm = self.bank.begin_propagation(rt)
         with self._scope() as cur:
             self._copy_in(self.img_in, img.reshape(3, rt.H, rt.W))
-            T = len(rt.slots[0])
-            self._T_at_propagate = T
-            wm = self._mass_needed(T)
             self._run(f'prop{T}{int(wm)}', rt.prog_encode() + rt.prog_project(None) + rt.prog_lstt(False, T, wm) + rt.prog_decode(None))
             self.pred_id_logits = rt.logits
             out = self._logits_out(output_size)
@@ -258,7 +196,7 @@ class AOTEngine:
         if not rt.enc_bufs or rt.lookahead != frames:
             rt.build_lookahead(1, frames)
             # captured lists that run or read the previous look-ahead buffers
-            self._graphs = {k: g for k, g in self._graphs.items() if not k.startswith(('encB', 'propl'))}
+            self._graphs.drop(('encB', 'propl'))
         return rt.enc_bufs[0]
 
     def propagate_to_label(self, img, label_u8, enc_slot=None):
@@ -268,17 +206,13 @@ class AOTEngine:
         enc_slot: the frame was encoded by encode_ahead (slot index); img is then unused."""
         self.frame_step += 1
         rt = self.rt
-        self._resolve_pending()
+        T, wm = self.bank.begin_propagation(rt)
         Ho, Wo = int(label_u8.shape[-2]), int(label_u8.shape[-1])
-        keep = self.obj_nums[0] if self.obj_nums else self.max_obj_num
         with self._scope():
-            T = len(rt.slots[0])
-            self._T_at_propagate = T
             pk = f'post_{label_u8.data_ptr()}_{Ho}_{Wo}'
             if pk not in rt._prog:
-                rt._prog[pk] = [ops.logits_post(rt.logits, ldl=16, nc=rt.nc, keep=keep, Hi=rt.H4, Wi=rt.W4, Ho=Ho, Wo=Wo,
+                rt._prog[pk] = [ops.logits_post(rt.logits, ldl=16, nc=rt.nc, keep=self._keep(), Hi=rt.H4, Wi=rt.W4, Ho=Ho, Wo=Wo,
                                                 align_corners=self.align_corners, label_u8=label_u8)]
-            wm = self._mass_needed(T)
             if enc_slot is None:
                 ops.copy_async(self.img_in, img, 3 * rt.H * rt.W * 4)(self._stream())
                 key = f'propl{T}{int(wm)}_{label_u8.data_ptr()}_{Ho}_{Wo}'
@@ -288,15 +222,9 @@ class AOTEngine:
                 self._run(key, rt.prog_project(enc_slot) + rt.prog_lstt(False, T, wm) + rt.prog_decode(enc_slot) + rt._prog[pk])
             self.pred_id_logits = rt.logits
 
-    def _mass_needed(self, T: int) -> bool:
-        """The per-memory-frame attention mass of layer 0 (layers/transformer.py:636-643) is only read by the eviction policy,
-        i.e. when the update that follows this propagation appends to the bank (aot_engine.py:338-343) and the bank then
-        overflows (or, DeAOT, on every append): both are known now, so the other frames skip the reduction."""
-        will_append = (not getattr(self.cfg, 'NO_LONG_MEMORY', False)) and \
-            (self.frame_step - self.last_mem_step >= self.long_term_mem_gap)
-        need = will_append and (self.policy_every_update or T + 1 > self.cfg.FORMER_MEM_LEN + self.cfg.LATTER_MEM_LEN)
-        self._mass_valid = need
-        return need
+    def _keep(self) -> int:
+        """Highest object id in use: logits and eviction scores mask the ids above it (aot_engine.py:450-453)."""
+        return self.obj_nums[0] if self.obj_nums else self.max_obj_num
 
     def decode_current_logits(self, output_size=None):
         """Logits with unused ids masked (aot_engine.py:450-453), resized to output_size (457-463)."""
@@ -309,8 +237,7 @@ class AOTEngine:
         rt = self.rt
         Ho, Wo = (rt.H4, rt.W4) if output_size is None else (int(output_size[0]), int(output_size[1]))
         out = torch.empty(1, rt.nc, Ho, Wo, dtype=F32, device=self.device)
-        keep = self.obj_nums[0] if self.obj_nums else self.max_obj_num
-        ops.run(ops.logits_post(rt.logits, ldl=16, nc=rt.nc, keep=keep, Hi=rt.H4, Wi=rt.W4, Ho=Ho, Wo=Wo,
+        ops.run(ops.logits_post(rt.logits, ldl=16, nc=rt.nc, keep=self._keep(), Hi=rt.H4, Wi=rt.W4, Ho=Ho, Wo=Wo,
                                 align_corners=self.align_corners, out=out), self._stream())
         return out
 
@@ -333,7 +260,7 @@ class AOTEngine:
             self._set_label(curr_mask)
             self._finish_update('lab', rt.prog_id_emb(self.label_in, rt.H, rt.W))
         if self.sync_caller:
-            self._resolve_pending()
+            self.bank.resolve()          # drop-in semantics: long_memories_indexes is exact when the call returns
 
     def update_memory_from_label_u8(self, label_u8: torch.Tensor):
         """Fast path: argmax labels at the OUTPUT size (uint8 [Ho, Wo], device); the nearest resize to the
@@ -345,57 +272,13 @@ class AOTEngine:
 
     def _finish_update(self, id_key: str, id_prog: list):
         """Memory update of the frame just propagated (aot_engine.py:327-369).  The launch list (identity embedding +
-        short-term update [+ bank append]) is one graph; if the bank now exceeds its size the eviction scores are
-        reduced on the device and read back asynchronously -- the decision itself is taken lazily
-        (_resolve_pending) right before the bank is used again, so the host never waits here."""
-        rt, s = self.rt, self._stream()
-        update_long = (not getattr(self.cfg, 'NO_LONG_MEMORY', False)) and \
-            (self.frame_step - self.last_mem_step >= self.long_term_mem_gap)
-        if update_long:
-            if not rt.free[0]:
-                raise ops.RmemError(f'the memory bank outgrew the {rt.S} slots of the runtime '
-                                    f'(unbounded banks are limited by the {MAX_CHUNKS}-row key table)')
-            self.last_mem_step = self.frame_step
-            slot = rt.free[0].pop(0)
-            rt.upload_append_slots([slot], s)
-        self._run(f'upd{int(update_long)}_{id_key}', id_prog + rt.prog_update(update_long))
-        if not update_long:
-            return
-        rt.slots[0].append(slot)
-        self._indexes.append(self.frame_step)
-        n_keep = self.cfg.FORMER_MEM_LEN + self.cfg.LATTER_MEM_LEN
-        overflow = len(rt.slots[0]) > n_keep
-        if overflow or self.policy_every_update:
-            if not getattr(self, '_mass_valid', False):
-                raise RuntimeError('long_term_mem_gap / memory length changed between match_propogate_one_frame and update_memory: '
-                                   'the attention mass of this frame was not recorded')
-            Tp = self._T_at_propagate
-            keep = self.obj_nums[0] if self.obj_nums else self.max_obj_num
-            ops.run([ops.evict_scores(rt.logits, rt.mass, rt.scores[0], ldl=16, nc=rt.nc, keep=keep, Hi=rt.H4, Wi=rt.W4,
-                                      He=rt.H16, We=rt.W16, T=Tp),
-                     ops.copy_async(rt.scores_host[0], rt.scores[0], 4 * Tp)], s)
-            ev = torch.cuda.Event()
-            ev.record(self.stream)
-            self._pending_evict = (Tp, ev, overflow)
-        if not overflow:
-            rt.upload_chunks(s)
-
-    def _resolve_pending(self):
-        """Finish a deferred eviction: wait for the score readback (normally long done), run the policy on the host
-        (layers/transformer.py:353-411), drop the entry from the slot table and upload the new chunk table."""
-        if self._pending_evict is None:
-            return
-        Tp, ev, overflow = self._pending_evict
-        self._pending_evict = None
-        ev.synchronize()                      # the one host wait of the policy (the reference syncs here too, transformer.py:353)
+        short-term update [+ bank append]) is one graph; whether the bank is appended to, and the eviction that may follow
+        (decided lazily, right before the bank is used again, so the host never waits here), is the schedule's."""
         rt = self.rt
-        drop = self.policy.choose(rt.scores_host[0, :Tp].clone(), self._indexes)
-        if not overflow:                      # DeAOT: the scores moved, nothing is dropped yet
-            return
-        self.drop_trace.append(drop)
-        rt.free[0].append(rt.slots[0].pop(drop))
-        del self._indexes[drop]
-        rt.upload_chunks(self._stream())
+        slots = self.bank.take_append_slots(rt)
+        update_long = slots[0] >= 0
+        self._run(f'upd{int(update_long)}_{id_key}', id_prog + rt.prog_update(update_long))
+        self.bank.commit_update(rt, slots, self._keep())
 
 
 class AOTInferEngine:

@@ -3,9 +3,9 @@
 ``GroupEngine`` is the batched counterpart of AOTEngine/AOTInferEngine (aot_engine.py) for clips with <= 10 objects whose
 label masks are fed back.  Per clip it keeps exactly the host state AOTEngine keeps -- bank slot order,
 ``long_memories_indexes``, the eviction policy's EMA scores and visit counts (networks/layers/transformer.py:338-411), the
-frame of the last long-term update (aot_engine.py:338-343) -- while the frame counter is shared, because clips of one length
-get one gap (managers/evaluator.py:330-335).  All device work goes through rmem_ocu_amd.group_runtime.GroupRuntime: one
-launch per layer for the whole group.
+frame of the last long-term update (aot_engine.py:338-343), all in one rmem_ocu_amd.bank_schedule.BankSchedule with
+clips = B -- while the frame counter is shared, because clips of one length get one gap (managers/evaluator.py:330-335).
+All device work goes through rmem_ocu_amd.group_runtime.GroupRuntime: one launch per layer for the whole group.
 
 Covered protocols (the reference's evaluator, managers/evaluator.py:385-523):
   * restricted banks (N = former + latter, eviction by the RMem policy) and UNBOUNDED banks (latter_mem_len = 9999,
@@ -22,15 +22,13 @@ Clips with > 10 objects and multi-scale / flip testing run on the per-clip engin
 """
 from __future__ import annotations
 
-from typing import Dict, Iterable, List, Optional
+from typing import Iterable, List, Optional
 
 import torch
 
 from ... import ops
-from ...group_runtime import GroupRuntime
-from ...group_runtime_deaot import GroupRuntimeDeAOT
-from ...runtime import MAX_CHUNKS
-from .aot_engine import MemoryPolicy
+from ...bank_schedule import BankSchedule, bank_slots
+from ...group_runtime import GroupRuntime, runtime_for
 
 F32 = torch.float32
 
@@ -40,8 +38,7 @@ class GroupEngine:
         self.cfg = aot_model.cfg
         self.AOT = aot_model
         self.B = clips
-        self.deaot = self.cfg.MODEL_VOS == 'deaot'
-        self.policy_every_update = self.deaot      # DeAOTEngine.policy_every_update
+        self.policy_every_update = self.cfg.MODEL_VOS == 'deaot'      # DeAOTEngine.policy_every_update
         self.gpu_id = gpu_id
         self.device = torch.device('cuda', gpu_id)
         self.align_corners = self.cfg.MODEL_ALIGN_CORNERS
@@ -59,62 +56,37 @@ class GroupEngine:
         self.use_graphs = True
         self.rt: Optional[GroupRuntime] = None
         self._side: Optional[GroupRuntime] = None
-        self._graphs: Dict[str, ops.Graph] = {}
+        self._graphs = ops.GraphCache()
+        self.bank = BankSchedule(self, clips)
         self.restart_engine()
 
     # ------------------------------------------------------------------ state
     def restart_engine(self):
         self.frame_step = 0
-        self.last_mem_step: List[int] = [-1] * self.B
         self.obj_nums = None
-        self._indexes: List[List[int]] = [[] for _ in range(self.B)]
-        self.policies = [MemoryPolicy() for _ in range(self.B)]
-        self.drop_trace: List[List[int]] = [[] for _ in range(self.B)]
-        self._pending = None
-        self._mass_valid = False
-        self._T_at_propagate = 0
-        self._Tc_at_propagate: List[int] = [0] * self.B
-        if self.rt is not None:
-            self.rt.reset_bank()
+        self.bank.restart(self.rt)
 
     def long_memories_indexes(self, clip: int) -> List[int]:
-        self._resolve_pending()
-        return self._indexes[clip]
+        return self.bank.long_memories_indexes(clip)
+
+    @property
+    def drop_trace(self) -> List[List[int]]:
+        return self.bank.drop_trace
 
     def _s(self) -> int:
         return self.stream.cuda_stream
 
-    @property
-    def n_keep(self) -> int:
-        return self.cfg.FORMER_MEM_LEN + self.cfg.LATTER_MEM_LEN
-
-    def _runtime(self, H: int, W: int, slots: int, clips: int, lookahead: int) -> GroupRuntime:
-        cls = GroupRuntimeDeAOT if self.deaot else GroupRuntime
-        return cls(self.AOT.packed(), (H, W), slots, self.device, clips, self.cfg.MODEL_LSTT_NUM, self.align_corners,
-                   self.max_obj_num + 1, lookahead)
-
     def _ensure_runtime(self, H: int, W: int):
-        n = self.n_keep
-        # +1: a restricted bank holds N + 1 entries between append and eviction; unbounded: as many as the key table has rows
-        slots = n + 1 if n < MAX_CHUNKS else MAX_CHUNKS
+        slots = bank_slots(self.bank.n_keep)
         if self.rt is None or (self.rt.H, self.rt.W) != (H, W) or self.rt.S != slots:
-            self.rt = self._runtime(H, W, slots, self.B, self.lookahead)
+            self.rt = runtime_for(self.AOT, (H, W), slots, self.device, self.B, self.lookahead)
             self.label_in = torch.empty(self.B, H, W, dtype=F32, device=self.device)
-            self._graphs = {}
+            self._graphs = ops.GraphCache()
             self._side = None
         return self.rt
 
     def _run(self, key: str, prog: list, s: Optional[int] = None):
-        s = self._s() if s is None else s
-        if self.use_graphs:
-            g = self._graphs.get(key)
-            if g is None:
-                ops.run(prog, s)
-                self._graphs[key] = ops.Graph(prog, s)
-            else:
-                g(s)
-        else:
-            ops.run(prog, s)
+        self._graphs.run(key, prog, self._s() if s is None else s, self.use_graphs)
 
     # ------------------------------------------------------------------ reference frames (aot_engine.py:241-325, all clips at once)
     def add_reference_frames(self, imgs: torch.Tensor, masks: torch.Tensor, obj_nums: int):
@@ -123,26 +95,14 @@ class GroupEngine:
         H, W = int(imgs.shape[-2]), int(imgs.shape[-1])
         rt = self._ensure_runtime(H, W)
         self.obj_nums = [self.max_obj_num]            # AOTInferEngine forces this (aot_engine.py:697)
-        self._pending = None
         with torch.cuda.stream(self.stream):
             s = self._s()
             ops.copy_async(rt.enc_now.img_in, imgs.contiguous(), B * 3 * H * W * 4)(s)
             self.label_in.copy_(masks.reshape(B, H, W), non_blocking=True)
             rt.prepare_pos(s)
-            rt.reset_bank()
-            first = []
-            for c in range(B):
-                sl = rt.free[c].pop(0)
-                rt.slots[c].append(sl)
-                first.append(sl)
-            rt.upload_chunks(s)
-            rt.upload_append_slots(first, s)
+            self.bank.start_reference(rt)
             self._run('ref', rt.prog_encode() + rt.prog_id_emb(self.label_in, H, W) + rt.prog_project(None) + rt.prog_lstt(True, 1) +
                       rt.prog_decode(None))
-        self.last_mem_step = [self.frame_step] * B
-        self.policies = [MemoryPolicy() for _ in range(B)]
-        for c in range(B):
-            self._indexes[c].append(self.frame_step)
 
     def add_reference_frame_for(self, clip: int, img: torch.Tensor, label_u8: torch.Tensor):
         """Mid-clip reference frame for ONE clip of the group (a new object's mask arrived, evaluator.py:484-508 ->
@@ -152,9 +112,8 @@ class GroupEngine:
         only bank entry and its short-term memory, the clip's long-term schedule restarts here, ``long_memories_indexes`` keeps
         growing (the reference's quirk, 323), the eviction policy's state is reset (init_memory, transformer.py:438-443)."""
         rt, c = self.rt, clip
-        self._resolve_pending()
         if self._side is None:
-            self._side = self._runtime(rt.H, rt.W, 1, 1, 1)         # one bank slot, one clip, no look-ahead
+            self._side = runtime_for(self.AOT, (rt.H, rt.W), 1, self.device, 1, 1)         # one bank slot, one clip, no look-ahead
         side = self._side
         hs, ws = int(label_u8.shape[-2]), int(label_u8.shape[-1])
         L = rt.L
@@ -162,25 +121,16 @@ class GroupEngine:
             s = self._s()
             ops.copy_async(side.enc_now.img_in, img.contiguous(), 3 * rt.H * rt.W * 4)(s)
             side.prepare_pos(s)
-            side.reset_bank()
-            side.slots[0].append(side.free[0].pop(0))
-            side.upload_chunks(s)
-            side.upload_append_slots(side.slots[0], s)
+            src = BankSchedule.restart_banks(side, [0], s)[0]
             ops.run(side.prog_encode() + side.prog_id_emb(label_u8, hs, ws) + side.prog_project(None) + side.prog_lstt(True, 1), s)
             # the clip's bank := this frame only (aot_engine.py:322), short-term memory := this frame's (transformer.py:675-678)
-            rt.free[c] = sorted(rt.free[c] + rt.slots[c])
-            new = rt.free[c].pop(0)
-            rt.slots[c] = [new]
+            new = self.bank.start_reference(rt, [c], append_table=False)[c]      # the entry is copied in, not appended by a launch
             for i in range(rt.NL):
                 nk, nv = L * rt.bank_kw * 2, L * rt.bank_vw * 2          # bytes of one bank entry's keys / values
-                ops.copy_async(rt.bank_K[i][c * rt.S + new], side.bank_K[i][side.slots[0][0]], nk)(s)
-                ops.copy_async(rt.bank_V[i][c * rt.S + new], side.bank_V[i][side.slots[0][0]], nv)(s)
+                ops.copy_async(rt.bank_K[i][c * rt.S + new], side.bank_K[i][src], nk)(s)
+                ops.copy_async(rt.bank_V[i][c * rt.S + new], side.bank_V[i][src], nv)(s)
                 ops.copy_async(rt.short_K[i][c * L:(c + 1) * L], side.short_K[i], nk)(s)
                 ops.copy_async(rt.short_V[i][c * L:(c + 1) * L], side.short_V[i], nv)(s)
-            rt.upload_chunks(s)
-        self.last_mem_step[c] = self.frame_step
-        self.policies[c] = MemoryPolicy()
-        self._indexes[c].append(self.frame_step)
 
     # ------------------------------------------------------------------ look-ahead encoder
     def encode_inputs(self, buf: int = 0) -> torch.Tensor:
@@ -199,33 +149,17 @@ class GroupEngine:
             self._enc_done[buf].record(es)
 
     # ------------------------------------------------------------------ propagate (aot_engine.py:398-465 + evaluator.py:430-441)
-    def _will_append(self, c: int) -> bool:
-        return self.frame_step - self.last_mem_step[c] >= self.long_term_mem_gap
-
-    def _mass_needed(self) -> bool:
-        """The attention mass of layer 0 is only read by the eviction policy: needed iff the update after this propagation appends
-        to some clip's bank and overflows it (DeAOT: appends at all)."""
-        need = any(self._will_append(c) and (self.policy_every_update or len(self.rt.slots[c]) + 1 > self.n_keep)
-                   for c in range(self.B))
-        self._mass_valid = need
-        return need
-
     def propagate_to_labels(self, labels_u8: torch.Tensor, enc_slot: Optional[int] = None, imgs: Optional[torch.Tensor] = None):
         """labels_u8: uint8 [B, Ho, Wo] device buffer at a fixed address.  Either enc_slot (frame encoded by encode_ahead) or
         imgs [B, 3, H, W] (encoded now)."""
         self.frame_step += 1
         rt, B = self.rt, self.B
-        self._resolve_pending()
+        T, wm = self.bank.begin_propagation(rt)
         Ho, Wo = int(labels_u8.shape[-2]), int(labels_u8.shape[-1])
-        keep = self.obj_nums[0]
         with torch.cuda.stream(self.stream):
-            T = rt.T
-            self._T_at_propagate = T
-            self._Tc_at_propagate = [len(sl) for sl in rt.slots]
-            wm = self._mass_needed()
             pk = f'post_{labels_u8.data_ptr()}_{Ho}_{Wo}'
             if pk not in rt._prog:
-                rt._prog[pk] = [ops.logits_post(rt.logits, ldl=16, nc=rt.nc, keep=keep, Hi=rt.H4, Wi=rt.W4, Ho=Ho, Wo=Wo,
+                rt._prog[pk] = [ops.logits_post(rt.logits, ldl=16, nc=rt.nc, keep=self.obj_nums[0], Hi=rt.H4, Wi=rt.W4, Ho=Ho, Wo=Wo,
                                                 align_corners=self.align_corners, label_u8=labels_u8, images=B)]
             if enc_slot is None:
                 ops.copy_async(rt.enc_now.img_in, imgs.contiguous(), B * 3 * rt.H * rt.W * 4)(self._s())
@@ -244,65 +178,13 @@ class GroupEngine:
     def update_from_labels(self, labels_u8: torch.Tensor, skip: Iterable[int] = ()):
         """labels_u8: uint8 [B, Ho, Wo] argmax labels at the output size (nearest-resized to the network size on the device).
         skip: clips whose memory is re-initialised right after by add_reference_frame_for (no bank append for them)."""
-        rt, B = self.rt, self.B
-        hs, ws = int(labels_u8.shape[-2]), int(labels_u8.shape[-1])
-        skip = set(skip)
-        appends = [self._will_append(c) and c not in skip for c in range(B)]
-        with torch.cuda.stream(self.stream):
-            s = self._s()
-            new_slots = [-1] * B
-            if any(appends):
-                for c in range(B):
-                    if appends[c]:
-                        if not rt.free[c]:
-                            raise ops.RmemError(f'clip {c}: the memory bank outgrew the {rt.S} slots of the group runtime '
-                                                f'(unbounded banks are limited by the {MAX_CHUNKS}-row key table)')
-                        new_slots[c] = rt.free[c].pop(0)
-                rt.upload_append_slots(new_slots, s)
-            self._run(f'upd{int(any(appends))}_{labels_u8.data_ptr()}', rt.prog_id_emb(labels_u8, hs, ws) + rt.prog_update(any(appends)))
-            if not any(appends):
-                return
-            scored, over = [], set()            # clips whose policy state moves / whose bank overflows
-            for c in range(B):
-                if appends[c]:
-                    self.last_mem_step[c] = self.frame_step
-                    rt.slots[c].append(new_slots[c])
-                    self._indexes[c].append(self.frame_step)
-                    if len(rt.slots[c]) > self.n_keep:
-                        over.add(c)
-                    if c in over or self.policy_every_update:
-                        scored.append(c)
-            if scored:
-                if not self._mass_valid:
-                    raise RuntimeError('long_term_mem_gap changed between propagate and update: attention mass not recorded')
-                Tp, L = self._T_at_propagate, rt.L
-                ops.run([ops.evict_scores(rt.logits[c * rt.M4:(c + 1) * rt.M4], rt.mass[c * L * Tp:(c + 1) * L * Tp], rt.scores[c],
-                                          ldl=16, nc=rt.nc, keep=self.obj_nums[0], Hi=rt.H4, Wi=rt.W4, He=rt.H16, We=rt.W16, T=Tp)
-                         for c in scored], s)
-                for c in scored:
-                    ops.copy_async(rt.scores_host[c], rt.scores[c], 4 * Tp)(s)
-                ev = torch.cuda.Event()
-                ev.record(self.stream)
-                self._pending = (ev, scored, over, list(self._Tc_at_propagate))
-            else:
-                rt.upload_chunks(s)
-
-    def _resolve_pending(self):
-        if self._pending is None:
-            return
-        ev, scored, over, tc = self._pending
-        self._pending = None
-        ev.synchronize()
         rt = self.rt
-        for c in scored:
-            drop = self.policies[c].choose(rt.scores_host[c, :tc[c]].clone(), self._indexes[c])
-            if c not in over:                 # DeAOT: the scores moved, nothing is dropped yet
-                continue
-            self.drop_trace[c].append(drop)
-            rt.free[c].append(rt.slots[c].pop(drop))
-            del self._indexes[c][drop]
+        hs, ws = int(labels_u8.shape[-2]), int(labels_u8.shape[-1])
         with torch.cuda.stream(self.stream):
-            rt.upload_chunks(self._s())
+            slots = self.bank.take_append_slots(rt, skip)
+            appends = max(slots) >= 0
+            self._run(f'upd{int(appends)}_{labels_u8.data_ptr()}', rt.prog_id_emb(labels_u8, hs, ws) + rt.prog_update(appends))
+            self.bank.commit_update(rt, slots, self.obj_nums[0])
 
     def synchronize(self):
         self.stream.synchronize()

@@ -9,7 +9,8 @@ memory and streams only.
 from __future__ import annotations
 
 import ctypes as C
-from typing import Optional, Sequence
+import os
+from typing import Dict, Optional, Sequence
 
 import torch
 
@@ -659,3 +660,26 @@ class Graph:
                 _lib.lib().rmem_graph_destroy(self.handle)
         except Exception:
             pass
+
+
+class GraphCache:
+    """Launch lists by key on a stream: enqueued directly, or (use_graphs) replayed as ONE hipGraph per key, captured on first use
+    after a warm run outside capture (first touch, lazy module load)."""
+
+    def __init__(self):
+        self.graphs: Dict[str, Graph] = {}
+
+    def run(self, key: str, prog: list, stream: int, use_graphs: bool):
+        ab = os.environ.get('RMEM_ABLATE')           # timing experiments only: drop every launch whose name contains the tag
+        if ab:
+            prog = [o for o in prog if not any(t in o.name for t in ab.split(','))]
+        if use_graphs and key in self.graphs:
+            self.graphs[key](stream)
+            return
+        run(prog, stream)
+        if use_graphs:
+            self.graphs[key] = Graph(prog, stream)
+
+    def drop(self, prefixes: tuple):
+        """Forget the graphs whose key starts with one of ``prefixes`` (their launch lists name buffers that were rebuilt)."""
+        self.graphs = {k: g for k, g in self.graphs.items() if not k.startswith(prefixes)}

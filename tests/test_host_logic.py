@@ -1,5 +1,5 @@
 """Host-side logic of the engine (no GPU): temporal-PE slots, positional embedding, the eviction
-policy against the oracle's restatement, weight packing, the state_dict contract, clip sharding."""
+policy and the bank schedule against the oracle's restatement, weight packing, the state_dict contract, clip sharding."""
 import numpy as np
 import torch
 
@@ -22,7 +22,7 @@ def test_sine_pos_emb_matches_reference_fixture(golden_ops):
 
 def test_memory_policy_equals_oracle_policy():
     """MemoryPolicy (product) and oracle.choose_eviction walk the same random score streams identically."""
-    from rmem_ocu_amd.networks.engines.aot_engine import MemoryPolicy
+    from rmem_ocu_amd.bank_schedule import MemoryPolicy
     rng = np.random.default_rng(0)
     for trial in range(20):
         N = int(rng.integers(2, 9))
@@ -42,6 +42,128 @@ def test_memory_policy_equals_oracle_policy():
             del idx_a[da]
             del idx_b[db]
             assert idx_a == idx_b and idx_a[0] == 0
+
+
+class _StandInBank:
+    """What BankSchedule uses of a runtime: the slot lists, S, the pinned score rows; the table uploads do nothing."""
+
+    def __init__(self, clips, slots):
+        self.B, self.S = clips, slots
+        self.scores_host = torch.zeros(clips, 32)
+        self.reset_bank()
+
+    def reset_bank(self):
+        self.slots = [[] for _ in range(self.B)]
+        self.free = [list(range(self.S)) for _ in range(self.B)]
+
+    def upload_chunks(self, stream):
+        pass
+
+    def upload_append_slots(self, slots, stream):
+        pass
+
+
+def _scores(clip, frame, T):
+    """The score stream of a clip: layer 0's attention mass [hw, T] and the foreground probability [hw] of ``frame``."""
+    rng = np.random.default_rng((7, clip, frame))
+    return torch.from_numpy(rng.random((50, T)).astype(np.float32)), torch.from_numpy(rng.random(50).astype(np.float32))
+
+
+def _schedule_traces(clips, N, gap, frames, restarts, every=False):
+    """Drive one BankSchedule for the score streams ``clips`` the way the engines do; restarts = {stream: frame of its mid-clip
+    reference frame}.  -> per frame, per clip (long_memories_indexes, drop_trace); the bank invariants are asserted on the way."""
+    from types import SimpleNamespace as NS
+    from rmem_ocu_amd.bank_schedule import BankSchedule, bank_slots
+    B = len(clips)
+    eng = NS(frame_step=0, long_term_mem_gap=9999, policy_every_update=every, stream=NS(cuda_stream=0),
+             cfg=NS(FORMER_MEM_LEN=1, LATTER_MEM_LEN=N - 1))
+    rt = _StandInBank(B, bank_slots(N))
+
+    def score(rt, stream, scored, T, keep):           # the "readback": the clip's scores for its own bank length, straight into the buffer
+        for c in scored:
+            Tc = len(rt.slots[c]) - 1
+            assert Tc <= T
+            mass, fg = _scores(clips[c], eng.frame_step, Tc)
+            rt.scores_host[c, :Tc] = (mass * fg[:, None]).sum(0)
+        return NS(synchronize=lambda: None)
+
+    def check(limit):
+        for c in range(B):
+            assert len(rt.slots[c]) <= limit
+            assert sorted(rt.slots[c] + rt.free[c]) == list(range(rt.S))      # every slot in 0..S-1, none both free and in use
+
+    sch = BankSchedule(eng, B, score=score)
+    eng.long_term_mem_gap = gap                       # set on the started engine, as the clip runners do
+    sch.start_reference(rt, mem_step=0)
+    trace = []
+    for f in range(1, frames):
+        eng.frame_step += 1
+        T, _ = sch.begin_propagation(rt)
+        assert T == max(len(sl) for sl in rt.slots)
+        again = [c for c in range(B) if restarts.get(clips[c]) == f]
+        sch.commit_update(rt, sch.take_append_slots(rt, skip=again), keep=10)
+        check(N + 1)
+        if again:
+            sch.start_reference(rt, again, append_table=False)
+        trace.append([(list(sch.long_memories_indexes(c)), list(sch.drop_trace[c])) for c in range(B)])
+        check(N)
+    return trace
+
+
+def _oracle_trace(N, gap, frames, restart_at):
+    """The same clip in the oracle's own bookkeeping (OracleEngine.add_reference_frame / match_propogate_one_frame /
+    update_memory / _update_memories, with the bank reduced to its length T)."""
+    frame_step, last_mem_step, indexes, evict, drops, T = 0, 0, [0], O.EvictionState(), [], 1      # add_reference_frame(frame_step=0)
+    trace = []
+    for f in range(1, frames):
+        frame_step += 1
+        if f == restart_at:                            # add_reference_frame(frame_step=self.frame_step) instead of the update
+            last_mem_step, evict, T = frame_step, O.EvictionState(), 1
+            indexes.append(frame_step)
+        elif frame_step - last_mem_step >= gap:
+            last_mem_step = frame_step
+            T += 1
+            indexes.append(frame_step)
+            if T > N:
+                mass, fg = _scores(0, frame_step, T - 1)
+                drop = O.choose_eviction(mass, fg, indexes, evict)
+                drops.append(drop)
+                T -= 1
+                del indexes[drop]
+        trace.append((list(indexes), list(drops)))
+    return trace
+
+
+def test_bank_schedule_equals_oracle_bookkeeping_and_group_equals_per_clip():
+    """BankSchedule with a stand-in for the device side (no GPU): a one-clip schedule walks restricted banks of N = 2..8 entries
+    with gaps 1..5 exactly like the oracle's bookkeeping -- long_memories_indexes and drop_trace equal at every frame of >= 60
+    frames with evictions, then a mid-clip reference frame and the frames until the restarted bank is full again.  The next
+    update would evict with an index list that kept growing across the bank reset: the reference raises there
+    (layers/transformer.py:401), and so do oracle and schedule, at the same frame.  A three-clip schedule
+    gives per clip the traces of three one-clip schedules, also when one clip restarts mid-clip (banks of different lengths from
+    then on) and when the policy state moves on every update (DeAOT)."""
+    import pytest
+    for N in range(2, 9):
+        for gap in range(1, 6):
+            restart = 60 + N
+            frames = restart + gap * N                 # the restarted bank overflows at frame restart + gap * N
+            got = _schedule_traces([0], N, gap, frames, {0: restart})
+            want = _oracle_trace(N, gap, frames, restart)
+            assert len(got) == frames - 1 >= 60 and len(want[restart - 2][1]) >= 60 // gap - N
+            for f, (g, w) in enumerate(zip(got, want), start=1):
+                assert g[0] == w, (N, gap, f)
+            with pytest.raises(RuntimeError):
+                _oracle_trace(N, gap, frames + 1, restart)
+            with pytest.raises(RuntimeError):
+                _schedule_traces([0], N, gap, frames + 1, {0: restart})
+    # every = True: the restarted clip's policy raises at its second update after the restart (DESIGN.md section 2): stop before it
+    for N, gap, every, frames in ((4, 2, False, 40 + 2 * 4), (3, 1, False, 40 + 3), (8, 3, False, 40 + 3 * 8), (4, 2, True, 40 + 2 * 2)):
+        restarts = {1: 40}
+        group = _schedule_traces([0, 1, 2], N, gap, frames, restarts, every)
+        for c in range(3):
+            solo = _schedule_traces([c], N, gap, frames, restarts, every)
+            assert [fr[c] for fr in group] == [fr[0] for fr in solo], (N, gap, every, c)
+        assert len(group[-1][1][0]) > N >= len(group[-1][0][0]) and len(group[-1][1][1]) < len(group[-1][0][1])      # the restart happened
 
 
 def test_state_dict_contract_and_packing():
