@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define RMEM_ABI_VERSION 9
+#define RMEM_ABI_VERSION 10
 
 int rmem_abi_version(void);
 const char* rmem_last_error_string(void);
@@ -539,6 +539,25 @@ int rmem_tta_merge(const float* const* logits_nchw, const int* flips, int n_aug,
  * counts (uint64 [2 * num_ids]).  Replaces evaluation/source/metrics.py:6-37 (db_eval_iou) per object. */
 int rmem_mask_iou_counts(const unsigned char* pred, const unsigned char* gt, long long n, int num_ids, int void_label,
                          unsigned long long* counts, void* stream);
+
+/* Clip scoring: boundary accuracy F and region similarity J counts for a whole stack of frames in one call, no host sync.
+ * pred / gt: uint8 label stacks [frames][H][W] with ids 0..num_ids-1 (2 <= num_ids <= 32); gt may carry `void_label`, whose pixels
+ * are cleared from both masks.  counts: uint64 [frames][num_ids][6], zeroed on the stream by the call, row of id 0 left zero:
+ *   [0] n_fg      boundary pixels of pred == id        [1] n_gt      boundary pixels of gt == id
+ *   [2] fg_match  pred boundary inside the gt boundary dilated by a disk of `radius` (dx^2 + dy^2 <= radius^2, zero padding)
+ *   [3] gt_match  gt boundary inside the dilated pred boundary
+ *   [4], [5]      J intersection and union, per frame what rmem_mask_iou_counts returns.
+ * The boundary map is seg2bmap at the mask's own size (a pixel differs from its east, south or south-east neighbour; last row:
+ * east only, last column: south only, bottom-right pixel: 0).  1 <= radius <= 63.  workspace: rmem_clip_score_workspace_bytes
+ * bytes of device memory (the boundary bit planes), no state kept between calls.
+ * Replaces evaluation/source/metrics.py db_eval_boundary / f_measure (seg2bmap + cv2.dilate with skimage's disk) per object and
+ * frame, and a per-frame loop over db_eval_iou. */
+size_t rmem_clip_score_workspace_bytes(int frames, int H, int W, int num_ids);   /* 0 on bad geometry */
+/* The dilation radius f_measure uses: bound_th itself when bound_th >= 1 (it must be an integer), else
+ * ceil(bound_th * sqrt(H^2 + W^2)); 0.008 gives 8 at 480x854 and 18 at 1080x1920.  -1 on a bad argument.  Host only. */
+int rmem_boundary_radius(int H, int W, double bound_th);
+int rmem_clip_score_counts(const unsigned char* pred, const unsigned char* gt, int frames, int H, int W, int num_ids,
+                           int void_label, int radius, void* workspace, unsigned long long* counts, void* stream);
 
 /* ------------------------------------------------------------------ stream capture helpers
  * Thin wrappers over hipStreamBeginCapture / hipGraphInstantiate / hipGraphLaunch so the Python host

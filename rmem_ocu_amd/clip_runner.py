@@ -270,7 +270,10 @@ class GroupSlot:
     """B clips of equal length in flight on one GroupEngine (networks/engines/group_engine.py): same protocol as ClipSlot, one
     launch per layer for the whole group.  With an encoder look-ahead of n frames the frames are encoded in batches of n per
     clip: batch k + 1 is copied in and encoded on the engine's side stream while the frames of batch k are propagated (two
-    look-ahead buffers, alternating; look-ahead slot = buffer * n + frame)."""
+    look-ahead buffers, alternating; look-ahead slot = buffer * n + frame).
+    labels: uint8 [B, n, Ho, Wo] on the device, labels[c, i] = the prediction of frame i of clip c (row 0 stays zero: frame 0 is the
+    given annotation).  Once the engine has been synchronised a clip is scored where it lies:
+    evaluator.score_clip(slot.labels[c, :n], gt_stack) -> J, F, J&F, decay, tail J."""
 
     def __init__(self, engine, out_hw, device):
         self.engine = engine

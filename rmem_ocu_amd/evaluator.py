@@ -8,11 +8,14 @@ Mirrors what networks/managers/evaluator.py:330-568 does for one sequence, witho
   * a ground-truth label that arrives on a later frame (a new object) is merged over the prediction and the frame is
     re-added as a reference frame to every engine (484-508); otherwise the prediction updates the memory (509-523);
   * masks can be written as palette PNGs (utils/image.py:90-106) and scored with the region similarity J
-    (evaluation/source/metrics.py:6-37) -- rmem_mask_iou_counts.
+    (evaluation/source/metrics.py:6-37) -- rmem_mask_iou_counts;
+  * whole clips are scored on the device with J and the boundary accuracy F (the benchmark toolkit's db_eval_iou /
+    db_eval_boundary and its per-sequence mean, recall and decay) -- rmem_clip_score_counts, score_clip.
 """
 from __future__ import annotations
 
 import ctypes as C
+from dataclasses import dataclass
 from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
@@ -76,6 +79,147 @@ def region_similarity(pred_u8: torch.Tensor, gt_u8: torch.Tensor, num_ids: int =
                                                torch.cuda.current_stream(pred_u8.device).cuda_stream), 'rmem_mask_iou_counts')
     c = counts.cpu().view(num_ids, 2)
     return {i: (1.0 if c[i, 1] == 0 else float(c[i, 0]) / float(c[i, 1])) for i in range(1, num_ids) if c[i, 1] > 0}
+
+
+_score_ws: Dict[Tuple[int, int], torch.Tensor] = {}      # (device index, stream) -> boundary bit planes of clip_counts, grow-only
+
+
+def _label_stacks(pred_u8, gt_u8, what):
+    for t in (pred_u8, gt_u8):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.uint8 or not t.is_cuda:
+            raise _lib.RmemError(f'{what}: pred and gt must be uint8 device tensors')
+    if pred_u8.shape != gt_u8.shape or pred_u8.dim() not in (2, 3) or pred_u8.numel() == 0 or pred_u8.device != gt_u8.device:
+        raise _lib.RmemError(f'{what}: pred and gt must have one shape, [n, H, W] or [H, W], on one device '
+                             f'(got {tuple(pred_u8.shape)} and {tuple(gt_u8.shape)})')
+    if pred_u8.dim() == 2:
+        pred_u8, gt_u8 = pred_u8[None], gt_u8[None]
+    return pred_u8.contiguous(), gt_u8.contiguous()
+
+
+def boundary_radius(H: int, W: int, bound_th: float = 0.008) -> int:
+    """f_measure's dilation radius: bound_th when it is >= 1 (an integer then), else ceil(bound_th * image diagonal)."""
+    r = _lib.lib().rmem_boundary_radius(int(H), int(W), float(bound_th))
+    if r < 0:
+        raise _lib.RmemError(f'boundary_radius: bad argument (H={H}, W={W}, bound_th={bound_th})')
+    return r
+
+
+def clip_counts(pred_u8: torch.Tensor, gt_u8: torch.Tensor, num_ids: int = 11, void_label: int = 255,
+                bound_th: float = 0.008) -> torch.Tensor:
+    """The six counts behind F and J per (frame, id): int64 device tensor [n, num_ids, 6] = n_fg, n_gt, fg_match, gt_match,
+    J intersection, J union (include/rmem.h, rmem_clip_score_counts).  pred / gt: uint8 device label maps [n, H, W] or [H, W].
+    Enqueued on the current stream, no host sync.  The bit-plane workspace is one buffer per (device, stream) that only grows
+    (to the longest stack seen), so calls on different streams never share planes."""
+    pred, gt = _label_stacks(pred_u8, gt_u8, 'clip_counts')
+    n, H, W = pred.shape
+    L = _lib.lib()
+    radius = boundary_radius(H, W, bound_th)
+    nbytes = L.rmem_clip_score_workspace_bytes(n, H, W, int(num_ids))
+    if nbytes == 0:
+        raise _lib.RmemError(f'clip_counts: num_ids must be in 2..32 (got {num_ids})')
+    stream = torch.cuda.current_stream(pred.device)
+    key = (pred.device.index, stream.cuda_stream)
+    ws = _score_ws.get(key)
+    if ws is None or ws.numel() < nbytes:
+        with torch.cuda.stream(stream):
+            ws = _score_ws[key] = torch.empty(nbytes, dtype=torch.uint8, device=pred.device)
+    counts = torch.empty(n, int(num_ids), 6, dtype=torch.int64, device=pred.device)
+    _lib.check(L.rmem_clip_score_counts(pred.data_ptr(), gt.data_ptr(), n, H, W, int(num_ids), int(void_label), radius,
+                                        ws.data_ptr(), counts.data_ptr(), stream.cuda_stream),
+               'rmem_clip_score_counts')
+    return counts
+
+
+def scores_from_counts(counts) -> Tuple[np.ndarray, np.ndarray]:
+    """counts [n, num_ids, 6] (host) -> (J, F) float64 [n, num_ids].  J = intersection / union, 1 for an empty union
+    (db_eval_iou); F = 2PR / (P + R) with f_measure's edge cases: no prediction boundary -> P = 1, R = 0; no annotation boundary
+    -> P = 0, R = 1; neither -> P = R = 1; F = 0 when P + R = 0."""
+    c = np.asarray(counts).astype(np.float64)
+    n_fg, n_gt, fg_m, gt_m, inter, union = (c[..., i] for i in range(6))
+    J = np.where(union == 0, 1.0, inter / np.maximum(union, 1.0))
+    P = np.where(n_fg > 0, np.where(n_gt > 0, fg_m / np.maximum(n_fg, 1.0), 0.0), 1.0)
+    R = np.where(n_gt > 0, np.where(n_fg > 0, gt_m / np.maximum(n_gt, 1.0), 0.0), 1.0)
+    F = np.where(P + R == 0, 0.0, 2.0 * P * R / np.where(P + R == 0, 1.0, P + R))
+    return J, F
+
+
+def boundary_accuracy(pred_u8: torch.Tensor, gt_u8: torch.Tensor, num_ids: int = 11, void_label: int = 255,
+                      bound_th: float = 0.008) -> Dict[int, float]:
+    """F per object id for one mask pair (device uint8 tensors of equal shape); ids absent from both masks are skipped."""
+    if isinstance(pred_u8, torch.Tensor) and pred_u8.dim() != 2:
+        raise _lib.RmemError('boundary_accuracy: one [H, W] mask pair (use clip_counts / score_clip for a stack)')
+    c = clip_counts(pred_u8, gt_u8, num_ids, void_label, bound_th).cpu().numpy()
+    F = scores_from_counts(c)[1]
+    return {i: float(F[0, i]) for i in range(1, num_ids) if c[0, i, 5] > 0}
+
+
+def sequence_statistics(values: np.ndarray) -> Tuple[float, float, float]:
+    """The benchmark's per-sequence summary of one object's per-frame values (db_statistics): mean, recall (share > 0.5) and
+    decay (mean of the first of four bins minus mean of the last; bin edges round(linspace(1, len, 5) + 1e-10) - 1, each bin
+    inclusive of its end index)."""
+    v = np.asarray(values, dtype=np.float64)
+    ids = (np.round(np.linspace(1, len(v), 5) + 1e-10) - 1).astype(np.int64)
+    bins = [v[ids[i]:ids[i + 1] + 1] for i in range(4)]
+    return float(v.mean()), float((v > 0.5).mean()), float(bins[0].mean() - bins[3].mean())
+
+
+@dataclass
+class ClipScore:
+    """score_clip's result.  J / F: per-frame values [n, num_objs] of every frame of the stack, column i = object id i + 1;
+    frames: the indices the statistics run over; *_obj_*: per object over those frames; J_mean, F_mean, JF_mean, J_recall, ...:
+    averaged over objects; J_tail: mean J over the last `tail` share of those frames (VOST's tail measure), averaged over objects."""
+    J: np.ndarray
+    F: np.ndarray
+    frames: np.ndarray
+    J_obj_mean: np.ndarray
+    J_obj_recall: np.ndarray
+    J_obj_decay: np.ndarray
+    F_obj_mean: np.ndarray
+    F_obj_recall: np.ndarray
+    F_obj_decay: np.ndarray
+    J_obj_tail: np.ndarray
+    J_mean: float
+    J_recall: float
+    J_decay: float
+    F_mean: float
+    F_recall: float
+    F_decay: float
+    JF_mean: float
+    J_tail: float
+
+
+def summarize_scores(J: np.ndarray, F: np.ndarray, frames=slice(1, -1), tail: float = 0.25) -> ClipScore:
+    """Host half of score_clip: per-frame J / F [n, num_objs] -> ClipScore.  The tail covers frames int(len * (1 - tail)) .. end
+    of the selected frames."""
+    J, F = np.asarray(J, dtype=np.float64), np.asarray(F, dtype=np.float64)
+    sel = np.arange(J.shape[0])[frames]
+    if sel.size == 0 or J.shape[1] == 0:
+        raise _lib.RmemError(f'score_clip: no frame or no object to score ({J.shape[0]} frames, {J.shape[1]} objects)')
+    if not 0.0 < tail <= 1.0:
+        raise _lib.RmemError(f'score_clip: tail must be in (0, 1] (got {tail})')
+    js = np.array([sequence_statistics(J[sel, o]) for o in range(J.shape[1])])
+    fs = np.array([sequence_statistics(F[sel, o]) for o in range(F.shape[1])])
+    jt = J[sel[int(sel.size * (1.0 - tail)):]].mean(axis=0)
+    return ClipScore(J=J, F=F, frames=sel, J_obj_mean=js[:, 0], J_obj_recall=js[:, 1], J_obj_decay=js[:, 2], F_obj_mean=fs[:, 0],
+                     F_obj_recall=fs[:, 1], F_obj_decay=fs[:, 2], J_obj_tail=jt, J_mean=float(js[:, 0].mean()),
+                     J_recall=float(js[:, 1].mean()), J_decay=float(js[:, 2].mean()), F_mean=float(fs[:, 0].mean()),
+                     F_recall=float(fs[:, 1].mean()), F_decay=float(fs[:, 2].mean()),
+                     JF_mean=float(0.5 * (js[:, 0].mean() + fs[:, 0].mean())), J_tail=float(jt.mean()))
+
+
+def score_clip(pred_u8: torch.Tensor, gt_u8: torch.Tensor, num_objs: Optional[int] = None, frames=slice(1, -1), tail: float = 0.25,
+               void_label: int = 255, bound_th: float = 0.008) -> ClipScore:
+    """J, F and their per-clip summary for a stack of predicted label maps against the annotation ([n, H, W] uint8, device):
+    one clip_counts call and one device-to-host copy.  Objects 1..num_objs are scored on every frame (empty against empty
+    scores 1, as the benchmark does); num_objs defaults to the largest non-void id of the annotation (one more scalar read).
+    frames: the frames the statistics run over; the default drops the first and the last one, as the semi-supervised protocol does."""
+    pred, gt = _label_stacks(pred_u8, gt_u8, 'score_clip')
+    if num_objs is None:
+        num_objs = int(torch.where(gt == void_label, torch.zeros_like(gt), gt).max().item())
+    if not 1 <= num_objs <= 31:
+        raise _lib.RmemError(f'score_clip: num_objs must be in 1..31 (got {num_objs})')
+    J, F = scores_from_counts(clip_counts(pred, gt, num_objs + 1, void_label, bound_th).cpu().numpy())
+    return summarize_scores(J[:, 1:], F[:, 1:], frames, tail)
 
 
 def frames_from_jpegs(paths_or_bytes: Sequence, device, scale: float = 1.0) -> torch.Tensor:
