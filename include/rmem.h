@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define RMEM_ABI_VERSION 10
+#define RMEM_ABI_VERSION 11
 
 int rmem_abi_version(void);
 const char* rmem_last_error_string(void);
@@ -558,6 +558,28 @@ size_t rmem_clip_score_workspace_bytes(int frames, int H, int W, int num_ids);  
 int rmem_boundary_radius(int H, int W, double bound_th);
 int rmem_clip_score_counts(const unsigned char* pred, const unsigned char* gt, int frames, int H, int W, int num_ids,
                            int void_label, int radius, void* workspace, unsigned long long* counts, void* stream);
+
+/* Palette-PNG payloads: one zlib stream per uint8 label map [frames][H][W] (contiguous, device), in one call on `stream`, no host
+ * sync.  lut: 256 device bytes applied to every label as it is read (save_mask's un-squeeze of object ids), or NULL.  The streams
+ * are packed back to back: stream f is out[offsets[f] : offsets[f+1]), offsets (device, int64 [frames + 1]) starts at 0; out holds
+ * frames * rmem_png_zlib_bound(H, W) bytes and is 4-byte aligned.  Whatever must be zero (the used part of out) is zeroed on the
+ * stream inside the call; workspace: rmem_png_workspace_bytes bytes, 16-byte aligned, no state kept between calls.
+ * The stream of one frame is fixed bit for bit:
+ *   78 01; one DEFLATE block, BFINAL = 1, BTYPE = 01 (fixed Huffman codes, RFC 1951 3.2.6); the end-of-block code; zero bits up to
+ *   the byte boundary; the Adler-32 of the filtered bytes, big-endian.
+ *   Filtered bytes: per row the filter type 2 (Up), then the W bytes label[y][x] - label[y-1][x] (mod 256), row -1 all zero.
+ *   Tokens: each row's W + 1 filtered bytes are cut into maximal runs of equal bytes (a run never crosses a row); a run of value v
+ *   and length L is: literal v; rem = L - 1; while rem >= 3 one match of distance 1 and length t = min(rem, 258), rem -= t; then
+ *   rem (0, 1 or 2) literals v.  Length 258 uses code 285.
+ * No token costs more than 9 bits per byte it covers: rmem_png_zlib_bound = 2 + ceil((3 + 9 (W + 1) H + 7) / 8) + 4.
+ * Wrapped into signature / IHDR (8 bit, colour type 3) / PLTE / IDAT / IEND on the host (rmem_ocu_amd/png.py; the chunk CRCs stay
+ * there).  H * W <= 2^26, so that a frame's bit count fits 32 bits.
+ * Replaces utils/image.py:90-106 (save_mask: Pillow's PNG encoder, one frame at a time on a host copy of the label map). */
+size_t rmem_png_zlib_bound(int H, int W);                         /* host only, 0 on bad geometry */
+/* uint32 [frames][H] x 3 (row bits, Adler-32 partials) + per frame its Adler-32 and byte size.  Host only, 0 on bad geometry. */
+size_t rmem_png_workspace_bytes(int frames, int H, int W);
+int rmem_png_encode_labels(const unsigned char* labels, int frames, int H, int W, const unsigned char* lut /* device, 256 bytes, or NULL */,
+                           void* workspace, unsigned char* out, long long* offsets, void* stream);
 
 /* ------------------------------------------------------------------ stream capture helpers
  * Thin wrappers over hipStreamBeginCapture / hipGraphInstantiate / hipGraphLaunch so the Python host

@@ -11,7 +11,7 @@ import subprocess
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('RMEM_LIB_PATH') or os.path.join(_HERE, 'librmem_hip.so')   # override: kernel experiments only
-ABI_VERSION = 10
+ABI_VERSION = 11
 
 
 class RmemError(RuntimeError):
@@ -141,6 +141,9 @@ SIGNATURES = {
     'rmem_clip_score_workspace_bytes': (C.c_size_t, [_i, _i, _i, _i]),
     'rmem_boundary_radius': (_i, [_i, _i, C.c_double]),
     'rmem_clip_score_counts': (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
+    'rmem_png_zlib_bound': (C.c_size_t, [_i, _i]),
+    'rmem_png_workspace_bytes': (C.c_size_t, [_i, _i, _i]),
+    'rmem_png_encode_labels': (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
     'rmem_split_label': (_i, [_vp, _i, _i, _vp, _ll, _vp]),
     'rmem_soft_logit_aggregate': (_i, [C.POINTER(_vp), _i, _i, _i, _i, _i, _vp, _vp]),
     'rmem_copy_async': (_i, [_vp, _vp, C.c_size_t, _vp]),

@@ -273,7 +273,8 @@ class GroupSlot:
     look-ahead buffers, alternating; look-ahead slot = buffer * n + frame).
     labels: uint8 [B, n, Ho, Wo] on the device, labels[c, i] = the prediction of frame i of clip c (row 0 stays zero: frame 0 is the
     given annotation).  Once the engine has been synchronised a clip is scored where it lies:
-    evaluator.score_clip(slot.labels[c, :n], gt_stack) -> J, F, J&F, decay, tail J."""
+    evaluator.score_clip(slot.labels[c, :n], gt_stack) -> J, F, J&F, decay, tail J; and its masks leave as palette PNGs encoded
+    on the device: png.encode_label_stack(slot.labels[c, 1:n]) -> one PNG file per frame (evaluator.save_masks writes them)."""
 
     def __init__(self, engine, out_hw, device):
         self.engine = engine

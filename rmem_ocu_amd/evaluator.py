@@ -9,6 +9,9 @@ Mirrors what networks/managers/evaluator.py:330-568 does for one sequence, witho
     re-added as a reference frame to every engine (484-508); otherwise the prediction updates the memory (509-523);
   * masks can be written as palette PNGs (utils/image.py:90-106) and scored with the region similarity J
     (evaluation/source/metrics.py:6-37) -- rmem_mask_iou_counts;
+  * whole stacks of predicted masks are written as palette PNGs from the device: the DEFLATE payload of every frame is encoded
+    there and only the few KB of each file cross to the host -- rmem_png_encode_labels, save_masks, png.encode_label_stack
+    (save_mask, one host mask through Pillow, stays as it is);
   * whole clips are scored on the device with J and the boundary accuracy F (the benchmark toolkit's db_eval_iou /
     db_eval_boundary and its per-sequence mean, recall and decay) -- rmem_clip_score_counts, score_clip.
 """
@@ -52,6 +55,18 @@ def save_mask(mask_u8: np.ndarray, path: str, squeeze_idx: Optional[Sequence[int
     im = Image.fromarray(mask).convert('P')
     im.putpalette(_davis_palette())
     im.save(path)
+
+
+def save_masks(labels_u8: torch.Tensor, paths: Sequence[str], squeeze_idx: Optional[Sequence[int]] = None):
+    """save_mask for a whole stack of device label maps ([n, H, W] or [H, W] uint8): one indexed PNG with the DAVIS palette per
+    path, the un-squeeze of object ids and the compression done on the device (png.encode_label_stack)."""
+    from . import png
+    files = png.encode_label_stack(labels_u8, squeeze_idx)
+    if len(files) != len(paths):
+        raise _lib.RmemError(f'save_masks: {len(files)} frames but {len(paths)} paths')
+    for path, data in zip(paths, files):
+        with open(path, 'wb') as f:
+            f.write(data)
 
 
 def tta_merge(logits: Sequence[torch.Tensor], flips: Sequence[bool], want_prob: bool = False):
