@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define RMEM_ABI_VERSION 11
+#define RMEM_ABI_VERSION 12
 
 int rmem_abi_version(void);
 const char* rmem_last_error_string(void);
@@ -580,6 +580,52 @@ size_t rmem_png_zlib_bound(int H, int W);                         /* host only, 
 size_t rmem_png_workspace_bytes(int frames, int H, int W);
 int rmem_png_encode_labels(const unsigned char* labels, int frames, int H, int W, const unsigned char* lut /* device, 256 bytes, or NULL */,
                            void* workspace, unsigned char* out, long long* offsets, void* stream);
+
+/* Palette-PNG annotations: the inverse direction.  One zlib stream per frame (the concatenated IDAT payloads of a PNG file) in, uint8
+ * label maps out[frames][H][W] (contiguous, device) out, in one call on `stream`, no host sync, no state kept between calls.
+ * bits: the streams packed back to back by the host (rmem_ocu_amd/png.py PackedPngs) -- every stream starts on an 8-byte boundary of
+ * an 8-byte aligned buffer and is followed by at least 8 zero bytes; descs[f] (device) says where stream f lies and how its samples
+ * are stored.  Only the compressed bytes and the descriptors cross PCIe; the chunk walk and the chunk CRC-32s stay on the host.
+ * Accepted: non-interlaced PNG of colour type 3 (indexed) at bit depth 1, 2, 4 or 8, or colour type 0 (grey) at bit depth 8; all
+ *   frames of a call share H and W, depth and colour type are per frame.  zlib: CM = 8, CINFO <= 7, no preset dictionary.  DEFLATE:
+ *   stored, fixed and dynamic blocks in any number and mix, distances up to 32768, lengths up to 258, overlapping copies.  All five
+ *   row filters (the filter unit is one byte for every accepted format).  Samples below 8 bits are unpacked most significant bits
+ *   first; a row's padding bits are ignored.
+ * lut: 256 device bytes applied to every sample (palette index or grey value, e.g. 255 -> 1), or NULL.
+ * status (device, int [frames]) is written for every frame by the call, 0 = decoded and its Adler-32 verified.  A frame whose
+ * status is not zero is zero-filled in `out`: every byte of out is written by every call.  The first error ends a stream, so one
+ * bit is set:
+ *   ST_INPUT   the stream needs more bits than it has (reads beyond its end return zero and touch no memory)
+ *   ST_SIZE    the inflated bytes would exceed, or end short of, H * (1 + ceil(W * depth / 8))
+ *   ST_RANGE   a match reaches back before the first byte
+ *   ST_CODE    block type 3, stored LEN != ~NLEN, HLIT > 286 or HDIST > 30, an over-subscribed or (other than zlib's single
+ *              one-bit code) incomplete code, no end-of-block code, a repeat with no previous length or running over HLIT + HDIST,
+ *              a bit pattern that is no code, literal/length symbol 286 / 287, distance symbol 30 / 31
+ *   ST_HEADER  CM != 8, CINFO > 7, FCHECK wrong, FDICT set
+ *   ST_ADLER   the Adler-32 of the inflated bytes differs from the trailer
+ *   ST_FILTER  a row's filter type is above 4
+ *   ST_DESC    a descriptor outside the accepted formats, or a misaligned offset
+ * workspace: rmem_png_decode_workspace_bytes bytes, 16-byte aligned: the inflated (filtered) bytes of every frame, sized for depth 8.
+ * Replaces dataloaders/eval_datasets.py (Image.open of an annotation file, np.array, one host-to-device copy of H * W bytes per
+ * frame). */
+typedef struct RmemPngDesc {
+  long long offset;     /* of the stream in bits, a multiple of 8 */
+  long long bytes;      /* of the stream (without the padding) */
+  int bit_depth;        /* 1, 2, 4, 8 */
+  int colour_type;      /* 3, or 0 with bit depth 8 */
+} RmemPngDesc;
+#define RMEM_PNG_ST_INPUT 1
+#define RMEM_PNG_ST_SIZE 2
+#define RMEM_PNG_ST_RANGE 4
+#define RMEM_PNG_ST_CODE 8
+#define RMEM_PNG_ST_HEADER 16
+#define RMEM_PNG_ST_ADLER 32
+#define RMEM_PNG_ST_FILTER 64
+#define RMEM_PNG_ST_DESC 128
+size_t rmem_png_decode_workspace_bytes(int frames, int H, int W);   /* host only, 0 on bad geometry (H * W <= 2^26) */
+int rmem_png_decode_labels(const unsigned char* bits, const RmemPngDesc* descs /* device */, int frames, int H, int W,
+                           const unsigned char* lut /* device, 256 bytes, or NULL */, void* workspace,
+                           unsigned char* out /* device [frames][H][W] */, int* status /* device [frames] */, void* stream);
 
 /* ------------------------------------------------------------------ stream capture helpers
  * Thin wrappers over hipStreamBeginCapture / hipGraphInstantiate / hipGraphLaunch so the Python host

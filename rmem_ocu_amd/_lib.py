@@ -11,7 +11,7 @@ import subprocess
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('RMEM_LIB_PATH') or os.path.join(_HERE, 'librmem_hip.so')   # override: kernel experiments only
-ABI_VERSION = 11
+ABI_VERSION = 12
 
 
 class RmemError(RuntimeError):
@@ -61,6 +61,10 @@ class JpegPlan(C.Structure):
 
 
 JPEG_FORCE_FALLBACK = 1
+
+
+class PngDesc(C.Structure):
+    _fields_ = [('offset', C.c_longlong), ('bytes', C.c_longlong), ('bit_depth', C.c_int), ('colour_type', C.c_int)]
 
 
 def _desc(name, ints, ptrs):
@@ -144,6 +148,8 @@ SIGNATURES = {
     'rmem_png_zlib_bound': (C.c_size_t, [_i, _i]),
     'rmem_png_workspace_bytes': (C.c_size_t, [_i, _i, _i]),
     'rmem_png_encode_labels': (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
+    'rmem_png_decode_workspace_bytes': (C.c_size_t, [_i, _i, _i]),
+    'rmem_png_decode_labels': (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
     'rmem_split_label': (_i, [_vp, _i, _i, _vp, _ll, _vp]),
     'rmem_soft_logit_aggregate': (_i, [C.POINTER(_vp), _i, _i, _i, _i, _i, _vp, _vp]),
     'rmem_copy_async': (_i, [_vp, _vp, C.c_size_t, _vp]),

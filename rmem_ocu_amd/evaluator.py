@@ -12,6 +12,8 @@ Mirrors what networks/managers/evaluator.py:330-568 does for one sequence, witho
   * whole stacks of predicted masks are written as palette PNGs from the device: the DEFLATE payload of every frame is encoded
     there and only the few KB of each file cross to the host -- rmem_png_encode_labels, save_masks, png.encode_label_stack
     (save_mask, one host mask through Pillow, stays as it is);
+  * annotation files are decoded on the device too: only the compressed bytes cross to it -- rmem_png_decode_labels,
+    labels_from_pngs, png.decode_label_stack;
   * whole clips are scored on the device with J and the boundary accuracy F (the benchmark toolkit's db_eval_iou /
     db_eval_boundary and its per-sequence mean, recall and decay) -- rmem_clip_score_counts, score_clip.
 """
@@ -263,6 +265,14 @@ def frames_from_jpegs(paths_or_bytes: Sequence, device, scale: float = 1.0) -> t
         ops.run([ops.ingest_rgb8(rgb[b], Hs=hs, Ws=ws, Hd=H, Wd=W, out_chw=out[k + b]) for b in range(m)], stream)
     clip.check(device, stream=stream)
     return out
+
+
+def labels_from_pngs(paths_or_bytes: Sequence, device, lut=None) -> torch.Tensor:
+    """A clip's annotation files (paths or bytes, one size; indexed PNGs, or 8-bit grey ones such as 0 / 255 masks with
+    lut[255] = 1) -> uint8 [n, H, W] label maps on the device, decoded there (png.decode_label_stack): the ground truth
+    score_clip takes, and with gt[0].float()[None, None] the first-frame mask of a run."""
+    from . import png
+    return png.decode_label_stack(paths_or_bytes, device, lut)
 
 
 class SequenceEvaluator:

@@ -1,4 +1,6 @@
-"""Predicted label maps -> indexed PNG files, the DEFLATE payload encoded on the device (rmem_png_encode_labels, include/rmem.h).
+"""Palette PNGs on the device, both directions.
+
+Writing: predicted label maps -> indexed PNG files, the DEFLATE payload encoded on the device (rmem_png_encode_labels, include/rmem.h).
 
 Replaces the Pillow encoder inside evaluator.save_mask (utils/image.py:90-106) for stacks of masks: the labels stay on the device,
 one call encodes every frame of a stack into a zlib stream of a fixed-Huffman, run-length-only format, and only those streams (a
@@ -7,11 +9,21 @@ on the host with zlib.crc32: they run over a few KB per frame.
 
     files = png.encode_label_stack(slot.labels[c, 1:n])            # after engine.synchronize(): one PNG file (bytes) per frame
     evaluator.save_masks(slot.labels[c, 1:n], paths, squeeze_idx)  # the same, written to paths
+
+Reading: annotation files -> uint8 label maps on the device (rmem_png_decode_labels).  Replaces Image.open of an annotation in
+dataloaders/eval_datasets.py: `parse` walks the chunks and checks their CRC-32s on the host (a few KB per file), PackedPngs packs the
+zlib streams of a clip's files into one pinned buffer, and only those bytes cross to the device, where they are inflated,
+unfiltered, unpacked and (optionally) mapped through a 256-entry table.
+
+    gt = png.decode_label_stack(paths, device)                      # uint8 [n, H, W], Pillow's np.array(Image.open(p)) bit for bit
+    gt = evaluator.labels_from_pngs(paths, device)                  # the same
 """
 from __future__ import annotations
 
 import struct
 import zlib
+import ctypes as C
+from dataclasses import dataclass
 from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
@@ -126,3 +138,288 @@ def encode_label_stack(labels_u8: torch.Tensor, squeeze_idx: Optional[Sequence[i
         data = data_h[:total].numpy().tobytes()
         files += [wrap(data[off[i]:off[i + 1]], H, W, palette) for i in range(m)]
     return files
+
+
+# ---------------------------------------------------------------------------------------------------------------- reading
+
+ST_INPUT, ST_SIZE, ST_RANGE, ST_CODE, ST_HEADER, ST_ADLER, ST_FILTER, ST_DESC = 1, 2, 4, 8, 16, 32, 64, 128    # include/rmem.h
+STATUS_NAMES = {ST_INPUT: 'the stream ends too early', ST_SIZE: 'wrong number of inflated bytes', ST_RANGE: 'distance too far back',
+                ST_CODE: 'invalid block or code', ST_HEADER: 'bad zlib header', ST_ADLER: 'Adler-32 mismatch',
+                ST_FILTER: 'filter type above 4', ST_DESC: 'bad descriptor'}
+MAX_PIXELS = 1 << 26
+_dec_ws: Dict[Tuple[int, int], torch.Tensor] = {}          # (device index, stream) -> inflated bytes, grow-only
+
+
+class PngUnsupported(_lib.RmemError):
+    """A well-formed PNG file in a format the device decoder refuses (decode_label_stack(host_fallback=True) hands these, and only
+    these, to Pillow)."""
+
+
+@dataclass
+class PngInfo:
+    width: int
+    height: int
+    bit_depth: int
+    colour_type: int
+    interlace: int
+    palette: Optional[bytes]                   # the PLTE payload (3 bytes per entry), or None
+    idat_ranges: List[Tuple[int, int]]         # [begin, end) of every IDAT payload in the file
+
+    def refusal(self) -> Optional[str]:
+        """why the device decoder does not take this file, or None"""
+        if self.interlace:
+            return 'interlaced PNG'
+        if self.bit_depth == 16:
+            return '16-bit samples'
+        if self.colour_type in (2, 4, 6):
+            return f'colour type {self.colour_type} (only indexed and 8-bit grey are decoded)'
+        if self.colour_type == 0 and self.bit_depth != 8:
+            return f'grey at bit depth {self.bit_depth} (only 8)'
+        if self.colour_type not in (0, 3) or self.bit_depth not in (1, 2, 4, 8):
+            return f'colour type {self.colour_type} at bit depth {self.bit_depth}'
+        if self.width * self.height > MAX_PIXELS:
+            return f'frame too large (H * W must not exceed 2^26, got {self.height}x{self.width})'
+        return None
+
+
+def _read(f) -> bytes:
+    if isinstance(f, (bytes, bytearray, memoryview)):
+        return bytes(f)
+    with open(f, 'rb') as fh:
+        return fh.read()
+
+
+def parse(data, check: bool = True) -> PngInfo:
+    """The chunks of one PNG file (no GPU needed): every chunk's CRC-32 is verified here.  A damaged file raises RmemError with the
+    reason; a sound file in a format the device decoder refuses raises PngUnsupported unless check is False."""
+    data = _read(data)
+    if data[:8] != _SIGNATURE:
+        raise _lib.RmemError('png.parse: bad signature (not a PNG file)')
+    at, ihdr, palette, idat, end = 8, None, None, [], False
+    while at < len(data) and not end:
+        if at + 12 > len(data):
+            raise _lib.RmemError(f'png.parse: truncated chunk header at byte {at}')
+        n, kind = struct.unpack('>I4s', data[at:at + 8])
+        if at + 12 + n > len(data):
+            raise _lib.RmemError(f'png.parse: chunk {kind!r} at byte {at} runs past the end of the file')
+        body = data[at + 8:at + 8 + n]
+        if zlib.crc32(data[at + 4:at + 8 + n]) & 0xFFFFFFFF != struct.unpack('>I', data[at + 8 + n:at + 12 + n])[0]:
+            raise _lib.RmemError(f'png.parse: chunk CRC mismatch in {kind!r} at byte {at}')
+        if ihdr is None and kind != b'IHDR':
+            raise _lib.RmemError('png.parse: missing IHDR (it must be the first chunk)')
+        if kind == b'IHDR':
+            if n != 13:
+                raise _lib.RmemError('png.parse: IHDR must have 13 bytes')
+            ihdr = struct.unpack('>IIBBBBB', body)
+        elif kind == b'PLTE':
+            palette = body
+        elif kind == b'IDAT':
+            idat.append((at + 8, at + 8 + n))
+        elif kind == b'IEND':
+            end = True
+        at += 12 + n                                    # every other chunk is ancillary here: skipped
+    if ihdr is None:
+        raise _lib.RmemError('png.parse: missing IHDR')
+    if not idat:
+        raise _lib.RmemError('png.parse: missing IDAT')
+    if not end:
+        raise _lib.RmemError('png.parse: missing IEND')
+    w, h, depth, ctype, comp, filt, interlace = ihdr
+    if w < 1 or h < 1 or comp != 0 or filt != 0 or interlace > 1 or (ctype, depth) not in {
+            (0, 1), (0, 2), (0, 4), (0, 8), (0, 16), (2, 8), (2, 16), (3, 1), (3, 2), (3, 4), (3, 8), (4, 8), (4, 16), (6, 8), (6, 16)}:
+        raise _lib.RmemError(f'png.parse: invalid IHDR {ihdr}')
+    info = PngInfo(w, h, depth, ctype, interlace, palette, idat)
+    if check and info.refusal():
+        raise PngUnsupported(f'png.parse: {info.refusal()}')
+    return info
+
+
+class _DevicePngs:
+    """a pack on one device: the stream bytes (filled range by range), the descriptor table, one status word per frame"""
+
+    def __init__(self, packed: 'PackedPngs', device):
+        self.bits = torch.empty(packed.buf.numel(), dtype=torch.uint8, device=device)
+        self.descs = packed.desc_bytes.to(device)
+        self.status = torch.zeros(len(packed), dtype=torch.int32, device=device)
+        torch.cuda.current_stream(device).synchronize()                # both are complete before any decode stream reads them
+
+
+class PackedPngs:
+    """Annotation files (paths or bytes) of one size, parsed once: the IDAT payloads of every file concatenated into its zlib
+    stream, the streams packed back to back into one pinned buffer -- each 8-byte aligned and followed by at least 8 zero bytes --
+    and the descriptor table (RmemPngDesc).  Bit depth and colour type may differ per frame."""
+
+    def __init__(self, files: Sequence):
+        datas = [_read(f) for f in files]
+        if not datas:
+            raise _lib.RmemError('PackedPngs: no files')
+        self.infos = [parse(d) for d in datas]
+        sizes = sorted({(i.height, i.width) for i in self.infos})
+        if len(sizes) != 1:
+            raise _lib.RmemError(f'PackedPngs: frames of one pack must share one size, got {sizes}')
+        self.height, self.width = sizes[0]
+        self.shape = torch.Size((len(datas), self.height, self.width))
+        streams = [b''.join(d[a:b] for a, b in i.idat_ranges) for d, i in zip(datas, self.infos)]
+        self.descs = (_lib.PngDesc * len(datas))()
+        at = 0
+        for k, (st, i) in enumerate(zip(streams, self.infos)):
+            self.descs[k] = _lib.PngDesc(at, len(st), i.bit_depth, i.colour_type)
+            at += (len(st) + 8 + 7) & ~7
+        host = np.zeros(at, dtype=np.uint8)
+        for d, st in zip(self.descs, streams):
+            host[d.offset:d.offset + len(st)] = np.frombuffer(st, dtype=np.uint8)
+        pin = torch.cuda.is_available()                                # packing itself needs no GPU
+        self.buf = torch.from_numpy(host)
+        self.desc_bytes = torch.frombuffer(bytearray(self.descs), dtype=torch.uint8)
+        if pin:
+            self.buf, self.desc_bytes = self.buf.pin_memory(), self.desc_bytes.pin_memory()
+        self.offsets = [int(d.offset) for d in self.descs]
+        self.ends = self.offsets[1:] + [at]                            # a frame's range includes its padding
+        self.palettes = [i.palette for i in self.infos]
+        self.compressed_bytes = sum(len(st) for st in streams)
+        self._dev: Dict[int, _DevicePngs] = {}
+
+    def __len__(self):
+        return len(self.descs)
+
+    def on_device(self, device) -> _DevicePngs:
+        device = torch.device(device)
+        key = device.index or 0
+        if key not in self._dev:
+            self._dev[key] = _DevicePngs(self, device)
+        return self._dev[key]
+
+    def status(self, device) -> torch.Tensor:
+        return self.on_device(device).status
+
+    def check(self, device, first: int = 0, count: Optional[int] = None, stream=None):
+        """Synchronise ``stream`` (the one the frames were decoded on; default: the current stream) and raise RmemError naming the
+        first frame of first .. first+count-1 whose status word is not zero, and its bits."""
+        device = torch.device(device)
+        count = len(self) - first if count is None else count
+        _stream_of(device, stream).synchronize()
+        st = self.status(device)[first:first + count].cpu()
+        bad = torch.nonzero(st).flatten().tolist()
+        if bad:
+            k = bad[0]
+            reasons = ', '.join(v for b, v in STATUS_NAMES.items() if int(st[k]) & b)
+            raise _lib.RmemError(f'PNG frame {first + k} failed to decode on the GPU (status {int(st[k])}: {reasons})'
+                                 + (f'; {len(bad)} frames bad' if len(bad) > 1 else ''))
+
+
+def _stream_of(device, stream) -> torch.cuda.Stream:
+    if stream is None:
+        return torch.cuda.current_stream(device)
+    if isinstance(stream, torch.cuda.Stream):
+        return stream
+    from .jpeg import _torch_stream
+    return _torch_stream(device, int(stream))
+
+
+def _device_lut(lut, dev, what) -> Optional[torch.Tensor]:
+    if lut is None:
+        return None
+    if not isinstance(lut, torch.Tensor):
+        arr = np.asarray(lut)
+        if arr.dtype != np.uint8 or arr.shape != (256,):
+            raise _lib.RmemError(f'{what}: lut must be 256 contiguous uint8 values')
+        return torch.from_numpy(np.ascontiguousarray(arr)).to(dev)
+    if lut.dtype != torch.uint8 or lut.numel() != 256 or lut.dim() != 1 or not lut.is_contiguous() or lut.device != dev:
+        raise _lib.RmemError(f'{what}: lut must be 256 contiguous uint8 values on the output\'s device')
+    return lut
+
+
+def decode_labels_into(packed: PackedPngs, out: torch.Tensor, first: int = 0, count: Optional[int] = None, stream=None, lut=None):
+    """Frames first .. first+count-1 of `packed` into out (uint8 [count, H, W], contiguous, device) on ``stream`` (a
+    torch.cuda.Stream or a raw handle; default: the current stream).  Nothing waits for the GPU: the compressed bytes are copied
+    from pinned memory on the stream, the status words land in packed.status(device)[first:first+count] and are read later by
+    packed.check(device).  The workspace is one buffer per (device, stream) that only grows, allocated on that stream."""
+    count = len(packed) - first if count is None else count
+    if not isinstance(packed, PackedPngs) or not 0 <= first or count < 1 or first + count > len(packed):
+        raise _lib.RmemError(f'png.decode_labels_into: frames {first}..{first + count - 1} of {len(packed)}')
+    H, W = packed.height, packed.width
+    if not isinstance(out, torch.Tensor) or out.dtype != torch.uint8 or not out.is_cuda:
+        raise _lib.RmemError('png.decode_labels_into: out must be a uint8 device tensor')
+    if tuple(out.shape) != (count, H, W) or not out.is_contiguous():
+        raise _lib.RmemError(f'png.decode_labels_into: out must be a contiguous [{count}, {H}, {W}] tensor (got {tuple(out.shape)})')
+    dev = out.device
+    lut = _device_lut(lut, dev, 'png.decode_labels_into')
+    ts = _stream_of(dev, stream)
+    L = _lib.lib()
+    nbytes = L.rmem_png_decode_workspace_bytes(count, H, W)
+    if nbytes == 0:
+        raise _lib.RmemError(f'png.decode_labels_into: frame too large (H * W must not exceed 2^26, got {H}x{W})')
+    dc = packed.on_device(dev)
+    key = (dev.index or 0, ts.cuda_stream)
+    ws = _dec_ws.get(key)
+    if ws is None or ws.numel() < nbytes:
+        with torch.cuda.stream(ts):
+            ws = _dec_ws[key] = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    for t in (dc.bits, dc.descs, dc.status, out) + (() if lut is None else (lut,)):
+        t.record_stream(ts)
+    a, b = packed.offsets[first], packed.ends[first + count - 1]
+    from . import ops
+    ops.copy_async(dc.bits[a:b], packed.buf[a:b], b - a)(ts.cuda_stream)
+    _lib.check(L.rmem_png_decode_labels(dc.bits.data_ptr(), dc.descs.data_ptr() + C.sizeof(_lib.PngDesc) * first, count, H, W,
+                                        None if lut is None else lut.data_ptr(), ws.data_ptr(), out.data_ptr(),
+                                        dc.status.data_ptr() + 4 * first, ts.cuda_stream), 'rmem_png_decode_labels')
+
+
+def _host_label(data: bytes) -> np.ndarray:
+    import io
+
+    from PIL import Image
+    arr = np.array(Image.open(io.BytesIO(data)))                       # palette indices, not RGB
+    if arr.ndim != 2 or arr.min() < 0 or arr.max() > 255:
+        raise _lib.RmemError(f'png.decode_label_stack: not a label map (Pillow gives shape {arr.shape}, dtype {arr.dtype})')
+    return arr.astype(np.uint8)
+
+
+def decode_label_stack(files_or_packed, device, lut=None, host_fallback: bool = False) -> torch.Tensor:
+    """uint8 [n, H, W] label maps on `device` of n annotation files of one size (paths, bytes, or a PackedPngs): what
+    np.array(Image.open(f)) gives per file, bit for bit, through `lut` (256 uint8 values) if given.  At most CHUNK frames per
+    decode call; after the last one, one synchronisation and one readback of the status words: a non-zero word raises RmemError
+    naming the frame and the bits.  host_fallback: files in a format the device decoder refuses (not damaged ones) are decoded by
+    Pillow and uploaded instead of raising PngUnsupported."""
+    device = torch.device(device)
+    if device.type != 'cuda':
+        raise _lib.RmemError('png.decode_label_stack: the target must be a GPU device (there is no host decoder)')
+    if device.index is None:
+        device = torch.device('cuda', torch.cuda.current_device())
+    lut = _device_lut(lut, device, 'png.decode_label_stack')
+    if isinstance(files_or_packed, (bytes, bytearray, memoryview, str)):
+        files_or_packed = [files_or_packed]
+    host: Dict[int, np.ndarray] = {}
+    if isinstance(files_or_packed, PackedPngs):
+        packed, n, on_dev = files_or_packed, len(files_or_packed), list(range(len(files_or_packed)))
+    else:
+        datas = [_read(f) for f in files_or_packed]
+        n = len(datas)
+        if host_fallback:
+            for k, d in enumerate(datas):
+                try:
+                    parse(d)
+                except PngUnsupported:
+                    host[k] = _host_label(d)
+        on_dev = [k for k in range(n) if k not in host]
+        packed = PackedPngs([datas[k] for k in on_dev]) if on_dev else None
+    if packed is not None:
+        H, W = packed.height, packed.width
+    else:
+        H, W = next(iter(host.values())).shape
+    if any(a.shape != (H, W) for a in host.values()):
+        raise _lib.RmemError('png.decode_label_stack: frames of one stack must share one size')
+    stream = torch.cuda.current_stream(device)
+    out = torch.empty(n, H, W, dtype=torch.uint8, device=device)
+    dec = out if not host else torch.empty(len(on_dev), H, W, dtype=torch.uint8, device=device)
+    for k in range(0, len(on_dev), CHUNK):
+        m = min(CHUNK, len(on_dev) - k)
+        decode_labels_into(packed, dec[k:k + m], k, m, stream, lut)
+    if host:
+        if on_dev:
+            out[torch.tensor(on_dev, device=device)] = dec
+        up = torch.from_numpy(np.stack([host[k] for k in sorted(host)])).to(device)
+        out[torch.tensor(sorted(host), device=device)] = up if lut is None else lut[up.long()]
+    if packed is not None:
+        packed.check(device, 0, len(on_dev), stream)
+    return out
