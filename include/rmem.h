@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define RMEM_ABI_VERSION 12
+#define RMEM_ABI_VERSION 13
 
 int rmem_abi_version(void);
 const char* rmem_last_error_string(void);
@@ -68,6 +68,37 @@ typedef struct rmem_conv_desc {
 size_t rmem_conv_workspace_bytes(const rmem_conv_desc* desc);
 int rmem_conv2d_nhwc(const rmem_conv_desc* desc, const void* x, const void* w, const float* bias,
                      const void* residual, void* y, void* y2, void* workspace, void* stream);
+
+/* The launch plan of a convolution / linear problem: which kernel family, ring depth, split count and grid rmem_conv2d_nhwc,
+ * rmem_conv1x1_dual_nhwc or rmem_linear_grouped give it.  A pure host function of the geometry (no pointer, no GPU): the three
+ * entry points take their decision from the same function.  The same for both element types. */
+enum rmem_gemm_family {
+  RMEM_GEMM_GENERAL64 = 0, /* 64x64 tile, per-lane addresses (any Cin % 8 == 0); the only family that is split along K */
+  RMEM_GEMM_SCALAR64 = 1,  /* 64x64, scalar k-walk (Cin % 64 == 0) */
+  RMEM_GEMM_ROWRUN64 = 2,  /* 64x64, row-run (KW * Cin contiguous elements per filter row) */
+  RMEM_GEMM_ONE128 = 3,    /* 128x128, scalar k-walk, every wave loads and multiplies */
+  RMEM_GEMM_PC128 = 4,     /* 128x128, scalar k-walk, producer / consumer waves (512 threads) */
+  RMEM_GEMM_ROWRUN128 = 5, /* 128x128, row-run */
+  RMEM_GEMM_DUAL64 = 6,    /* rmem_conv1x1_dual_nhwc, 64x64 */
+  RMEM_GEMM_DUAL128 = 7,   /* rmem_conv1x1_dual_nhwc, 128x128 */
+  RMEM_GEMM_GROUPED = 8    /* rmem_linear_grouped, 64x64 (scalar k-walk when fast == 1, else per-lane addresses) */
+};
+enum rmem_gemm_entry { RMEM_GEMM_ENTRY_CONV2D = 0, RMEM_GEMM_ENTRY_DUAL = 1, RMEM_GEMM_ENTRY_GROUPED = 2 };
+typedef struct rmem_gemm_plan {
+  int family;           /* enum rmem_gemm_family */
+  int tile;             /* output tile edge: 64 or 128 */
+  int ring;             /* LDS ring depth of the k-loop: 1, 2 or 3 */
+  int is1x1;            /* 1x1 stride-1 pad-0 problem (a plain GEMM) */
+  int fast;             /* address form the geometry allows: 0 general, 1 scalar k-walk, 2 row-run */
+  int splits;           /* > 1: split along K over grid_z, followed by the slab-summing epilogue kernel */
+  int steps_per_split;  /* k-steps (of 64) per slice; all of them when splits == 1 */
+  int xcd_ny;           /* > 0: 1-D grid in XCD-aware order, xcd_ny column tiles per row tile; 0: plain 2-D grid */
+  int grid_x, grid_y, grid_z, threads;
+} rmem_gemm_plan;
+/* desc as for the entry point named by `entry` (enum rmem_gemm_entry); has_workspace: a split-K workspace would be passed
+ * (rmem_conv2d_nhwc only); extra: Cin2 of rmem_conv1x1_dual_nhwc, n of rmem_linear_grouped, otherwise ignored.
+ * Returns -1 for the geometry errors the entry point itself reports. */
+int rmem_conv_plan(const rmem_conv_desc* desc, int has_workspace, int entry, int extra, rmem_gemm_plan* plan);
 
 /* n <= 4 GEMMs of IDENTICAL shape (desc: 1x1, stride 1) with different operands as one launch: the per-layer linears of one
  * memory update (linear_QMem / linear_VMem / linear_V of layers/transformer.py:279-285 for the 3 LSTT layers) do not depend on

@@ -11,7 +11,7 @@ import subprocess
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('RMEM_LIB_PATH') or os.path.join(_HERE, 'librmem_hip.so')   # override: kernel experiments only
-ABI_VERSION = 12
+ABI_VERSION = 13
 
 
 class RmemError(RuntimeError):
@@ -22,6 +22,15 @@ class ConvDesc(C.Structure):
     _fields_ = [(n, C.c_int) for n in ('H', 'W', 'Cin', 'Ho', 'Wo', 'Cout', 'KH', 'KW', 'stride', 'pad',
                                        'ldo', 'ldr', 'ld2', 'relu', 'out_f32', 'res_f32', 'ldx', 'batch', 'act_begin',
                                        'res_up_h', 'res_up_w', 'res_up_align')]
+
+
+class GemmPlan(C.Structure):
+    _fields_ = [(n, C.c_int) for n in ('family', 'tile', 'ring', 'is1x1', 'fast', 'splits', 'steps_per_split', 'xcd_ny',
+                                       'grid_x', 'grid_y', 'grid_z', 'threads')]
+
+
+GEMM_FAMILIES = ('general64', 'scalar64', 'rowrun64', 'one128', 'pc128', 'rowrun128', 'dual64', 'dual128', 'grouped')   # enum rmem_gemm_family
+GEMM_ENTRIES = ('conv2d', 'conv1x1_dual', 'linear_grouped')                                                              # enum rmem_gemm_entry
 
 
 class BneckChainDesc(C.Structure):
@@ -86,6 +95,7 @@ SIGNATURES = {
     'rmem_last_error_string': (C.c_char_p, []),
     'rmem_conv_workspace_bytes': (C.c_size_t, [C.POINTER(ConvDesc)]),
     'rmem_conv2d_nhwc': (_i, [C.POINTER(ConvDesc), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    'rmem_conv_plan': (_i, [C.POINTER(ConvDesc), _i, _i, _i, C.POINTER(GemmPlan)]),
     'rmem_attn_workspace_bytes': (C.c_size_t, [_i, _i, _i]),
     'rmem_mem_read_attn': (_i, [_vp, _i, _vp, _vp, _ll, _i, _vp, _i, _i, _vp, _vp, _i, _i, _vp, _i, _vp, _i, _vp, _vp]),
     'rmem_profile_start': (_i, [_i]),

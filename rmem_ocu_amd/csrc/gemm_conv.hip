@@ -9,15 +9,25 @@
 // of the reference (encoders/resnet.py:48-68,
 // decoders/fpn.py:36-68, layers/transformer.py:576, 675, 685, models/aot.py:112, 133).
 //
-// Tiling: 256 threads = 4 waves in a 2x2 grid over a BM x BN block tile, BK = 64,
-// v_mfma_f32_16x16x32_bf16 (two MFMAs per k-step and 16x16 sub-tile), fp32 accumulation.
-// Global -> register -> LDS staging: a ring of PF register stages keeps PF k-tiles in flight
-// from HBM/L2 (these problems run at ~1 workgroup per CU, so latency is hidden inside the
-// workgroup, not by occupancy); LDS is double-buffered with one barrier per k-step.  LDS rows
-// are 128 B; the 16-byte chunk index is XOR-swizzled with (row >> 1) & 7 so the four 16-lane
-// groups of a ds_read_b128 fragment read hit 16 distinct 16-byte slots of the 256-byte bank row.
+// Staging: global -> LDS goes through LDS-DMA (global_load_lds_dwordx4 / buffer_load_dwordx4 ... lds): no VGPR staging and
+// no ds_write.  Each wave-instruction fills 8 rows x 128 B of a tile linearly; LDS rows are 128 B (BK = 64) and the 16-byte
+// chunk index is XOR-swizzled with (row >> 1) & 7 -- applied to the per-lane SOURCE address -- so the four 16-lane groups of
+// a ds_read_b128 fragment read hit 16 distinct 16-byte slots of the 256-byte bank row.  Padded / out-of-range pieces read a
+// 16-byte zero buffer (general form) or are zero-filled by the buffer descriptor's range check (fast forms).  The k-loop is
+// an LDS ring of 1 to 3 stages with counted vmcnt + raw s_barrier, v_mfma_f32_16x16x32 (two MFMAs per k-step and 16x16
+// sub-tile), fp32 accumulation.  One body, conv_gemm_dma_body, in three address forms (MODE): general (per-lane 64-bit
+// addresses, any Cin % 8 == 0), scalar k-walk (Cin % 64 == 0) and row-run (KW * Cin contiguous elements per filter row),
+// plus the dual-source form of the scalar walk.
 //
-// Epilogue: the accumulators go through LDS (fp32, half a tile at a time) so that every
+// Three tile forms:
+//   64x64, 256 threads (k_conv_gemm_dma, k_gemm_dma_grouped): a single 16 KB buffer lets 8 workgroups share a CU; a 3-deep
+//     ring where there are too few workgroups for that.  The only form that is split along K.
+//   128x128, 256 threads (k_conv_gemm_dma_big): half the global -> LDS bytes per flop for the many-row, deep-K problems.
+//   128x128 producer / consumer, 512 threads (k_conv_gemm_dma_pc): four loader waves issue the DMA, four waves run the MFMAs.
+// (The register-staged 64x64 / 128x64 / 128x128 kernels this file began with were never faster -- 1962 vs 1981 frames/s with
+// 4 clips per launch -- and were removed together with the switches that reached them; they are in the history.)
+//
+// Epilogue: the accumulators go through LDS (fp32, 32 rows at a time) so that every
 // thread finishes 8 consecutive channels of one output row: bias / residual / second
 // output / store are 16- or 32-byte accesses instead of 2-byte scatters.
 //
@@ -25,6 +35,10 @@
 // cut along K over gridDim.z; each slice stores an fp32 slab with plain 16-byte stores
 // and k_splitk_epilogue sums the slabs in slice order (bitwise reproducible, no atomics)
 // while applying the same fused epilogue.
+//
+// Selection: gemm_plan() is the ONE place that decides which kernel, ring depth, split count and grid a problem gets -- a
+// pure host function of the geometry, the entry point and the four knobs of GemmKnobs; launch() turns a plan into the
+// launch, and rmem_conv_plan() shows the plan to the host (tests/test_gemm_plan_host.py checks it without a GPU).
 #include "common.h"
 #include "../../include/rmem.h"
 #include <stdlib.h>
@@ -158,189 +172,12 @@ __device__ __forceinline__ void finish1(const ConvParams& p, int m, int n, float
   else reinterpret_cast<e16*>(p.y)[(long)m * p.ldo + n] = (e16)v;
 }
 
-template <int BM, int BN, int PF, bool IS1X1, bool SPLITK>
-__global__ __launch_bounds__(256) void k_conv_gemm(ConvParams p) {
-  constexpr int BK = 64;
-  constexpr int NA = BM / 32;  // 16-byte A chunks per thread per k-step (BM rows x 8 chunks / 256 threads)
-  constexpr int NB = BN / 32;
-  constexpr int TM = BM / 32;  // 16x16 tiles per wave along M
-  constexpr int TN = BN / 32;
-  constexpr int CP = BN + 4;   // padded fp32 row of the epilogue staging tile
-  constexpr int AB_BYTES = 2 * (BM + BN) * BK * 2;
-  constexpr int C_BYTES = (BM / 2) * CP * 4;
-  constexpr int SMEM = AB_BYTES > C_BYTES ? AB_BYTES : C_BYTES;
-  __shared__ __attribute__((aligned(16))) char smem[SMEM];
-  e16* As = reinterpret_cast<e16*>(smem);                 // [2][BM*64]
-  e16* Bs = As + 2 * BM * BK;                              // [2][BN*64]
-
-  const int tid = threadIdx.x;
-  const int lane = tid & 63;
-  const int wave = tid >> 6;
-  const int wm = wave >> 1, wn = wave & 1;
-  const int m0 = blockIdx.x * BM;
-  const int n0 = blockIdx.y * BN;
-  const int nk_total = (p.K + BK - 1) / BK;
-  const int kt0 = SPLITK ? blockIdx.z * p.steps_per_split : 0;
-  const int kt1 = SPLITK ? min(nk_total, kt0 + p.steps_per_split) : nk_total;
-
-  // ---- per-thread gather state for the A operand: chunk id = tid + i*256 -> (row = id >> 3, chunk = id & 7) ----
-  const int a_chunk = tid & 7;             // same for every i (256 % 8 == 0)
-  long a_base[NA];
-  int a_hi0[NA], a_wi0[NA];
-  bool a_ok[NA];
-  int a_ci, a_kw, a_kh;                    // k position of this thread's chunk column (shared by its rows)
-#pragma unroll
-  for (int i = 0; i < NA; ++i) {
-    const int m = m0 + (tid >> 3) + i * 32;
-    a_ok[i] = m < p.M;
-    if (IS1X1) {
-      a_base[i] = (long)m * p.ldx;
-      a_hi0[i] = a_wi0[i] = 0;
-    } else {
-      const int img = m / p.HoWo, rem = m - img * p.HoWo;      // batch of images: rows are [image][ho][wo]
-      const int ho = rem / p.Wo, wo = rem - ho * p.Wo;
-      a_hi0[i] = ho * p.stride - p.pad;
-      a_wi0[i] = wo * p.stride - p.pad;
-      a_base[i] = (long)img * p.H * p.W * p.Cin;
-    }
-  }
-  if (IS1X1) {
-    a_ci = a_kw = a_kh = 0;
-  } else {
-    const int kidx = kt0 * BK + a_chunk * 8;
-    const int kk = kidx / p.Cin;
-    a_ci = kidx - kk * p.Cin;
-    a_kh = kk / p.KW;
-    a_kw = kk - a_kh * p.KW;
-  }
-  const int b_chunk = tid & 7;
-
-  const e16x8 zero8 = {0, 0, 0, 0, 0, 0, 0, 0};
-  // register ring: PF tiles of (A, B) pieces in flight from HBM/L2 while earlier tiles are being multiplied
-  e16x8 ra[PF][NA], rb[PF][NB];
-
-  auto load_tile = [&](e16x8 (&xa)[NA], e16x8 (&xb)[NB], int k0) {
-#pragma unroll
-    for (int i = 0; i < NA; ++i) {
-      e16x8 v = zero8;
-      if (IS1X1) {
-        const int kidx = k0 + a_chunk * 8;
-        if (a_ok[i] && kidx < p.K) v = *reinterpret_cast<const e16x8*>(p.x + a_base[i] + kidx);
-      } else {
-        const int hi = a_hi0[i] + a_kh, wi = a_wi0[i] + a_kw;
-        if (a_ok[i] && a_kh < p.KH && (unsigned)hi < (unsigned)p.H && (unsigned)wi < (unsigned)p.W)
-          v = *reinterpret_cast<const e16x8*>(p.x + a_base[i] + ((long)hi * p.W + wi) * p.Cin + a_ci);
-      }
-      xa[i] = v;
-    }
-    if (!IS1X1) {   // advance this thread's (ci, kw, kh) by BK for the next k-step
-      a_ci += BK;
-      while (a_ci >= p.Cin) {
-        a_ci -= p.Cin;
-        if (++a_kw == p.KW) { a_kw = 0; ++a_kh; }
-      }
-    }
-#pragma unroll
-    for (int i = 0; i < NB; ++i) {
-      e16x8 v = zero8;
-      const int n = n0 + (tid >> 3) + i * 32;
-      const int kidx = k0 + b_chunk * 8;
-      if (n < p.Cout && kidx < p.K) v = *reinterpret_cast<const e16x8*>(p.w + (long)n * p.K + kidx);
-      xb[i] = v;
-    }
-  };
-  auto store_tile = [&](const e16x8 (&xa)[NA], const e16x8 (&xb)[NB], int buf) {
-#pragma unroll
-    for (int i = 0; i < NA; ++i) *reinterpret_cast<e16x8*>(&As[buf * BM * BK + swz((tid >> 3) + i * 32, a_chunk)]) = xa[i];
-#pragma unroll
-    for (int i = 0; i < NB; ++i) *reinterpret_cast<e16x8*>(&Bs[buf * BN * BK + swz((tid >> 3) + i * 32, b_chunk)]) = xb[i];
-  };
-
-  f32x4 acc[TM][TN];
-#pragma unroll
-  for (int i = 0; i < TM; ++i)
-#pragma unroll
-    for (int j = 0; j < TN; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-
-  const int fr = lane & 15, fc = lane >> 4;
-  // prologue: PF tiles in flight, tile kt0 staged
-#pragma unroll
-  for (int u = 0; u < PF; ++u)
-    if (kt0 + u < kt1) load_tile(ra[u], rb[u], (kt0 + u) * BK);
-  if (kt0 < kt1) store_tile(ra[0], rb[0], 0);
-  __syncthreads();
-
-  for (int ktb = kt0; ktb < kt1; ktb += PF) {
-#pragma unroll
-    for (int u = 0; u < PF; ++u) {        // static ring index (runtime-indexed register arrays would go to scratch)
-      const int kt = ktb + u;
-      if (kt < kt1) {
-        const int cur = (kt - kt0) & 1;
-        if (kt + PF < kt1) load_tile(ra[u], rb[u], (kt + PF) * BK);     // slot u was drained into LDS one step ago
-#pragma unroll
-        for (int ks = 0; ks < 2; ++ks) {
-          e16x8 af[TM], bfr[TN];
-#pragma unroll
-          for (int i = 0; i < TM; ++i)
-            af[i] = *reinterpret_cast<const e16x8*>(&As[cur * BM * BK + swz(wm * (BM / 2) + i * 16 + fr, 4 * ks + fc)]);
-#pragma unroll
-          for (int j = 0; j < TN; ++j)
-            bfr[j] = *reinterpret_cast<const e16x8*>(&Bs[cur * BN * BK + swz(wn * (BN / 2) + j * 16 + fr, 4 * ks + fc)]);
-#pragma unroll
-          for (int i = 0; i < TM; ++i)
-#pragma unroll
-            for (int j = 0; j < TN; ++j)
-              acc[i][j] = RMEM_MFMA_16x16x32(af[i], bfr[j], acc[i][j], 0, 0, 0);
-        }
-        if (kt + 1 < kt1) store_tile(ra[(u + 1) % PF], rb[(u + 1) % PF], cur ^ 1);
-        __syncthreads();
-      }
-    }
-  }
-
-  // ---- epilogue through LDS: two passes of BM/2 rows ----
-  // C/D map of the 16x16 MFMA: col = lane & 15, row = (lane >> 4) * 4 + reg.
-  float* Cs = reinterpret_cast<float*>(smem);
-  constexpr int VPR = BN / 8;                       // 8-wide vectors per staged row
-#pragma unroll
-  for (int pass = 0; pass < 2; ++pass) {
-    if (wm == pass) {
-#pragma unroll
-      for (int i = 0; i < TM; ++i)
-#pragma unroll
-        for (int j = 0; j < TN; ++j)
-#pragma unroll
-          for (int r = 0; r < 4; ++r) Cs[(i * 16 + fc * 4 + r) * CP + wn * (BN / 2) + j * 16 + fr] = acc[i][j][r];
-    }
-    __syncthreads();
-    for (int vi = tid; vi < (BM / 2) * VPR; vi += 256) {
-      const int row = vi / VPR, cv = vi - row * VPR;
-      const int m = m0 + pass * (BM / 2) + row;
-      const int n = n0 + cv * 8;
-      if (m >= p.M || n >= p.Cout) continue;
-      const float* c = Cs + row * CP + cv * 8;
-      const f32x4 c0 = *reinterpret_cast<const f32x4*>(c), c1 = *reinterpret_cast<const f32x4*>(c + 4);
-      float v[8] = {c0[0], c0[1], c0[2], c0[3], c1[0], c1[1], c1[2], c1[3]};
-      if (SPLITK) {
-        float* s = p.slabs + ((long)blockIdx.z * p.M + m) * p.Cout + n;    // Cout % 8 == 0 is required for split-K
-        *reinterpret_cast<f32x4*>(s) = c0;
-        *reinterpret_cast<f32x4*>(s + 4) = c1;
-      } else if (p.vec_ok && n + 8 <= p.Cout) {
-        finish8(p, m, n, v);
-      } else {
-        for (int j = 0; j < 8 && n + j < p.Cout; ++j) finish1(p, m, n + j, v[j]);
-      }
-    }
-    __syncthreads();
-  }
-}
-
 // ---------------------------------------------------------------------------------------------------------------
-// LDS-DMA variant of the 64x64 tile (the one every shape of this path uses).  Global -> LDS goes through
-// global_load_lds_dwordx4 (no VGPR staging, no ds_write: the ~79 B/clk ds_write path was the per-k-step bottleneck of the
-// register-staged kernel).  Each wave-instruction fills 8 rows x 128 B of the tile linearly, so the XOR swizzle is
-// applied to the per-lane SOURCE address; padded / out-of-range pieces read a 16-byte zero buffer.  ST-deep LDS ring with
-// counted vmcnt + raw s_barrier; the default is ST = 1 (a single 16 KB buffer, 8 workgroups per CU: see launch()).
+// The kernels.  Global -> LDS goes through global_load_lds_dwordx4 (no VGPR staging, no ds_write: the ~79 B/clk ds_write path
+// was the per-k-step bottleneck of the register-staged kernels that preceded these).  Each wave-instruction fills 8 rows x
+// 128 B of the tile linearly, so the XOR swizzle is applied to the per-lane SOURCE address; padded / out-of-range pieces read
+// a 16-byte zero buffer.  ST-deep LDS ring with counted vmcnt + raw s_barrier; ST = 1 is a single 16 KB buffer at 64x64,
+// 8 workgroups per CU (see gemm_plan()).
 static __device__ uint4 g_zero16[1];
 
 typedef __attribute__((address_space(1))) const void* gptr_t;
@@ -752,170 +589,199 @@ __global__ __launch_bounds__(256) void k_splitk_epilogue(ConvParams p, int split
     for (int j = 0; j < 8; ++j) finish1(p, m, n + j, v[j]);
 }
 
-template <int BM, int BN, int PF>
-void launch(const ConvParams& p, bool is1x1, int splits, hipStream_t s) {
-  dim3 grid((p.M + BM - 1) / BM, (p.Cout + BN - 1) / BN, splits);
-  static const bool use_dma = !(getenv("RMEM_GEMM_DMA") && atoi(getenv("RMEM_GEMM_DMA")) == 0);   // kernel experiments only
-  if (BM == 64 && BN == 64 && use_dma) {
-    if (splits > 1) {
-      if (is1x1) hipLaunchKernelGGL((k_conv_gemm_dma<true, true>), grid, dim3(256), 0, s, p);
-      else hipLaunchKernelGGL((k_conv_gemm_dma<false, true>), grid, dim3(256), 0, s, p);
-      const long total = (long)p.M * (p.Cout / 8);
-      hipLaunchKernelGGL(k_splitk_epilogue, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, p, splits);
-    } else {
-      ConvParams q = p;
-      static const bool xcd_on = !(getenv("RMEM_GEMM_XCD") && atoi(getenv("RMEM_GEMM_XCD")) == 0);   // kernel experiments only
-      if (xcd_on && grid.y > 1 && grid.x >= 16) {        // XCD-aware order: the column tiles of a row tile share one L2
-        q.xcd_ny = (int)grid.y;
-        grid = dim3(8 * ((grid.x + 7) / 8) * grid.y, 1, 1);
-      }
-      const ConvParams& p = q;
-      // ring depth: measured with 4 clips per launch, 1 / 2 / 3 / 4 stages give 2146 / 2044 / 1978 / 1735 frames/s -- a
-      // 16 KB single buffer lets 8 workgroups share a CU, and their DMA in flight beats any prefetch depth inside one
-      static const int st = getenv("RMEM_GEMM_ST") ? atoi(getenv("RMEM_GEMM_ST")) : 1;     // kernel experiments only
-      if (st == 2) {
-        if (is1x1) hipLaunchKernelGGL((k_conv_gemm_dma<true, false, 2>), grid, dim3(256), 0, s, p);
-        else hipLaunchKernelGGL((k_conv_gemm_dma<false, false, 2>), grid, dim3(256), 0, s, p);
-      } else if (st == 3) {
-        if (is1x1) hipLaunchKernelGGL((k_conv_gemm_dma<true, false, 3>), grid, dim3(256), 0, s, p);
-        else hipLaunchKernelGGL((k_conv_gemm_dma<false, false, 3>), grid, dim3(256), 0, s, p);
-      } else if (p.fast_ok) {
-        // few-workgroup problems (token GEMMs of the LSTT, id bank): too few resident workgroups to hide the DMA latency behind
-        // each other, so a 3-deep ring keeps two k-steps in flight inside the workgroup
-        static const int deep_wgs = getenv("RMEM_GEMM_DEEP_WGS") ? atoi(getenv("RMEM_GEMM_DEEP_WGS")) : 1024;
-        const bool deep = (long)((p.M + 63) / 64) * ((p.Cout + 63) / 64) <= deep_wgs && p.steps_per_split >= 3;
-        if (p.fast_ok == 2) {
-          if (deep) hipLaunchKernelGGL((k_conv_gemm_dma<false, false, 3, 2>), grid, dim3(256), 0, s, p);
-          else hipLaunchKernelGGL((k_conv_gemm_dma<false, false, 1, 2>), grid, dim3(256), 0, s, p);
-        } else if (is1x1) {
-          if (deep) hipLaunchKernelGGL((k_conv_gemm_dma<true, false, 3, 1>), grid, dim3(256), 0, s, p);
-          else hipLaunchKernelGGL((k_conv_gemm_dma<true, false, 1, 1>), grid, dim3(256), 0, s, p);
-        } else {
-          if (deep) hipLaunchKernelGGL((k_conv_gemm_dma<false, false, 3, 1>), grid, dim3(256), 0, s, p);
-          else hipLaunchKernelGGL((k_conv_gemm_dma<false, false, 1, 1>), grid, dim3(256), 0, s, p);
-        }
-      } else {
-        if (is1x1) hipLaunchKernelGGL((k_conv_gemm_dma<true, false>), grid, dim3(256), 0, s, p);
-        else hipLaunchKernelGGL((k_conv_gemm_dma<false, false>), grid, dim3(256), 0, s, p);
-      }
-    }
-    return;
-  }
-  if (splits > 1) {
-    if (is1x1) hipLaunchKernelGGL((k_conv_gemm<BM, BN, PF, true, true>), grid, dim3(256), 0, s, p);
-    else hipLaunchKernelGGL((k_conv_gemm<BM, BN, PF, false, true>), grid, dim3(256), 0, s, p);
-    const long total = (long)p.M * (p.Cout / 8);
-    hipLaunchKernelGGL(k_splitk_epilogue, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, p, splits);
-  } else {
-    if (is1x1) hipLaunchKernelGGL((k_conv_gemm<BM, BN, PF, true, false>), grid, dim3(256), 0, s, p);
-    else hipLaunchKernelGGL((k_conv_gemm<BM, BN, PF, false, false>), grid, dim3(256), 0, s, p);
-  }
+// ---------------------------------------------------------------------------------------------------------------
+// Host side: knobs -> plan -> launch.
+
+typedef rmem_gemm_plan GemmPlan;   // family, tile, ring, is1x1, fast, splits, steps_per_split, xcd_ny, grid, threads (include/rmem.h)
+
+// Thresholds of the plan, all measured on MI355X.
+// Split-K (64x64 tiles only): K = 1024 (16 steps) is faster unsplit, K >= 2304 split; aim at >= ~450 workgroups, keep >= 4 k-steps
+// (of 64) per slice, at most 16 slices.
+constexpr int kSplitMaxTiles = 192, kSplitMinSteps = 24, kSplitTargetWgs = 448, kSplitMinStepsPerSlice = 4, kSplitMaxSlices = 16;
+// 128x128 tiles halve the global -> LDS bytes per flop; they pay only where the k-loop dominates (K >= 512) and there are enough
+// tiles to balance 256 CUs.  Per layer with 8 images / 4 clips per launch: 121x213 3x3 128->128 563 -> 662 TFLOP/s, 512->1024
+// stride 2 393 -> 470; shallow-K 1x1 layers (64->256, 128->512) lose 20-40 % and stay on 64x64.  With 16 images / 8 clips per
+// launch, in the whole pipeline where other streams' kernels share the CUs, the K = 256 layers (layer-3 conv3, the decoder's
+// 1x1s) are better off on 64x64 tiles as well: 3276 -> 3315 frames/s, three A/B pairs.  The dual form keeps its own bound, 256.
+constexpr int kBigTile = 128, kBigMinTiles = 128, kBigMinK = 512, kDualBigMinK = 256;
+// One-role 128x128 kernel: at most ~1 workgroup per CU and a deep k-loop -- nothing else hides the DMA latency, so keep two
+// k-steps in flight (ring 3); with more tiles a single buffer.
+constexpr int kBigDeepMaxTiles = 256;
+// Producer / consumer 128x128 form, 16 images / 8 clips per launch, bit-identical outputs: a 2-deep ring (64 KB, two workgroups =
+// 16 waves per CU) takes the K >= 512 layers from 70.3 / 46.4 / 58.0 / 66.1 / 50.7 / 27.5 / 49.9 us to 57.7 / 38.7 / 49.6 / 60.6 /
+// 42.9 / 21.1 / 44.2 us alone and the whole pipeline from 3371 to 3404 frames/s (three A/B pairs); a 3-deep ring (one workgroup
+// per CU) is as fast alone but loses 3 % in the pipeline, where the other streams' kernels want the LDS.
+constexpr int kPcRing = 2;
+// Row-run problems on 128x128 tiles: their k-loop is all global -> LDS traffic as well.  The id bank (17x17x16 -> 256, 85 k-steps)
+// 105.8 -> 81.2 us with a 3-deep ring; the stem (7x7x8 -> 64) was no faster end to end on 128x64 tiles and stays on 64x64.
+constexpr int kRowrunBigRing = 3;
+// 64x64 ring depth, 4 clips per launch: 1 / 2 / 3 / 4 stages give 2146 / 2044 / 1978 / 1735 frames/s -- a 16 KB single buffer lets
+// 8 workgroups share a CU, and their DMA in flight beats any prefetch depth inside one.  Few-workgroup problems (token GEMMs of
+// the LSTT, id bank) have too few resident workgroups for that: a 3-deep ring keeps two k-steps in flight inside the workgroup.
+constexpr int kDeepMaxWgs = 1024, kDeepMinSteps = 3, kDeepRing = 3;
+// XCD-aware order (tile_of_block): only where a row tile has several column tiles to share an L2 and every XCD gets row tiles.
+constexpr int kXcdMinRowTiles = 16;
+
+// The switches that remain, read once per process.  PC, FAST and XCD choose among kernels that are all built and tested;
+// DEBUG is passed into the kernel body (timing experiments only: results are then wrong by construction).
+struct GemmKnobs {
+  int pc;       // RMEM_GEMM_PC: 128x128 producer / consumer form.  0 = one-role kernel, 1 = ring by shape, 2 (default) / 3 = ring depth;
+                // -1 = set to something else (every call then fails)
+  bool fast;    // RMEM_GEMM_FAST=0: general address form everywhere
+  bool xcd;     // RMEM_GEMM_XCD=0: plain 2-D grids
+  int debug;    // RMEM_GEMM_DEBUG -> ConvParams::debug
+};
+const GemmKnobs& gemm_knobs() {
+  static const GemmKnobs knobs = [] {
+    auto num = [](const char* name, int dflt) { const char* v = getenv(name); return v ? atoi(v) : dflt; };
+    GemmKnobs k;
+    k.pc = kPcRing;
+    if (const char* v = getenv("RMEM_GEMM_PC")) k.pc = (v[0] >= '0' && v[0] <= '3' && v[1] == 0) ? v[0] - '0' : -1;
+    k.fast = num("RMEM_GEMM_FAST", 1) != 0;
+    k.xcd = num("RMEM_GEMM_XCD", 1) != 0;
+    k.debug = num("RMEM_GEMM_DEBUG", 0);
+    return k;
+  }();
+  return knobs;
 }
 
-template <int BM, int BN, int MODE = 1>
-void launch_big(const ConvParams& pin, bool is1x1, int st, hipStream_t s) {
-  dim3 grid((pin.M + BM - 1) / BM, (pin.Cout + BN - 1) / BN, 1);
-  ConvParams p = pin;
-  static const bool xcd_on = !(getenv("RMEM_GEMM_XCD") && atoi(getenv("RMEM_GEMM_XCD")) == 0);   // kernel experiments only
-  if (xcd_on && grid.y > 1 && grid.x >= 16) {
-    p.xcd_ny = (int)grid.y;
-    grid = dim3(8 * ((grid.x + 7) / 8) * grid.y, 1, 1);
-  }
-  if constexpr (BM == 128 && BN == 128 && MODE == 1) {
-    // producer / consumer form (loader waves + MFMA waves), ring depth RMEM_GEMM_PC (0 = off).  Measured, 16 images / 8 clips per
-    // launch, bit-identical outputs: a 2-deep ring (64 KB, two workgroups = 16 waves per CU) takes the K >= 512 layers from
-    // 70.3 / 46.4 / 58.0 / 66.1 / 50.7 / 27.5 / 49.9 us to 57.7 / 38.7 / 49.6 / 60.6 / 42.9 / 21.1 / 44.2 us alone and the whole
-    // pipeline from 3371 to 3404 frames/s (three A/B pairs); 3- and 4-deep rings (one workgroup per CU) are as fast alone but
-    // lose 3 % in the pipeline, where the other streams' kernels want the LDS
-    static const int pc_env = getenv("RMEM_GEMM_PC") ? atoi(getenv("RMEM_GEMM_PC")) : 2;
-    const int pc = pc_env == 1 ? (st >= 3 ? 3 : 2) : pc_env;     // 1 = by shape: the few-tile deep-K problems keep the 3-deep ring
-    if (pc >= 2) {
-      if (pc >= 4) {
-        if (is1x1) hipLaunchKernelGGL((k_conv_gemm_dma_pc<true, 4, 1>), grid, dim3(512), 0, s, p);
-        else hipLaunchKernelGGL((k_conv_gemm_dma_pc<false, 4, 1>), grid, dim3(512), 0, s, p);
-      } else if (pc == 3) {
-        if (is1x1) hipLaunchKernelGGL((k_conv_gemm_dma_pc<true, 3, 1>), grid, dim3(512), 0, s, p);
-        else hipLaunchKernelGGL((k_conv_gemm_dma_pc<false, 3, 1>), grid, dim3(512), 0, s, p);
-      } else {
-        if (is1x1) hipLaunchKernelGGL((k_conv_gemm_dma_pc<true, 2, 1>), grid, dim3(512), 0, s, p);
-        else hipLaunchKernelGGL((k_conv_gemm_dma_pc<false, 2, 1>), grid, dim3(512), 0, s, p);
-      }
-      return;
-    }
-  }
-  if constexpr (BM == 128 && BN == 128) {
-    if (st == 5) {        // 160 KB of LDS: one workgroup per CU with four k-steps (128 KB) in flight
-      if (is1x1) hipLaunchKernelGGL((k_conv_gemm_dma_big<true, 5, BM, BN, MODE>), grid, dim3(256), 0, s, p);
-      else hipLaunchKernelGGL((k_conv_gemm_dma_big<false, 5, BM, BN, MODE>), grid, dim3(256), 0, s, p);
-      return;
-    }
-    if (st == 4) {
-      if (is1x1) hipLaunchKernelGGL((k_conv_gemm_dma_big<true, 4, BM, BN, MODE>), grid, dim3(256), 0, s, p);
-      else hipLaunchKernelGGL((k_conv_gemm_dma_big<false, 4, BM, BN, MODE>), grid, dim3(256), 0, s, p);
-      return;
-    }
-  }
-  if (st == 3) {
-    if (is1x1) hipLaunchKernelGGL((k_conv_gemm_dma_big<true, 3, BM, BN, MODE>), grid, dim3(256), 0, s, p);
-    else hipLaunchKernelGGL((k_conv_gemm_dma_big<false, 3, BM, BN, MODE>), grid, dim3(256), 0, s, p);
-  } else if (st == 2) {
-    if (is1x1) hipLaunchKernelGGL((k_conv_gemm_dma_big<true, 2, BM, BN, MODE>), grid, dim3(256), 0, s, p);
-    else hipLaunchKernelGGL((k_conv_gemm_dma_big<false, 2, BM, BN, MODE>), grid, dim3(256), 0, s, p);
-  } else {
-    if (is1x1) hipLaunchKernelGGL((k_conv_gemm_dma_big<true, 1, BM, BN, MODE>), grid, dim3(256), 0, s, p);
-    else hipLaunchKernelGGL((k_conv_gemm_dma_big<false, 1, BM, BN, MODE>), grid, dim3(256), 0, s, p);
-  }
-}
-
-// split-K plan shared by rmem_conv_workspace_bytes and the launcher (64x64 tiles only)
+// split-K slices of a 64x64 problem (before the "no empty slice" re-division in gemm_plan)
 int plan_splits(int M, int Cout, int K) {
   if (Cout % 8) return 1;
   const long tiles = (long)((M + 63) / 64) * ((Cout + 63) / 64);
   const int nk = (K + 63) / 64;
-  if (tiles >= 192 || nk < 24) return 1;          // measured: K = 1024 (16 steps) is faster unsplit, K >= 2304 split
-  int s = (int)((448 + tiles - 1) / tiles);      // aim at >= ~450 workgroups
-  s = min(s, nk / 4);                            // keep >= 4 k-steps (of 64) per slice
-  return max(1, min(s, 16));
+  if (tiles >= kSplitMaxTiles || nk < kSplitMinSteps) return 1;
+  int s = (int)((kSplitTargetWgs + tiles - 1) / tiles);
+  s = min(s, nk / kSplitMinStepsPerSlice);
+  return max(1, min(s, kSplitMaxSlices));
 }
 
-// Measured on MI355X over every conv / linear shape of the path (M = 1674 .. 102425 rows, and 4 - 16 images or clips per
-// launch, M up to 412 k): the LDS-DMA 64x64 tile at 4 workgroups per CU is never slower than the register-ring 128x64 /
-// 128x128 kernels (1981 vs 1962 frames/s with 4 clips per launch), so it is used for everything; the larger tiles stay
-// reachable through RMEM_GEMM_TILE for experiments.
-bool use_small_tiles(int M, int Cout) {
-  (void)M; (void)Cout;
-  return true;
+// grid of an unsplit launch over tile x tile output tiles, in XCD-aware order where that applies
+void plan_grid(GemmPlan& pl, const ConvParams& p, int tile, bool xcd_on) {
+  const int gx = (p.M + tile - 1) / tile, gy = (p.Cout + tile - 1) / tile;
+  pl.tile = tile;
+  pl.grid_x = gx; pl.grid_y = gy; pl.grid_z = 1;
+  if (xcd_on && gy > 1 && gx >= kXcdMinRowTiles) {      // the column tiles of a row tile share one L2
+    pl.xcd_ny = gy;
+    pl.grid_x = 8 * ((gx + 7) / 8) * gy; pl.grid_y = 1;
+  }
 }
 
-}  // namespace
-
-#ifndef RMEM_F16
-extern "C" size_t rmem_conv_workspace_bytes(const rmem_conv_desc* d) {
-  if (!d) return 0;
-  const int M = (d->batch > 0 ? d->batch : 1) * d->Ho * d->Wo, K = d->KH * d->KW * d->Cin;
-  if (!use_small_tiles(M, d->Cout)) return 0;
-  const int s = plan_splits(M, d->Cout, K);
-  return s > 1 ? (size_t)s * M * d->Cout * sizeof(float) : 0;
+// The one decision: which kernel, ring, split and grid.  p carries the geometry (conv_geometry: no pointer is read), `entry` is
+// an RMEM_GEMM_ENTRY_* with `extra` = Cin2 of the dual form / n of the grouped one.  No HIP call.
+int gemm_plan(const ConvParams& p, bool is1x1, bool has_workspace, int entry, int extra, const GemmKnobs& kn, GemmPlan& pl) {
+  RMEM_REQUIRE(kn.pc >= 0, "RMEM_GEMM_PC must be 0, 1, 2 or 3");
+  pl = GemmPlan{};
+  const int K = entry == RMEM_GEMM_ENTRY_DUAL ? p.Cin + extra : p.K;
+  const int nk = (K + 63) / 64;
+  const long t64 = (long)((p.M + 63) / 64) * ((p.Cout + 63) / 64);
+  const long t128 = (long)((p.M + 127) / 128) * ((p.Cout + 127) / 128);
+  pl.is1x1 = is1x1; pl.fast = p.fast_ok;
+  pl.ring = 1; pl.splits = 1; pl.steps_per_split = nk; pl.threads = 256;
+  switch (entry) {
+    case RMEM_GEMM_ENTRY_DUAL:
+      RMEM_REQUIRE(is1x1, "rmem_conv1x1_dual_nhwc: the main problem must be a dense 1x1 stride-1 convolution");
+      RMEM_REQUIRE(p.Cin % 64 == 0 && extra > 0 && extra % 64 == 0, "rmem_conv1x1_dual_nhwc: Cin and Cin2 must be multiples of 64");
+      if (p.Cout >= kBigTile && K >= kDualBigMinK && t128 >= kBigMinTiles) { pl.family = RMEM_GEMM_DUAL128; plan_grid(pl, p, 128, kn.xcd); }
+      else { pl.family = RMEM_GEMM_DUAL64; plan_grid(pl, p, 64, kn.xcd); }
+      return 0;
+    case RMEM_GEMM_ENTRY_GROUPED:
+      RMEM_REQUIRE(extra >= 1 && extra <= 4, "rmem_linear_grouped: 1..4 problems");
+      RMEM_REQUIRE(is1x1, "rmem_linear_grouped: 1x1 stride-1 problems only");
+      pl.family = RMEM_GEMM_GROUPED;
+      plan_grid(pl, p, 64, false);
+      pl.grid_z = extra;
+      if (p.fast_ok == 1 && t64 * extra <= kDeepMaxWgs && nk >= kDeepMinSteps) pl.ring = kDeepRing;
+      return 0;
+    case RMEM_GEMM_ENTRY_CONV2D: break;
+    default: RMEM_REQUIRE(false, "rmem_conv_plan: unknown entry kind");
+  }
+  const int splits = has_workspace ? plan_splits(p.M, p.Cout, K) : 1;
+  if (splits > 1) {      // always the general kernel + k_splitk_epilogue, never the XCD order
+    pl.family = RMEM_GEMM_GENERAL64;
+    pl.steps_per_split = (nk + splits - 1) / splits;
+    pl.splits = (nk + pl.steps_per_split - 1) / pl.steps_per_split;   // no empty slice
+    plan_grid(pl, p, 64, false);
+    pl.grid_z = pl.splits;
+  } else if (p.fast_ok == 1 && p.Cout >= kBigTile && K >= kBigMinK && t128 >= kBigMinTiles) {
+    const int one_role_ring = t128 <= kBigDeepMaxTiles ? kDeepRing : 1;
+    pl.family = kn.pc == 0 ? RMEM_GEMM_ONE128 : RMEM_GEMM_PC128;
+    pl.ring = kn.pc == 0 ? one_role_ring : kn.pc == 1 ? (one_role_ring == kDeepRing ? kDeepRing : kPcRing) : kn.pc;
+    pl.threads = kn.pc == 0 ? 256 : 512;
+    plan_grid(pl, p, 128, kn.xcd);
+  } else if (p.fast_ok == 2 && p.Cout >= kBigTile) {
+    pl.family = RMEM_GEMM_ROWRUN128;
+    pl.ring = kRowrunBigRing;
+    plan_grid(pl, p, 128, kn.xcd);
+  } else {
+    pl.family = p.fast_ok == 1 ? RMEM_GEMM_SCALAR64 : p.fast_ok == 2 ? RMEM_GEMM_ROWRUN64 : RMEM_GEMM_GENERAL64;
+    if (p.fast_ok && t64 <= kDeepMaxWgs && nk >= kDeepMinSteps) pl.ring = kDeepRing;
+    plan_grid(pl, p, 64, kn.xcd);
+  }
+  return 0;
 }
-#endif
 
-static int conv_setup(const rmem_conv_desc* d, const void* x, const void* w, const float* bias, const void* residual, void* y,
-                      void* y2, ConvParams& p, bool& is1x1) {
-  RMEM_REQUIRE(d && x && w && y, "rmem_conv2d_nhwc: null argument");
+typedef void (*conv_kernel_t)(ConvParams);
+// the IS1X1 = true / false pair of one instantiation
+conv_kernel_t pick(bool is1x1, conv_kernel_t k1x1, conv_kernel_t kkxk) { return is1x1 ? k1x1 : kkxk; }
+
+// the kernel of a plan; every instantiation this file builds is named here (and in launch() for the grouped form) and nowhere else
+conv_kernel_t plan_kernel(const GemmPlan& pl) {
+  const bool i = pl.is1x1 != 0, deep = pl.ring == kDeepRing;
+  switch (pl.family) {
+    case RMEM_GEMM_GENERAL64:
+      return pl.splits > 1 ? pick(i, k_conv_gemm_dma<true, true, 1, 0>, k_conv_gemm_dma<false, true, 1, 0>)
+                           : pick(i, k_conv_gemm_dma<true, false, 1, 0>, k_conv_gemm_dma<false, false, 1, 0>);
+    case RMEM_GEMM_SCALAR64:
+      return deep ? pick(i, k_conv_gemm_dma<true, false, 3, 1>, k_conv_gemm_dma<false, false, 3, 1>)
+                  : pick(i, k_conv_gemm_dma<true, false, 1, 1>, k_conv_gemm_dma<false, false, 1, 1>);
+    case RMEM_GEMM_ROWRUN64: return deep ? k_conv_gemm_dma<false, false, 3, 2> : k_conv_gemm_dma<false, false, 1, 2>;
+    case RMEM_GEMM_ONE128:
+      return deep ? pick(i, k_conv_gemm_dma_big<true, 3, 128, 128, 1>, k_conv_gemm_dma_big<false, 3, 128, 128, 1>)
+                  : pick(i, k_conv_gemm_dma_big<true, 1, 128, 128, 1>, k_conv_gemm_dma_big<false, 1, 128, 128, 1>);
+    case RMEM_GEMM_PC128:
+      return deep ? pick(i, k_conv_gemm_dma_pc<true, 3, 1>, k_conv_gemm_dma_pc<false, 3, 1>)
+                  : pick(i, k_conv_gemm_dma_pc<true, 2, 1>, k_conv_gemm_dma_pc<false, 2, 1>);
+    case RMEM_GEMM_ROWRUN128: return k_conv_gemm_dma_big<false, 3, 128, 128, 2>;
+    case RMEM_GEMM_DUAL64: return k_conv_gemm_dma<true, false, 1, 3>;
+    case RMEM_GEMM_DUAL128: return k_conv_gemm_dma_big<true, 1, 128, 128, 3>;
+    default: return nullptr;
+  }
+}
+
+int launch(const GemmPlan& pl, const ConvParams& pin, hipStream_t s, const GroupPtrs* g = nullptr) {
+  ConvParams p = pin;
+  p.steps_per_split = pl.steps_per_split;
+  p.xcd_ny = pl.xcd_ny;
+  const dim3 grid(pl.grid_x, pl.grid_y, pl.grid_z), block(pl.threads);
+  if (pl.family == RMEM_GEMM_GROUPED) {
+    RMEM_REQUIRE(g, "gemm launch: the grouped form needs its operand table");
+    if (pl.ring == kDeepRing) hipLaunchKernelGGL((k_gemm_dma_grouped<true, 3>), grid, block, 0, s, p, *g);
+    else if (pl.fast == 1) hipLaunchKernelGGL((k_gemm_dma_grouped<true, 1>), grid, block, 0, s, p, *g);
+    else hipLaunchKernelGGL((k_gemm_dma_grouped<false, 1>), grid, block, 0, s, p, *g);
+    return 0;
+  }
+  const conv_kernel_t kernel = plan_kernel(pl);
+  RMEM_REQUIRE(kernel, "gemm launch: the plan names no kernel");
+  hipLaunchKernelGGL(kernel, grid, block, 0, s, p);
+  if (pl.splits > 1) {
+    const long total = (long)p.M * (p.Cout / 8);
+    hipLaunchKernelGGL(k_splitk_epilogue, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, p, pl.splits);
+  }
+  return 0;
+}
+
+// The geometry half of the setup: every field of ConvParams that does not depend on an operand pointer (pointers stay null).
+int conv_geometry(const rmem_conv_desc* d, ConvParams& p, bool& is1x1) {
+  RMEM_REQUIRE(d, "rmem_conv2d_nhwc: null argument");
   RMEM_REQUIRE(d->Cin > 0 && d->Cin % 8 == 0, "rmem_conv2d_nhwc: Cin must be a positive multiple of 8");
   RMEM_REQUIRE(d->KH > 0 && d->KW > 0 && d->stride > 0 && d->pad >= 0, "rmem_conv2d_nhwc: bad kernel geometry");
   const int Ho = (d->H + 2 * d->pad - d->KH) / d->stride + 1;
   const int Wo = (d->W + 2 * d->pad - d->KW) / d->stride + 1;
   RMEM_REQUIRE(Ho == d->Ho && Wo == d->Wo && Ho > 0 && Wo > 0, "rmem_conv2d_nhwc: Ho/Wo do not match the geometry");
   RMEM_REQUIRE(d->ldo >= d->Cout, "rmem_conv2d_nhwc: ldo < Cout");
-  RMEM_REQUIRE(!residual || d->ldr >= d->Cout, "rmem_conv2d_nhwc: ldr < Cout");
-  RMEM_REQUIRE(!y2 || d->ld2 >= d->Cout, "rmem_conv2d_nhwc: ld2 < Cout");
-  RMEM_REQUIRE(((uintptr_t)x % 16) == 0 && ((uintptr_t)w % 16) == 0, "rmem_conv2d_nhwc: x/w must be 16-byte aligned");
-  p.x = (const e16*)x; p.w = (const e16*)w; p.bias = bias; p.res = residual; p.y = y; p.y2 = (e16*)y2;
-  p.slabs = nullptr;
-  p.xcd_ny = 0;
-  { static const int dbg = getenv("RMEM_GEMM_DEBUG") ? atoi(getenv("RMEM_GEMM_DEBUG")) : 0; p.debug = dbg; }
-  p.x2 = nullptr; p.H2 = p.W2 = p.Cin2 = p.stride2 = 0; p.x2_elems = 0;
+  p = ConvParams{};
+  p.debug = gemm_knobs().debug;
   p.H = d->H; p.W = d->W; p.Cin = d->Cin; p.Ho = Ho; p.Wo = Wo; p.Cout = d->Cout;
   p.KH = d->KH; p.KW = d->KW; p.stride = d->stride; p.pad = d->pad;
   const int nb = d->batch > 0 ? d->batch : 1;
@@ -931,20 +797,49 @@ static int conv_setup(const rmem_conv_desc* d, const void* x, const void* w, con
   p.act_begin = d->act_begin;
   p.up_h = d->res_up_h; p.up_w = d->res_up_w; p.up_align = d->res_up_align;
   RMEM_REQUIRE(p.up_h >= 0 && p.up_w >= 0 && (p.up_h > 0) == (p.up_w > 0), "rmem_conv2d_nhwc: res_up_h / res_up_w must both be set or both be 0");
+  p.steps_per_split = (p.K + 63) / 64;
+  // address form.  1: scalar k-walk + hardware zero fill (Cin % 64 == 0, <= 32 taps); 2: row-run (7x7x8 stem, 17x17x16 id bank, 4x4x8
+  // patch embedding); both need every in-range byte offset below 2^31 (masked lanes may wrap: unused).  0: general form
+  p.x_elems = is1x1 ? (long)(p.M - 1) * p.ldx + p.Cin : (long)nb * p.H * p.W * p.Cin;
+  const long shift = is1x1 ? 0 : ((long)p.pad * p.W + p.pad) * p.Cin;
+  const long lim = (1L << 31) - (1L << 22);
+  const bool small = gemm_knobs().fast && (p.x_elems + shift) * 2 < lim && (long)p.Cout * p.K * 2 < lim;
+  if (small && p.Cin % 64 == 0 && p.KH * p.KW <= 32) p.fast_ok = 1;
+  else if (small && !is1x1 && p.KH <= 32 && (p.KW * p.Cin + 63) / 64 <= 32 && p.KW * p.Cin >= 48) p.fast_ok = 2;
+  return 0;
+}
+
+}  // namespace
+
+#ifndef RMEM_F16
+// (built once: the plan does not depend on the element type)
+extern "C" int rmem_conv_plan(const rmem_conv_desc* d, int has_workspace, int entry, int extra, rmem_gemm_plan* plan) {
+  RMEM_REQUIRE(plan, "rmem_conv_plan: null argument");
+  ConvParams p;
+  bool is1x1 = false;
+  if (conv_geometry(d, p, is1x1)) return -1;
+  return gemm_plan(p, is1x1, has_workspace != 0, entry, extra, gemm_knobs(), *plan);
+}
+
+extern "C" size_t rmem_conv_workspace_bytes(const rmem_conv_desc* d) {
+  rmem_gemm_plan pl;
+  if (rmem_conv_plan(d, 1, RMEM_GEMM_ENTRY_CONV2D, 0, &pl) || pl.splits <= 1) return 0;
+  return (size_t)pl.splits * (d->batch > 0 ? d->batch : 1) * d->Ho * d->Wo * d->Cout * sizeof(float);
+}
+#endif
+
+// geometry + the operand pointers and what depends on them (alignment, vector access)
+static int conv_setup(const rmem_conv_desc* d, const void* x, const void* w, const float* bias, const void* residual, void* y,
+                      void* y2, ConvParams& p, bool& is1x1) {
+  RMEM_REQUIRE(d && x && w && y, "rmem_conv2d_nhwc: null argument");
+  if (conv_geometry(d, p, is1x1)) return -1;
+  RMEM_REQUIRE(!residual || d->ldr >= d->Cout, "rmem_conv2d_nhwc: ldr < Cout");
+  RMEM_REQUIRE(!y2 || d->ld2 >= d->Cout, "rmem_conv2d_nhwc: ld2 < Cout");
+  RMEM_REQUIRE(((uintptr_t)x % 16) == 0 && ((uintptr_t)w % 16) == 0, "rmem_conv2d_nhwc: x/w must be 16-byte aligned");
   RMEM_REQUIRE(p.up_h == 0 || (residual && !d->res_f32 && p.Cout % 8 == 0 && p.ldr % 8 == 0 && ((uintptr_t)residual % 16) == 0 && p.ldo % 8 == 0),
                "rmem_conv2d_nhwc: the resized residual must be e16, 16-byte aligned, with Cout, ldr, ldo multiples of 8");
-  p.steps_per_split = (p.K + 63) / 64;
+  p.x = (const e16*)x; p.w = (const e16*)w; p.bias = bias; p.res = residual; p.y = y; p.y2 = (e16*)y2;
   auto al = [](const void* q, int a) { return q == nullptr || ((uintptr_t)q % a) == 0; };
-  {
-    static const bool fast_on = !(getenv("RMEM_GEMM_FAST") && atoi(getenv("RMEM_GEMM_FAST")) == 0);   // kernel experiments only
-    p.x_elems = is1x1 ? (long)(p.M - 1) * p.ldx + p.Cin : (long)nb * p.H * p.W * p.Cin;
-    const long shift = is1x1 ? 0 : ((long)p.pad * p.W + p.pad) * p.Cin;
-    const long lim = (1L << 31) - (1L << 22);          // every in-range byte offset stays below 2^31 (masked lanes may wrap: unused)
-    const bool small = (p.x_elems + shift) * 2 < lim && (long)p.Cout * p.K * 2 < lim;
-    p.fast_ok = fast_on && small && p.Cin % 64 == 0 && p.KH * p.KW <= 32;
-    if (!p.fast_ok && fast_on && small && !is1x1 && p.KH <= 32 && (p.KW * p.Cin + 63) / 64 <= 32 && p.KW * p.Cin >= 48)
-      p.fast_ok = 2;                                     // row-run form (7x7x8 stem, 17x17x16 id bank, 4x4x8 patch embedding)
-  }
   p.vec_ok = p.Cout % 8 == 0 && p.ldo % 8 == 0 && al(y, 16) && al(bias, 16) &&
              (!residual || (p.ldr % 8 == 0 && al(residual, 16))) && (!y2 || (p.ld2 % 8 == 0 && al(y2, 16)));
   return 0;
@@ -954,61 +849,11 @@ extern "C" int RMEM_API(rmem_conv2d_nhwc)(const rmem_conv_desc* d, const void* x
                                 const void* residual, void* y, void* y2, void* workspace, void* stream) {
   ConvParams p;
   bool is1x1 = false;
+  GemmPlan pl;
   if (conv_setup(d, x, w, bias, residual, y, y2, p, is1x1)) return -1;
-  hipStream_t s = (hipStream_t)stream;
-  const long t128 = (long)((p.M + 127) / 128) * ((p.Cout + 127) / 128);
-  static const int force_tile = getenv("RMEM_GEMM_TILE") ? atoi(getenv("RMEM_GEMM_TILE")) : -1;   // kernel experiments only
-  if (force_tile == 0) { launch<64, 64, 4>(p, is1x1, 1, s); return rmem_check_launch("rmem_conv2d_nhwc"); }
-  if (force_tile == 1) { launch<128, 64, 3>(p, is1x1, 1, s); return rmem_check_launch("rmem_conv2d_nhwc"); }
-  if (force_tile == 2) { launch<128, 128, 2>(p, is1x1, 1, s); return rmem_check_launch("rmem_conv2d_nhwc"); }
-  if (!use_small_tiles(p.M, p.Cout)) {
-    if (p.Cout >= 128 && t128 >= 384) launch<128, 128, 2>(p, is1x1, 1, s);
-    else launch<128, 64, 3>(p, is1x1, 1, s);
-  } else {
-    int splits = workspace ? plan_splits(p.M, p.Cout, p.K) : 1;
-    if (splits > 1) {
-      const int nk = (p.K + 63) / 64;
-      p.steps_per_split = (nk + splits - 1) / splits;
-      splits = (nk + p.steps_per_split - 1) / p.steps_per_split;   // no empty slice
-      p.slabs = (float*)workspace;
-    }
-    // 128x128 tiles halve the global -> LDS bytes per flop; they pay only where the k-loop dominates (K >= 512) and there are
-    // enough tiles to balance 256 CUs.  Measured per layer with 8 images / 4 clips per launch: 121x213 3x3 128->128 563 -> 662
-    // TFLOP/s, 512->1024 stride 2 393 -> 470; shallow-K 1x1 layers (64->256, 128->512) lose 20-40 % and stay on 64x64.
-    static const int big_thr = getenv("RMEM_GEMM_BIG") ? atoi(getenv("RMEM_GEMM_BIG")) : 128;
-    // (round 3, 16 images / 8 clips per launch, measured in the whole pipeline where other streams' kernels share the CUs: K = 256
-    // layers -- layer-3 conv3, the decoder's 1x1s -- are better off on 64x64 tiles: 3276 -> 3315 frames/s, three A/B pairs)
-    static const int big_k = getenv("RMEM_GEMM_BIG_K") ? atoi(getenv("RMEM_GEMM_BIG_K")) : 512;
-    static const int big_st = getenv("RMEM_GEMM_BIG_ST") ? atoi(getenv("RMEM_GEMM_BIG_ST")) : 1;
-    if (splits == 1 && big_thr > 0 && p.fast_ok == 1 && p.Cout >= 128 && p.K >= big_k &&
-        (long)((p.M + 127) / 128) * ((p.Cout + 127) / 128) >= big_thr) {
-      // at most ~1 workgroup per CU and a deep k-loop: nothing else hides the DMA latency, so keep two k-steps in flight
-      static const int big_deep = getenv("RMEM_GEMM_BIG_DEEP") ? atoi(getenv("RMEM_GEMM_BIG_DEEP")) : 256;
-      const long t128 = (long)((p.M + 127) / 128) * ((p.Cout + 127) / 128);
-      static const int deep_st = getenv("RMEM_GEMM_BIG_DEEP_ST") ? atoi(getenv("RMEM_GEMM_BIG_DEEP_ST")) : 3;
-      launch_big<128, 128>(p, is1x1, (t128 <= big_deep && p.K >= 512) ? deep_st : big_st, s);
-      return rmem_check_launch("rmem_conv2d_nhwc");
-    }
-    // row-run problems on the larger tiles: their k-loop is all global -> LDS traffic as well.  Measured (16 images / 8 clips per
-    // launch): the id bank (17x17x16 -> 256, 85 k-steps) 105.8 -> 81.2 us on 128x128 tiles with a 3-deep ring (bit 0, the default);
-    // the stem (7x7x8 -> 64) on 128x64 tiles (bit 1) 213.8 -> 195.2 us alone with a single buffer but no faster end to end: off
-    static const int rr_big = getenv("RMEM_GEMM_ROWRUN_BIG") ? atoi(getenv("RMEM_GEMM_ROWRUN_BIG")) : 1;
-    static const int rr_st = getenv("RMEM_GEMM_ROWRUN_ST") ? atoi(getenv("RMEM_GEMM_ROWRUN_ST")) : 3;
-    if (splits == 1 && p.fast_ok == 2 && (rr_big & 1) && p.Cout >= 128) {
-      launch_big<128, 128, 2>(p, false, rr_st, s);
-      return rmem_check_launch("rmem_conv2d_nhwc");
-    }
-    if (splits == 1 && p.fast_ok == 2 && (rr_big & 2) && p.Cout <= 64) {
-      launch_big<128, 64, 2>(p, false, rr_st > 3 ? 3 : rr_st, s);
-      return rmem_check_launch("rmem_conv2d_nhwc");
-    }
-    static const int big64 = getenv("RMEM_GEMM_BIG64") ? atoi(getenv("RMEM_GEMM_BIG64")) : 0;
-    if (splits == 1 && big64 > 0 && p.fast_ok == 1 && p.Cout <= 64 && p.K >= big_k && (p.M + 127) / 128 >= big64) {
-      launch_big<128, 64>(p, is1x1, big_st, s);
-      return rmem_check_launch("rmem_conv2d_nhwc");
-    }
-    launch<64, 64, 4>(p, is1x1, splits, s);
-  }
+  if (gemm_plan(p, is1x1, workspace != nullptr, RMEM_GEMM_ENTRY_CONV2D, 0, gemm_knobs(), pl)) return -1;
+  if (pl.splits > 1) p.slabs = (float*)workspace;
+  if (launch(pl, p, (hipStream_t)stream)) return -1;
   return rmem_check_launch("rmem_conv2d_nhwc");
 }
 
@@ -1018,34 +863,20 @@ extern "C" int RMEM_API(rmem_conv1x1_dual_nhwc)(const rmem_conv_desc* d, const v
                                       const void* w_cat, const float* bias, void* y, void* stream) {
   ConvParams p;
   bool is1x1 = false;
+  GemmPlan pl;
   RMEM_REQUIRE(d && x2 && H2 > 0 && W2 > 0 && stride2 >= 1, "rmem_conv1x1_dual_nhwc: bad second source");
   if (conv_setup(d, x, w_cat, bias, nullptr, y, nullptr, p, is1x1)) return -1;
-  RMEM_REQUIRE(is1x1 && d->ldx == 0, "rmem_conv1x1_dual_nhwc: the main problem must be a dense 1x1 stride-1 convolution");
-  RMEM_REQUIRE(p.Cin % 64 == 0 && Cin2 % 64 == 0, "rmem_conv1x1_dual_nhwc: Cin and Cin2 must be multiples of 64");
+  RMEM_REQUIRE(d->ldx == 0, "rmem_conv1x1_dual_nhwc: the main problem must be a dense 1x1 stride-1 convolution");
+  if (gemm_plan(p, is1x1, false, RMEM_GEMM_ENTRY_DUAL, Cin2, gemm_knobs(), pl)) return -1;
   RMEM_REQUIRE((H2 - 1) / stride2 + 1 == p.Ho && (W2 - 1) / stride2 + 1 == p.Wo, "rmem_conv1x1_dual_nhwc: x2 geometry does not match the output");
   RMEM_REQUIRE(((uintptr_t)x2 % 16) == 0, "rmem_conv1x1_dual_nhwc: x2 must be 16-byte aligned");
   const int nb = d->batch > 0 ? d->batch : 1;
   p.x2 = (const e16*)x2; p.H2 = H2; p.W2 = W2; p.Cin2 = Cin2; p.stride2 = stride2;
   p.x2_elems = (long)nb * H2 * W2 * Cin2;
   p.K = p.Cin + Cin2;                                   // Wcat is [Cout][Cin + Cin2]
-  p.steps_per_split = p.K / 64;
   const long lim = (1L << 31) - (1L << 22);
   RMEM_REQUIRE(p.x_elems * 2 < lim && p.x2_elems * 2 < lim && (long)p.Cout * p.K * 2 < lim, "rmem_conv1x1_dual_nhwc: operands must stay below 2 GB");
-  hipStream_t s = (hipStream_t)stream;
-  static const int big_thr = getenv("RMEM_GEMM_BIG") ? atoi(getenv("RMEM_GEMM_BIG")) : 128;
-  static const bool xcd_on = !(getenv("RMEM_GEMM_XCD") && atoi(getenv("RMEM_GEMM_XCD")) == 0);   // kernel experiments only
-  if (big_thr > 0 && p.Cout >= 128 && p.K >= 256 && (long)((p.M + 127) / 128) * ((p.Cout + 127) / 128) >= big_thr) {
-    dim3 grid((p.M + 127) / 128, (p.Cout + 127) / 128, 1);
-    if (xcd_on && grid.y > 1 && grid.x >= 16) { p.xcd_ny = (int)grid.y; grid = dim3(8 * ((grid.x + 7) / 8) * grid.y, 1, 1); }
-    static const int pc = getenv("RMEM_GEMM_PC_DUAL") ? atoi(getenv("RMEM_GEMM_PC_DUAL")) : 0;   // producer / consumer form, as launch_big
-    if (pc >= 3) hipLaunchKernelGGL((k_conv_gemm_dma_pc<true, 3, 3>), grid, dim3(512), 0, s, p);
-    else if (pc == 2) hipLaunchKernelGGL((k_conv_gemm_dma_pc<true, 2, 3>), grid, dim3(512), 0, s, p);
-    else hipLaunchKernelGGL((k_conv_gemm_dma_big<true, 1, 128, 128, 3>), grid, dim3(256), 0, s, p);
-  } else {
-    dim3 grid((p.M + 63) / 64, (p.Cout + 63) / 64, 1);
-    if (xcd_on && grid.y > 1 && grid.x >= 16) { p.xcd_ny = (int)grid.y; grid = dim3(8 * ((grid.x + 7) / 8) * grid.y, 1, 1); }
-    hipLaunchKernelGGL((k_conv_gemm_dma<true, false, 1, 3>), grid, dim3(256), 0, s, p);
-  }
+  if (launch(pl, p, (hipStream_t)stream)) return -1;
   return rmem_check_launch("rmem_conv1x1_dual_nhwc");
 }
 
@@ -1055,19 +886,15 @@ extern "C" int RMEM_API(rmem_linear_grouped)(const rmem_conv_desc* d, int n, con
   ConvParams p;
   bool is1x1 = false;
   GroupPtrs g = {};
+  GemmPlan pl;
   for (int i = 0; i < n; ++i) {
     ConvParams pi;
     if (conv_setup(d, x[i], w[i], bias ? bias[i] : nullptr, residual ? residual[i] : nullptr, y[i], nullptr, pi, is1x1)) return -1;
-    RMEM_REQUIRE(is1x1, "rmem_linear_grouped: 1x1 stride-1 problems only");
     RMEM_REQUIRE(i == 0 || pi.vec_ok == p.vec_ok, "rmem_linear_grouped: operands of all problems must have the same alignment class");
     if (i == 0) p = pi;
     g.x[i] = pi.x; g.w[i] = pi.w; g.bias[i] = pi.bias; g.res[i] = pi.res; g.y[i] = pi.y; g.y2[i] = nullptr;
   }
-  dim3 grid((p.M + 63) / 64, (p.Cout + 63) / 64, n);
-  static const int deep_wgs = getenv("RMEM_GEMM_DEEP_WGS") ? atoi(getenv("RMEM_GEMM_DEEP_WGS")) : 1024;
-  if (p.fast_ok == 1 && (long)grid.x * grid.y * n <= deep_wgs && p.steps_per_split >= 3)
-    hipLaunchKernelGGL((k_gemm_dma_grouped<true, 3>), grid, dim3(256), 0, (hipStream_t)stream, p, g);
-  else if (p.fast_ok == 1) hipLaunchKernelGGL(k_gemm_dma_grouped<true>, grid, dim3(256), 0, (hipStream_t)stream, p, g);
-  else hipLaunchKernelGGL(k_gemm_dma_grouped<false>, grid, dim3(256), 0, (hipStream_t)stream, p, g);
+  if (gemm_plan(p, is1x1, false, RMEM_GEMM_ENTRY_GROUPED, n, gemm_knobs(), pl)) return -1;
+  if (launch(pl, p, (hipStream_t)stream, &g)) return -1;
   return rmem_check_launch("rmem_linear_grouped");
 }

@@ -102,6 +102,17 @@ def conv2d(x, w, bias, y, *, H, W, Cin, Cout, KH=1, KW=1, stride=1, pad=0, resid
     return Op(_fn('rmem_conv2d_nhwc', dt), args, 'rmem_conv2d_nhwc', (d, x, w, bias, residual, y, y2, ws))
 
 
+def conv_plan(*, H, W, Cin, Cout, KH=1, KW=1, stride=1, pad=0, batch=1, ldx=0, has_ws=False, entry='conv2d', extra=0) -> Dict[str, int]:
+    """The launch plan (kernel family, ring depth, split count, grid: include/rmem.h, rmem_gemm_plan) of a conv2d / conv1x1_dual /
+    linear_grouped problem, as a dict.  extra: Cin2 of the dual form, n of the grouped one.  Host only: no tensor, no GPU."""
+    Ho = (H + 2 * pad - KH) // stride + 1
+    Wo = (W + 2 * pad - KW) // stride + 1
+    d = ConvDesc(H, W, Cin, Ho, Wo, Cout, KH, KW, stride, pad, Cout, Cout, Cout, 0, 0, 0, ldx, batch, 0, 0, 0, 0)
+    pl = _lib.GemmPlan()
+    _lib.check(_lib.lib().rmem_conv_plan(C.byref(d), int(has_ws), _lib.GEMM_ENTRIES.index(entry), extra, C.byref(pl)), 'rmem_conv_plan')
+    return {n: getattr(pl, n) for n, _ in pl._fields_}
+
+
 def conv1x1_dual(x, x2, w_cat, bias, y, *, H, W, Cin, Cout, H2, W2, Cin2, stride2, relu=False, batch=1) -> Op:
     """y = act([x | x2 sampled at stride2] @ w_cat^T + bias): bottleneck conv3 + its 1x1 shortcut as one GEMM.
     x [batch*H*W, Cin] bf16, x2 NHWC [batch, H2, W2, Cin2] bf16, w_cat [Cout, Cin + Cin2] bf16."""

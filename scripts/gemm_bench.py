@@ -1,8 +1,9 @@
 #!/usr/bin/env python3
 """Per-layer timing of rmem_conv2d_nhwc over the conv / linear shapes of the cfg-2 path (--images frames per encoder launch, --clips
 clips per LSTT / decoder launch; round 3 bench default: 16 / 8) and of Swin-B stage 3 at 720p.  Each measurement is --reps launches
-back to back inside one event pair, rotating over --sets operand sets so that a layer does not find its own input in the caches.  The tile choice is read from the environment once per process
-(RMEM_GEMM_BIG256 = 256x128 tiles from that many tiles on, RMEM_GEMM_BIG, RMEM_GEMM_TILE ...): run it once per setting.
+back to back inside one event pair, rotating over --sets operand sets so that a layer does not find its own input in the caches.  The
+kernel of a shape is the library's launch plan (ops.conv_plan shows it); the switches that remain (RMEM_GEMM_PC, RMEM_GEMM_FAST,
+RMEM_GEMM_XCD) are read from the environment once per process: run it once per setting.
 Usage: python scripts/gemm_bench.py [--iters 30]"""
 import argparse
 import os

@@ -71,6 +71,12 @@ CONV_CASES = [
                                                              # ragged last row tile, half-empty column tile, residual epilogue
     (45, 52, 16, 64, 5, 3, 2, False, None, False),           # row-run form with 2 k-steps per filter row (KW * Cin = 80), stride 3
     (37, 41, 24, 64, 3, 2, 1, True, None, False),            # Cin = 24: neither fast form (row run of 72 elements is allowed: spr = 2)
+    # the instantiations no case above reaches (tests/test_gemm_plan_host.py::test_gpu_tests_reach_every_kernel keeps this list complete)
+    (19, 23, 8, 40, 3, 1, 1, True, None, False),             # general form k x k (KW * Cin = 24: no row run), ragged row and column tiles
+    (300, 1, 72, 40, 1, 1, 0, False, None, False),           # general form 1x1 (Cin = 72)
+    (200, 1, 1536, 64, 1, 1, 0, False, None, False),         # 24 k-steps on 4 tiles: the split-K form of a 1x1 problem
+    (21, 23, 128, 40, 1, 2, 0, False, None, False),          # scalar k-walk, not a plain GEMM (stride 2), 2 k-steps: single buffer
+    (20, 21, 24, 40, 2, 1, 1, True, None, False),            # row-run form, 2 k-steps (filter rows of 48 elements): single buffer
 ]
 
 
@@ -675,7 +681,10 @@ def test_conv2d_batch_of_images(dev):
     assert_close(y, ref.permute(0, 2, 3, 1).reshape(B, Ho * Wo, Cout), 1e-2, 'batched conv')
 
 
-@pytest.mark.parametrize('B,H2,W2,K1,K2,Cout,stride', [(2, 23, 31, 64, 128, 192, 2), (1, 9, 14, 64, 64, 256, 1), (3, 61, 43, 256, 512, 1024, 2)])
+DUAL_CASES = [(2, 23, 31, 64, 128, 192, 2), (1, 9, 14, 64, 64, 256, 1), (3, 61, 43, 256, 512, 1024, 2)]      # B, H2, W2, K1, K2, Cout, stride
+
+
+@pytest.mark.parametrize('B,H2,W2,K1,K2,Cout,stride', DUAL_CASES)
 def test_conv1x1_dual_bottleneck_tail(dev, B, H2, W2, K1, K2, Cout, stride):
     """relu(conv3(h) + b3 + downsample(x) + bd) of a ResNet bottleneck (encoders/resnet.py:48-68) as one GEMM over [h | x sampled];
     fp32 reference on the bf16-rounded operands.  The 3rd case takes the 128x128 tile, the others the 64x64 one."""
@@ -885,10 +894,13 @@ def test_groupnorm_head_fused(dev, B, M):
     assert_close(y2[:, :N], ref.reshape(B * M, N), 1e-2, 'fused head vs torch')
 
 
+GROUPED_LAUNCH = (1674, 256, 256, 3)      # M, K, N, n of test_grouped_launches
+
+
 def test_grouped_launches(dev):
     """rmem_linear_grouped / rmem_add16_grouped / rmem_layernorm256_pair are bit-identical to the single launches."""
     from rmem_ocu_amd import ops
-    M, K, N, n = 1674, 256, 256, 3
+    M, K, N, n = GROUPED_LAUNCH
     xs = [rb(seeded(20 + i, (M, K))).to(BF16).to(dev) for i in range(n)]
     ws = [rb(seeded(30 + i, (N, K), 1 / 16.0)).to(BF16).to(dev) for i in range(n)]
     bs = [seeded(40 + i, (N,), 0.1).to(dev) for i in range(n)]
@@ -912,6 +924,27 @@ def test_grouped_launches(dev):
     ops.run([ops.layernorm256(a[0], g, be, M=M, b=a[1], y=s0), ops.layernorm256(a[2], g, be, M=M, b=a[3], y=s1)])
     torch.cuda.synchronize()
     assert torch.equal(p0, s0) and torch.equal(p1, s1)
+
+
+GROUPED_CASES = [(300, 128, 40, 2), (300, 72, 40, 3)]      # M, K, N, n
+
+
+@pytest.mark.parametrize('M,K,N,n', GROUPED_CASES)
+def test_grouped_linear_single_buffer_forms(dev, M, K, N, n):
+    """The two instantiations of rmem_linear_grouped that test_grouped_launches does not reach: scalar k-walk with a single buffer
+    (2 k-steps) and the general address form (K = 72) -- bit-identical to the single launches, ragged row and column tiles."""
+    from rmem_ocu_amd import ops
+    xs = [rb(seeded(120 + i, (M, K))).to(BF16).to(dev) for i in range(n)]
+    ws = [rb(seeded(130 + i, (N, K), K ** -0.5)).to(BF16).to(dev) for i in range(n)]
+    bs = [seeded(140 + i, (N,), 0.1).to(dev) for i in range(n)]
+    ys = [torch.zeros(M, N, dtype=BF16, device=dev) for _ in range(n)]
+    y1 = [torch.zeros(M, N, dtype=BF16, device=dev) for _ in range(n)]
+    ops.run(ops.linear_grouped(xs, ws, bs, ys, M=M, K=K, N=N))
+    ops.run([ops.linear(xs[i], ws[i], bs[i], y1[i], M=M, K=K, N=N) for i in range(n)])
+    torch.cuda.synchronize()
+    for i in range(n):
+        assert torch.equal(ys[i], y1[i])
+        assert_close(ys[i], xs[i].float() @ ws[i].float().t() + bs[i], 1e-2, 'grouped linear')
 
 
 @pytest.mark.parametrize('H,W,C,groups,act', [(31, 54, 1024, 32, 2), (11, 13, 1024, 32, 2), (9, 20, 128, 8, 1)])
@@ -1384,9 +1417,9 @@ def test_producer_consumer_forms_are_bit_identical(dev):
         e = dict(os.environ)
         e.pop('RMEM_GEMM_PC', None), e.pop('RMEM_GP_PC', None)
         e.update(env)
-        r = subprocess.run([sys.executable, os.path.join(root, 'scripts', 'pc_check.py')], env=e, capture_output=True, text=True, timeout=300)
+        r = subprocess.run([sys.executable, os.path.join(root, 'scripts', 'pc_check.py'), '--ring3-3x3'], env=e, capture_output=True, text=True, timeout=300)
         assert r.returncode == 0, r.stderr[-2000:]
         outs[name] = [l for l in r.stdout.splitlines() if l and l[0].isalnum()]
-        assert len(outs[name]) == 9, r.stdout
+        assert len(outs[name]) == 10, r.stdout
     assert outs['default'] == outs['one_role']
     assert outs['ring3'] == outs['one_role']
