@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define RMEM_ABI_VERSION 13
+#define RMEM_ABI_VERSION 14
 
 int rmem_abi_version(void);
 const char* rmem_last_error_string(void);
@@ -657,6 +657,60 @@ size_t rmem_png_decode_workspace_bytes(int frames, int H, int W);   /* host only
 int rmem_png_decode_labels(const unsigned char* bits, const RmemPngDesc* descs /* device */, int frames, int H, int W,
                            const unsigned char* lut /* device, 256 bytes, or NULL */, void* workspace,
                            unsigned char* out /* device [frames][H][W] */, int* status /* device [frames] */, void* stream);
+
+/* Baseline-JPEG files written on the device: uint8 RGB frames rgb[frames][H][W][3] (contiguous, device) in, complete .jpg files
+ * packed back to back out, in one call on `stream`, no host sync, no state kept between calls.  File f is
+ * out[offsets[f] : offsets[f+1]) (offsets: device, int64 [frames + 1], starts at 0); out holds frames * rmem_jpeg_encode_bound(H, W)
+ * bytes.  With labels (uint8 [frames][H][W], device) the overlay of rmem_overlay_rgb8 is applied to every pixel as it is read; the
+ * overlaid frames are never written to memory.  The counterpart of rmem_jpeg_decode_batch; replaces a host copy of the frames, a
+ * numpy blend and Pillow's Image.save per frame (the reference's demo / overlay script).
+ * A file is SOI, APP0 (JFIF 1.01), two DQT, SOF0, four DHT, DRI (unless restart_rows is 0), SOS, the entropy-coded segment, EOI.
+ * The segment is libjpeg-turbo's bit for bit (Pillow: Image.save(f, 'JPEG', quality=q, subsampling=2, optimize=False,
+ * restart_marker_rows=restart_rows)):
+ *   Colour (jccolor.c):  Y  = (19595 R + 38470 G + 7471 B + 32768) >> 16
+ *                        Cb = (-11059 R - 21709 G + 32768 B + (128 << 16) + 32767) >> 16
+ *                        Cr = (32768 R - 27439 G - 5329 B + (128 << 16) + 32767) >> 16
+ *   Sampling: 4:2:0 only, Y 2x2, Cb and Cr 1x1.  Per component cw = ceil(W h / 2), ch = ceil(H v / 2), wib = ceil(cw / 8) and
+ *     hib = ceil(ch / 8) real blocks; the MCU grid has ceil(W / 16) x ceil(H / 16) MCUs of Y00 Y01 Y10 Y11 Cb Cr.
+ *   Edges: luma is replicated to the right up to 8 wib columns and downwards up to 8 hib rows.  Chroma at full resolution is
+ *     replicated to the right up to 16 wib columns and downwards by at most one row (to an even height), then averaged (jcsample.c
+ *     h2v2): (a + b + c + d + bias) >> 2 with bias 1, 2, 1, 2, ... by output column; the averaged rows are replicated down to 8 hib.
+ *   FDCT: jfdctint.c (ISLOW) on sample - 128, CONST_BITS 13, PASS1_BITS 2, rows first, then columns.
+ *   Quantisation: d = 8 Q[k], q = (|c| + (d >> 1)) / d, sign restored.  Q: Annex K's luminance and chrominance tables scaled as
+ *     jpeg_quality_scaling does (s = 5000 / quality below 50, else 200 - 2 quality; entry = (base s + 50) / 100 clamped to 1..255).
+ *   Dummy blocks (jccoefct.c): luma blocks of the MCU grid to the right of wib or below hib are not transformed: their ACs are zero
+ *     and their DC is the DC of the block before them in the MCU (which may itself be a dummy).
+ *   Entropy coding: Annex K's four Huffman tables; the DC difference per component, the predictor reset at every restart interval;
+ *     ZRL (0xF0) for every 16 zeros inside a run, EOB (0x00) when a block ends in zeros; an interval is padded to a byte with
+ *     1-bits; every 0xFF data byte is followed by 0x00; RSTm with m = interval index mod 8 between intervals, none after the last.
+ *   Restart interval: restart_rows MCU rows, DRI = restart_rows * ceil(W / 16) <= 65535; 0 = one interval per frame, no DRI segment.
+ * rmem_jpeg_encode_header (host only): the header bytes (header may be NULL: *header_bytes alone is set) and the table blob the
+ * device calls read (RMEM_JPEG_ENC_TABLE_BYTES bytes, copied to the device by the caller): the divisors 8 Q, code and length of
+ * every Huffman symbol, restart_rows and the header itself.  It depends on (H, W, quality, restart_rows) alone.
+ * rmem_jpeg_encode_bound (host only, 0 on bad geometry): the most bytes one file can take.  A block costs at most 22 + 63 * 26 bits
+ * = 208 bytes (DC: an 11-bit code and 11 value bits; each AC: a 16-bit code and 10 value bits), every byte of the segment may be
+ * 0xFF and be followed by 0x00, every interval pads to a byte and is followed by a 2-byte marker, at most one interval per MCU row:
+ *   bound = RMEM_JPEG_ENC_HEADER_MAX + 2 * 208 * 6 * MCUs + 4 * ceil(H / 16) + 2.
+ * workspace: rmem_jpeg_encode_workspace_bytes bytes (0 on bad geometry), 16-byte aligned: int16 coefficients in scan and zig-zag
+ * order, bit counts, and the unstuffed bits of every interval at its worst-case distance (untouched memory beyond what is used).
+ * Limits, refused with a reason before anything is launched: 1 <= H, W <= 65535, H * W <= 2^26, quality 1..100, frames <= 65535. */
+#define RMEM_JPEG_ENC_HEADER_MAX 629
+#define RMEM_JPEG_ENC_TABLE_BYTES 4096
+int rmem_jpeg_encode_header(int H, int W, int quality, int restart_rows, unsigned char* header, int capacity, int* header_bytes,
+                            void* tables /* host, RMEM_JPEG_ENC_TABLE_BYTES bytes, or NULL */);
+size_t rmem_jpeg_encode_bound(int H, int W);
+size_t rmem_jpeg_encode_workspace_bytes(int frames, int H, int W);
+int rmem_jpeg_encode_rgb8(const unsigned char* rgb, const unsigned char* labels /* device, or NULL: no overlay */,
+                          const unsigned char* palette /* device, 768 bytes; may be NULL without labels */, int alpha256, int frames,
+                          int H, int W, const void* tables /* device: the blob of rmem_jpeg_encode_header for this H, W */,
+                          void* workspace, unsigned char* out, long long* offsets, void* stream);
+/* The overlay alone: out_rgb[frames][H][W][3].  For a pixel p with label l = labels[p] and m the largest label among its
+ * 4-neighbours inside the image:  m > l: black (a one-pixel contour just outside every object; between two touching objects on the
+ * side of the smaller id, as painting the objects in ascending id gives);  else l != 0:
+ * out_c = (a rgb_c + (256 - a) palette[3 l + c] + 128) >> 8 with a = alpha256 in 0..256;  else the pixel unchanged.  Integer
+ * arithmetic throughout; in the manner of the reference's demo overlay, which blends in floating point (no bit parity claimed). */
+int rmem_overlay_rgb8(const unsigned char* rgb, const unsigned char* labels, const unsigned char* palette /* device, 768 bytes */,
+                      int alpha256, int frames, int H, int W, unsigned char* out_rgb, void* stream);
 
 /* ------------------------------------------------------------------ stream capture helpers
  * Thin wrappers over hipStreamBeginCapture / hipGraphInstantiate / hipGraphLaunch so the Python host

@@ -11,7 +11,7 @@ import subprocess
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('RMEM_LIB_PATH') or os.path.join(_HERE, 'librmem_hip.so')   # override: kernel experiments only
-ABI_VERSION = 13
+ABI_VERSION = 14
 
 
 class RmemError(RuntimeError):
@@ -70,6 +70,7 @@ class JpegPlan(C.Structure):
 
 
 JPEG_FORCE_FALLBACK = 1
+JPEG_ENC_HEADER_MAX, JPEG_ENC_TABLE_BYTES = 629, 4096                  # include/rmem.h
 
 
 class PngDesc(C.Structure):
@@ -180,6 +181,11 @@ SIGNATURES = {
     'rmem_jpeg_entropy_decode': (_i, [_vp, _vp, _i, _i, C.POINTER(JpegPlan), _vp, _vp, _vp, _vp]),
     'rmem_jpeg_coef_to_rgb': (_i, [_vp, _i, _i, C.POINTER(JpegPlan), _vp, _vp, _vp]),
     'rmem_jpeg_decode_batch': (_i, [_vp, _vp, _i, _i, C.POINTER(JpegPlan), _vp, _vp, _vp, _vp, _vp]),
+    'rmem_jpeg_encode_header': (_i, [_i, _i, _i, _i, _vp, _i, C.POINTER(_i), _vp]),
+    'rmem_jpeg_encode_bound': (C.c_size_t, [_i, _i]),
+    'rmem_jpeg_encode_workspace_bytes': (C.c_size_t, [_i, _i, _i]),
+    'rmem_jpeg_encode_rgb8': (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
+    'rmem_overlay_rgb8': (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp]),
     'rmem_graph_begin': (_i, [_vp]),
     'rmem_graph_end': (_i, [_vp, C.POINTER(_vp)]),
     'rmem_graph_launch': (_i, [_vp, _vp]),

@@ -12,6 +12,9 @@ Mirrors what networks/managers/evaluator.py:330-568 does for one sequence, witho
   * whole stacks of predicted masks are written as palette PNGs from the device: the DEFLATE payload of every frame is encoded
     there and only the few KB of each file cross to the host -- rmem_png_encode_labels, save_masks, png.encode_label_stack
     (save_mask, one host mask through Pillow, stays as it is);
+  * frames with the predicted masks laid over them (palette tint, black contour: the reference's demo overlay) are written as
+    baseline JPEGs from the device, overlay and compression fused in one call -- rmem_jpeg_encode_rgb8, save_overlays,
+    jpeg.encode_rgb_stack, jpeg.overlay;
   * annotation files are decoded on the device too: only the compressed bytes cross to it -- rmem_png_decode_labels,
     labels_from_pngs, png.decode_label_stack;
   * whole clips are scored on the device with J and the boundary accuracy F (the benchmark toolkit's db_eval_iou /
@@ -66,6 +69,22 @@ def save_masks(labels_u8: torch.Tensor, paths: Sequence[str], squeeze_idx: Optio
     files = png.encode_label_stack(labels_u8, squeeze_idx)
     if len(files) != len(paths):
         raise _lib.RmemError(f'save_masks: {len(files)} frames but {len(paths)} paths')
+    for path, data in zip(paths, files):
+        with open(path, 'wb') as f:
+            f.write(data)
+
+
+def save_overlays(rgb_u8: torch.Tensor, labels_u8: torch.Tensor, paths: Sequence[str], quality: int = 90, alpha: float = 0.4):
+    """One baseline .jpg per path of the device frames ([n, H, W, 3] or [H, W, 3] uint8) with the label maps ([n, H, W] or [H, W]
+    uint8) laid over them: every object tinted in its DAVIS palette colour, a black contour round it (jpeg.overlay).  Overlay and
+    compression run on the device (jpeg.encode_rgb_stack); only the files cross to the host."""
+    from . import jpeg
+    if labels_u8 is None:
+        raise _lib.RmemError('save_overlays: labels must be a uint8 device tensor')
+    n = rgb_u8.shape[0] if isinstance(rgb_u8, torch.Tensor) and rgb_u8.dim() == 4 else 1
+    if n != len(paths):
+        raise _lib.RmemError(f'save_overlays: {n} frames but {len(paths)} paths')
+    files = jpeg.encode_rgb_stack(rgb_u8, labels_u8, quality=quality, alpha=alpha)
     for path, data in zip(paths, files):
         with open(path, 'wb') as f:
             f.write(data)

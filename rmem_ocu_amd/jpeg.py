@@ -6,6 +6,13 @@
 
 Supported: 8-bit baseline / extended Huffman, one scan, grayscale or YCbCr 4:4:4 / 4:2:2 / 4:2:0, restart intervals optional,
 any size.  Anything else raises RmemError with the reason (decode(..., host_fallback=True) decodes such files with Pillow).
+
+The other direction (rmem_jpeg_encode_rgb8, rmem_overlay_rgb8): uint8 RGB frames on the device, optionally with uint8 label maps
+that are overlaid first (palette tint + black contour), out as complete baseline .jpg files (4:2:0, standard tables) whose
+entropy-coded segment is libjpeg-turbo's byte for byte; only the compressed bytes cross to the host.
+
+    files = encode_rgb_stack(rgb, labels, quality=90)           # one .jpg file (bytes) per frame
+    evaluator.save_overlays(rgb, labels, paths)                 # the same, written to paths
 """
 from __future__ import annotations
 
@@ -14,6 +21,7 @@ import time
 from dataclasses import dataclass
 from typing import Dict, List, Optional, Sequence, Tuple
 
+import numpy as np
 import torch
 
 from . import _lib, ops
@@ -305,3 +313,169 @@ def _decode_on_host(frames, device) -> torch.Tensor:
     from PIL import Image
     arrs = [np.asarray(Image.open(io.BytesIO(_as_bytes(f))).convert('RGB')) for f in frames]
     return torch.from_numpy(np.stack(arrs)).to(device)
+
+
+# ---------------------------------------------------------------------------------------------------------------- writing
+
+_enc_ws: Dict[Tuple[int, int], torch.Tensor] = {}          # (device index, stream) -> encoder workspace, grow-only
+_enc_tables: Dict[Tuple, torch.Tensor] = {}                # (device index, H, W, quality, restart_rows) -> device table blob
+_enc_palettes: Dict[Tuple, torch.Tensor] = {}              # (device index, palette bytes or None) -> 768 device bytes
+_enc_pinned: Dict[int, List[torch.Tensor]] = {}            # device index -> [offsets, bytes] pinned host buffers, grow-only
+
+
+def _header_and_tables(H: int, W: int, quality: int, restart_rows: int) -> Tuple[bytes, np.ndarray]:
+    for name, v in (('H', H), ('W', W), ('quality', quality), ('restart_rows', restart_rows)):
+        if not isinstance(v, (int, np.integer)) or isinstance(v, bool) or not -2 ** 31 <= v < 2 ** 31:
+            raise RmemError(f'jpeg.encode_header: {name} must be an integer (got {v!r})')
+    header = (C.c_ubyte * _lib.JPEG_ENC_HEADER_MAX)()
+    tables = np.zeros(_lib.JPEG_ENC_TABLE_BYTES, dtype=np.uint8)
+    n = C.c_int(0)
+    _lib.check(_lib.lib().rmem_jpeg_encode_header(int(H), int(W), int(quality), int(restart_rows), header, len(header), C.byref(n),
+                                                  tables.ctypes.data), 'rmem_jpeg_encode_header')
+    return bytes(header[:n.value]), tables
+
+
+def encode_header(H: int, W: int, quality: int = 90, restart_rows: int = 1) -> bytes:
+    """Everything of an encoded file before its entropy-coded segment: SOI, APP0 (JFIF 1.01), two DQT, SOF0 (4:2:0), four DHT,
+    DRI (restart_rows MCU rows per interval; 0: none), SOS.  Host only; depends on nothing but its arguments."""
+    return _header_and_tables(H, W, quality, restart_rows)[0]
+
+
+def _device_tables(dev, H, W, quality, restart_rows) -> torch.Tensor:
+    key = (dev.index, H, W, quality, restart_rows)
+    t = _enc_tables.get(key)
+    if t is None:
+        if len(_enc_tables) > 256:
+            _enc_tables.clear()
+        t = _enc_tables[key] = torch.from_numpy(_header_and_tables(H, W, quality, restart_rows)[1]).to(dev)
+    return t
+
+
+def _device_palette(dev, palette) -> torch.Tensor:
+    key = (dev.index, None if palette is None else bytes(bytearray(int(v) & 255 for v in palette)))
+    t = _enc_palettes.get(key)
+    if t is None:
+        if key[1] is None:
+            from .evaluator import _davis_palette
+            data = bytes(bytearray(_davis_palette()))
+        else:
+            data = key[1]
+        if len(data) != 768:
+            raise RmemError(f'jpeg: the palette must have 256 RGB entries (got {len(data)} values)')
+        if len(_enc_palettes) > 64:
+            _enc_palettes.clear()
+        t = _enc_palettes[key] = torch.frombuffer(bytearray(data), dtype=torch.uint8).to(dev)
+    return t
+
+
+def _alpha256(alpha) -> int:
+    a = int(round(256 * float(alpha)))
+    if not 0 <= a <= 256:
+        raise RmemError(f'jpeg: alpha must be in 0..1 (got {alpha})')
+    return a
+
+
+def _frames_and_labels(rgb_u8, labels_u8, what):
+    """-> (rgb [n, H, W, 3], labels [n, H, W] or None); views only, nothing copied"""
+    if not isinstance(rgb_u8, torch.Tensor) or rgb_u8.dtype != torch.uint8 or not rgb_u8.is_cuda:
+        raise RmemError(f'{what}: rgb must be a uint8 device tensor')
+    if rgb_u8.dim() not in (3, 4) or rgb_u8.shape[-1] != 3 or rgb_u8.numel() == 0:
+        raise RmemError(f'{what}: rgb must be a non-empty [n, H, W, 3] or [H, W, 3] stack (got {tuple(rgb_u8.shape)})')
+    rgb = rgb_u8[None] if rgb_u8.dim() == 3 else rgb_u8
+    if labels_u8 is None:
+        return rgb, None
+    if not isinstance(labels_u8, torch.Tensor) or labels_u8.dtype != torch.uint8 or not labels_u8.is_cuda:
+        raise RmemError(f'{what}: labels must be a uint8 device tensor')
+    if labels_u8.device != rgb.device:
+        raise RmemError(f'{what}: rgb is on {rgb.device} but labels on {labels_u8.device}')
+    labels = labels_u8[None] if labels_u8.dim() == 2 else labels_u8
+    if labels.dim() != 3 or tuple(labels.shape) != tuple(rgb.shape[:3]):
+        raise RmemError(f'{what}: labels must be [n, H, W] matching rgb {tuple(rgb.shape)} (got {tuple(labels_u8.shape)})')
+    return rgb, labels
+
+
+def overlay(rgb_u8: torch.Tensor, labels_u8: torch.Tensor, alpha: float = 0.4, palette: Optional[Sequence[int]] = None) -> torch.Tensor:
+    """uint8 [n, H, W, 3]: the frames with every object tinted in its palette colour (out = (a rgb + (256 - a) colour + 128) >> 8,
+    a = round(256 alpha)) and a black one-pixel contour just outside it (a pixel one of whose 4-neighbours carries a larger label).
+    palette: 768 values, default the DAVIS palette.  Enqueued on the current stream, no host sync."""
+    if labels_u8 is None:
+        raise RmemError('jpeg.overlay: labels must be a uint8 device tensor')
+    rgb, labels = _frames_and_labels(rgb_u8, labels_u8, 'jpeg.overlay')
+    rgb, labels = rgb.contiguous(), labels.contiguous()
+    n, H, W, _ = rgb.shape
+    dev = rgb.device
+    a, pal = _alpha256(alpha), _device_palette(dev, palette)
+    out = torch.empty_like(rgb)
+    _lib.check(_lib.lib().rmem_overlay_rgb8(rgb.data_ptr(), labels.data_ptr(), pal.data_ptr(), a, n, H, W, out.data_ptr(),
+                                            torch.cuda.current_stream(dev).cuda_stream), 'rmem_overlay_rgb8')
+    return out
+
+
+def encode_files(rgb_u8: torch.Tensor, labels_u8: Optional[torch.Tensor] = None, quality: int = 90, restart_rows: int = 1,
+                 alpha: float = 0.4, palette: Optional[Sequence[int]] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """One complete .jpg file per frame of a uint8 device stack [n, H, W, 3] or [H, W, 3] (a non-contiguous view is copied first):
+    returns (out, offsets), device tensors; file f is out[offsets[f]:offsets[f + 1]] (offsets: int64 [n + 1]), out is sized for
+    the worst case n * rmem_jpeg_encode_bound(H, W).  labels_u8 ([n, H, W] or [H, W]): `overlay` is applied to the pixels as the
+    encoder reads them.  Enqueued on the current stream, no host sync (the table blob of a new (H, W, quality, restart_rows) is
+    uploaded once).  The workspace is one buffer per (device, stream) that only grows."""
+    rgb, labels = _frames_and_labels(rgb_u8, labels_u8, 'jpeg.encode_files')
+    rgb = rgb.contiguous()
+    labels = None if labels is None else labels.contiguous()
+    n, H, W, _ = rgb.shape
+    dev = rgb.device
+    tables = _device_tables(dev, H, W, quality, restart_rows)          # refuses bad geometry, quality and restart_rows by name
+    a, pal = _alpha256(alpha), (None if labels is None else _device_palette(dev, palette))
+    L = _lib.lib()
+    bound, nbytes = L.rmem_jpeg_encode_bound(H, W), L.rmem_jpeg_encode_workspace_bytes(n, H, W)
+    if bound == 0 or nbytes == 0:
+        raise RmemError(f'jpeg.encode_files: bad geometry {n} x {H}x{W}')
+    stream = torch.cuda.current_stream(dev)
+    key = (dev.index, stream.cuda_stream)
+    ws = _enc_ws.get(key)
+    if ws is None or ws.numel() < nbytes:
+        with torch.cuda.stream(stream):
+            ws = _enc_ws[key] = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    out = torch.empty(n * bound, dtype=torch.uint8, device=dev)
+    offsets = torch.empty(n + 1, dtype=torch.int64, device=dev)
+    _lib.check(L.rmem_jpeg_encode_rgb8(rgb.data_ptr(), None if labels is None else labels.data_ptr(),
+                                       None if pal is None else pal.data_ptr(), a, n, H, W, tables.data_ptr(), ws.data_ptr(),
+                                       out.data_ptr(), offsets.data_ptr(), stream.cuda_stream), 'rmem_jpeg_encode_rgb8')
+    return out, offsets
+
+
+def _enc_pinned_buffers(dev_index: int, nbytes: int, noffsets: int) -> List[torch.Tensor]:
+    bufs = _enc_pinned.get(dev_index)
+    if bufs is None:
+        bufs = _enc_pinned[dev_index] = [torch.empty(CHUNK + 1, dtype=torch.int64).pin_memory(), torch.empty(0, dtype=torch.uint8)]
+    if bufs[0].numel() < noffsets:
+        bufs[0] = torch.empty(noffsets, dtype=torch.int64).pin_memory()
+    if bufs[1].numel() < nbytes:
+        bufs[1] = torch.empty(nbytes, dtype=torch.uint8).pin_memory()
+    return bufs
+
+
+def encode_rgb_stack(rgb_u8: torch.Tensor, labels_u8: Optional[torch.Tensor] = None, quality: int = 90, restart_rows: int = 1,
+                     alpha: float = 0.4, palette: Optional[Sequence[int]] = None) -> List[bytes]:
+    """Complete .jpg files (bytes), one per frame.  Per chunk of at most CHUNK frames: one encode call, then two device-to-host
+    copies into pinned memory -- the offsets, then the offsets[n] bytes of the files."""
+    rgb, labels = _frames_and_labels(rgb_u8, labels_u8, 'jpeg.encode_rgb_stack')
+    n = rgb.shape[0]
+    dev = rgb.device
+    stream = torch.cuda.current_stream(dev)
+    files: List[bytes] = []
+    for k in range(0, n, CHUNK):
+        m = min(CHUNK, n - k)
+        out, offsets = encode_files(rgb[k:k + m], None if labels is None else labels[k:k + m], quality, restart_rows, alpha, palette)
+        off_h, _ = _enc_pinned_buffers(dev.index, 0, m + 1)
+        off_h[:m + 1].copy_(offsets, non_blocking=True)
+        stream.synchronize()
+        off = off_h[:m + 1].tolist()
+        total = off[m]
+        if off[0] != 0 or total > out.numel() or any(b <= a for a, b in zip(off, off[1:])):
+            raise RmemError(f'jpeg.encode_rgb_stack: bad file offsets from the device ({off[:4]} ... {total})')
+        _, data_h = _enc_pinned_buffers(dev.index, total, m + 1)
+        data_h[:total].copy_(out[:total], non_blocking=True)
+        stream.synchronize()
+        data = data_h[:total].numpy().tobytes()
+        files += [data[off[i]:off[i + 1]] for i in range(m)]
+    return files
