@@ -16,7 +16,7 @@
 //                  OR-ed into the zeroed memory with a vector atomic.  The interval's last block adds the 1-bits of the padding.
 //   k_jenc_count   one workgroup per interval: the 0xFF bytes of its raw bytes -> its size in the file (+ 2 for a marker).
 //   k_jenc_frames  one workgroup per frame: exclusive scan of the interval sizes; the frame's file size.
-//   k_jenc_offsets one workgroup: exclusive scan of the file sizes -> offsets[0..frames].
+//   k_codec_offsets (codec.h) one workgroup: exclusive scan of the file sizes -> offsets[0..frames].
 //   k_jenc_place   one workgroup per interval: its raw bytes to their final place, 0x00 after every 0xFF, then RSTm; the first
 //                  interval's workgroup also copies the header, the last one's writes EOI.
 // The restart interval and the header travel in the device table blob (rmem_jpeg_encode_header); the host sizes every grid
@@ -28,11 +28,11 @@
 #include <string.h>
 #include <algorithm>
 #include "common.h"
+#include "codec.h"
 #include "../../include/rmem.h"
 
 namespace {
 
-constexpr int kMaxPixels = 1 << 26;
 constexpr int kBlockBits = 22 + 63 * 26;          // DC: 11-bit code + 11 bits; AC: 16-bit code + 10 bits
 constexpr int kBlockBytes = (kBlockBits + 7) / 8;  // 208
 // table blob, 32-bit words
@@ -345,24 +345,11 @@ __global__ __launch_bounds__(256) void k_jenc_scan(uint32_t* __restrict__ bbits,
   const int row0 = it * rows_per, rows = min(rows_per, g.mcus_y - row0);
   const long b0 = (long)row0 * g.mcus_x * 6, nb = (long)rows * g.mcus_x * 6;
   uint32_t* fb = bbits + f * g.nblk + b0;
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   unsigned carry = 0;
   for (long i0 = 0; i0 < nb; i0 += 256) {
     const long i = i0 + threadIdx.x;
-    const unsigned v = i < nb ? fb[i] : 0;
-    unsigned incl = v;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-      const unsigned t = __shfl_up(incl, o, 64);
-      if (lane >= o) incl += t;
-    }
-    if (lane == 63) s_wave[wv] = incl;
-    __syncthreads();
-    unsigned before = carry;
-    for (int k = 0; k < wv; ++k) before += s_wave[k];
-    if (i < nb) fb[i] = before + incl - v;
-    carry += s_wave[0] + s_wave[1] + s_wave[2] + s_wave[3];
-    __syncthreads();
+    const unsigned at = block_excl_scan(i < nb ? fb[i] : 0u, s_wave, carry);
+    if (i < nb) fb[i] = at;
   }
   if (threadIdx.x == 0) ibits[f * g.mcus_y + it] = carry;
   // the words the interval's bits (and their padding) touch; the slice holds rows * row_words >= this many
@@ -464,16 +451,6 @@ __global__ __launch_bounds__(256) void k_jenc_emit(const int16_t* __restrict__ c
   }
 }
 
-// workgroup-wide sum of one unsigned per thread (256 threads); every thread gets the total
-__device__ __forceinline__ unsigned group_sum(unsigned v, unsigned* s_wave) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) s_wave[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return s_wave[0] + s_wave[1] + s_wave[2] + s_wave[3];
-}
-
 __global__ __launch_bounds__(256) void k_jenc_count(Geo g, const uint32_t* __restrict__ tab, const uint32_t* __restrict__ ibits,
                                                     const uint32_t* __restrict__ raw, uint32_t* __restrict__ isize) {
   __shared__ unsigned s_wave[4];
@@ -503,50 +480,13 @@ __global__ __launch_bounds__(256) void k_jenc_frames(Geo g, const uint32_t* __re
   intervals_of(g, (int)tab[kTabRestart], rows_per, nint);
   const long f = blockIdx.x;
   uint32_t* fi = isize + f * g.mcus_y;
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   unsigned carry = 0;
   for (int i0 = 0; i0 < nint; i0 += 256) {
     const int i = i0 + threadIdx.x;
-    const unsigned v = i < nint ? fi[i] : 0;
-    unsigned incl = v;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-      const unsigned t = __shfl_up(incl, o, 64);
-      if (lane >= o) incl += t;
-    }
-    if (lane == 63) s_wave[wv] = incl;
-    __syncthreads();
-    unsigned before = carry;
-    for (int k = 0; k < wv; ++k) before += s_wave[k];
-    if (i < nint) fi[i] = before + incl - v;
-    carry += s_wave[0] + s_wave[1] + s_wave[2] + s_wave[3];
-    __syncthreads();
+    const unsigned at = block_excl_scan(i < nint ? fi[i] : 0u, s_wave, carry);
+    if (i < nint) fi[i] = at;
   }
   if (threadIdx.x == 0) fsize[f] = (unsigned long long)tab[kTabHeaderLen] + carry + 2;
-}
-
-__global__ __launch_bounds__(256) void k_jenc_offsets(const unsigned long long* __restrict__ fsize, int frames, long long* __restrict__ offsets) {
-  __shared__ unsigned long long s_wave[4];
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  unsigned long long carry = 0;
-  for (int f0 = 0; f0 < frames; f0 += 256) {
-    const int f = f0 + threadIdx.x;
-    const unsigned long long v = f < frames ? fsize[f] : 0;
-    unsigned long long incl = v;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-      const unsigned long long t = __shfl_up(incl, o, 64);
-      if (lane >= o) incl += t;
-    }
-    if (lane == 63) s_wave[wv] = incl;
-    __syncthreads();
-    unsigned long long before = carry;
-    for (int i = 0; i < wv; ++i) before += s_wave[i];
-    if (f < frames) offsets[f] = (long long)(before + incl - v);
-    carry += s_wave[0] + s_wave[1] + s_wave[2] + s_wave[3];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) offsets[frames] = (long long)carry;
 }
 
 __global__ __launch_bounds__(256) void k_jenc_place(Geo g, const uint32_t* __restrict__ tab, const uint32_t* __restrict__ ibits,
@@ -598,8 +538,6 @@ const char* geometry_error(int H, int W) {
   if ((long)H * W > kMaxPixels) return "frame too large (H * W must not exceed 2^26)";
   return nullptr;
 }
-
-inline size_t align16(size_t v) { return (v + 15) & ~(size_t)15; }
 
 struct Layout {
   size_t coef, bbits, ibits, isize, fsize, raw, total;
@@ -792,7 +730,7 @@ extern "C" int rmem_jpeg_encode_rgb8(const unsigned char* rgb, const unsigned ch
   if (int rc = rmem_check_launch("rmem_jpeg_encode_rgb8 (count)")) return rc;
   hipLaunchKernelGGL(k_jenc_frames, dim3(frames), dim3(256), 0, st, g, tab, isize, fsize);
   if (int rc = rmem_check_launch("rmem_jpeg_encode_rgb8 (frames)")) return rc;
-  hipLaunchKernelGGL(k_jenc_offsets, dim3(1), dim3(256), 0, st, fsize, frames, offsets);
+  hipLaunchKernelGGL(k_codec_offsets, dim3(1), dim3(256), 0, st, fsize, frames, offsets);
   if (int rc = rmem_check_launch("rmem_jpeg_encode_rgb8 (offsets)")) return rc;
   hipLaunchKernelGGL(k_jenc_place, dim3(g.mcus_y, frames), dim3(256), 0, st, g, tab, ibits, isize, raw, offsets, out);
   return rmem_check_launch("rmem_jpeg_encode_rgb8 (place)");

@@ -11,7 +11,7 @@
 //   k_png_rows    one workgroup per frame: exclusive scan of the row bits (in place), the frame's byte size, and its Adler-32
 //                 A = 1 + sum s1_y, B = H (W + 1) + sum (s2_y + (H - 1 - y)(W + 1) s1_y)  (mod 65521) -- the row combine
 //                 A' = A + s1, B' = B + len A + s2 unrolled, so it is a plain sum.
-//   k_png_frames  one workgroup: exclusive scan of the frame sizes -> offsets[0..frames].
+//   k_codec_offsets (codec.h) one workgroup: exclusive scan of the frame sizes -> offsets[0..frames].
 //   k_png_zero    zeroes the words of out[0 : offsets[frames]) -- the bytes this call uses, not the whole bound.
 //   k_png_emit    k_png_count's pass again (the labels are read a second time instead of keeping a per-row scratch of the
 //                 bound's size); every run-ending lane gets its bit position from a wave scan and writes its run's tokens through
@@ -25,13 +25,13 @@
 #include <stdint.h>
 #include <algorithm>
 #include "common.h"
+#include "codec.h"
 #include "../../include/rmem.h"
 
 namespace {
 
 constexpr unsigned kAdler = 65521u;
 constexpr int kHeaderBits = 19;         // 78 01, BFINAL = 1, BTYPE = 01
-constexpr int kMaxPixels = 1 << 26;     // per frame: 9 (W + 1) H stays below 2^32
 
 __device__ __forceinline__ int lit_bits(int v) { return v < 144 ? 8 : 9; }
 
@@ -145,12 +145,7 @@ __device__ __forceinline__ unsigned row_pass(const uint8_t* __restrict__ cur, co
       L = lower ? lane - (63 - __builtin_clzll(lower)) : open_len + lane;
       bits = run_bits(pb, L);
     }
-    unsigned incl = bits;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-      const unsigned t = __shfl_up(incl, o, 64);
-      if (lane >= o) incl += t;
-    }
+    const unsigned incl = wave_incl_scan(bits);
     if (EMIT) {
       if (ends) {
         BitWriter bw(words, bitpos + row_bits + (incl - bits));
@@ -212,25 +207,12 @@ __global__ __launch_bounds__(256) void k_png_rows(uint32_t* __restrict__ bits, c
   uint64_t A = 0, B = 0;                                              // per thread, reduced below: at most H terms below 2^16 * 2^16 each
   for (int y0 = 0; y0 < H; y0 += 256) {
     const int y = y0 + threadIdx.x;
-    const unsigned v = y < H ? fb[y] : 0;
-    unsigned incl = v;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-      const unsigned t = __shfl_up(incl, o, 64);
-      if (lane >= o) incl += t;
-    }
-    if (lane == 63) s_wave[wv] = incl;
-    __syncthreads();
-    unsigned before = carry;
-    for (int i = 0; i < wv; ++i) before += s_wave[i];
-    const unsigned total = s_wave[0] + s_wave[1] + s_wave[2] + s_wave[3];
+    const unsigned at = block_excl_scan(y < H ? fb[y] : 0u, s_wave, carry);
     if (y < H) {
-      fb[y] = before + incl - v;
+      fb[y] = at;
       A += f1[y];
       B += (f2[y] + ((uint64_t)(H - 1 - y) * len % kAdler) * f1[y]) % kAdler;
     }
-    carry += total;
-    __syncthreads();
   }
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) {
@@ -248,30 +230,6 @@ __global__ __launch_bounds__(256) void k_png_rows(uint32_t* __restrict__ bits, c
     adler[f] = (uint32_t)(b << 16 | a);
     sizes[f] = frame_bytes(carry);
   }
-}
-
-__global__ __launch_bounds__(256) void k_png_frames(const unsigned long long* __restrict__ sizes, int frames, long long* __restrict__ offsets) {
-  __shared__ unsigned long long s_wave[4];
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  unsigned long long carry = 0;
-  for (int f0 = 0; f0 < frames; f0 += 256) {
-    const int f = f0 + threadIdx.x;
-    const unsigned long long v = f < frames ? sizes[f] : 0;
-    unsigned long long incl = v;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-      const unsigned long long t = __shfl_up(incl, o, 64);
-      if (lane >= o) incl += t;
-    }
-    if (lane == 63) s_wave[wv] = incl;
-    __syncthreads();
-    unsigned long long before = carry;
-    for (int i = 0; i < wv; ++i) before += s_wave[i];
-    if (f < frames) offsets[f] = (long long)(before + incl - v);
-    carry += s_wave[0] + s_wave[1] + s_wave[2] + s_wave[3];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) offsets[frames] = (long long)carry;
 }
 
 __global__ __launch_bounds__(256) void k_png_zero(uint32_t* __restrict__ words, const long long* __restrict__ offsets, int frames) {
@@ -312,10 +270,6 @@ __global__ __launch_bounds__(256) void k_png_emit(const uint8_t* __restrict__ la
   }
 }
 
-bool geometry_ok(int frames, int H, int W) { return frames >= 1 && H >= 1 && W >= 1 && (long)H * W <= kMaxPixels; }
-
-inline size_t align16(size_t v) { return (v + 15) & ~(size_t)15; }
-
 }  // namespace
 
 extern "C" size_t rmem_png_zlib_bound(int H, int W) {
@@ -350,7 +304,7 @@ extern "C" int rmem_png_encode_labels(const unsigned char* labels, int frames, i
   if (int rc = rmem_check_launch("rmem_png_encode_labels (count)")) return rc;
   hipLaunchKernelGGL(k_png_rows, dim3(frames), dim3(256), 0, st, bits, a1, a2, H, W, adler, sizes);
   if (int rc = rmem_check_launch("rmem_png_encode_labels (rows)")) return rc;
-  hipLaunchKernelGGL(k_png_frames, dim3(1), dim3(256), 0, st, sizes, frames, offsets);
+  hipLaunchKernelGGL(k_codec_offsets, dim3(1), dim3(256), 0, st, sizes, frames, offsets);
   if (int rc = rmem_check_launch("rmem_png_encode_labels (frames)")) return rc;
   const size_t bound_words = (size_t)frames * rmem_png_zlib_bound(H, W) / 4;
   const int zero_blocks = (int)std::min<size_t>(std::max<size_t>((bound_words / 64 + 255) / 256, 1), 2048);   // typical streams are 2-3 % of it

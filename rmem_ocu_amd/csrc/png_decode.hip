@@ -31,11 +31,11 @@
 #include <stdint.h>
 #include <algorithm>
 #include "common.h"
+#include "codec.h"
 #include "../../include/rmem.h"
 
 namespace {
 
-constexpr int kMaxPixels = 1 << 26;     // per frame, as the encoder
 constexpr unsigned kRing = 32768u;      // DEFLATE's largest distance
 constexpr unsigned kAdler = 65521u;
 constexpr int kTabBits = 10;            // primary table of the literal/length and the distance code
@@ -441,9 +441,9 @@ __global__ __launch_bounds__(64) void k_pngd_inflate(const uint8_t* __restrict__
 // One row by one 256-thread block: reconstruct (in place in the workspace unless the filter is None), unpack, table, store.
 // `a` / `c` are thread 0's left and upper-left bytes carried over the 256-byte steps of an Average / Paeth row.
 __device__ __forceinline__ void unfilter_row(uint8_t* __restrict__ src, size_t stride, int y, int ft, uint32_t row_bytes, int depth, int W,
-                                             const uint8_t* s_lut, uint8_t* s_x, uint8_t* s_up, uint8_t* s_r, int* s_wave,
+                                             const uint8_t* s_lut, uint8_t* s_x, uint8_t* s_up, uint8_t* s_r, unsigned* s_wave,
                                              uint8_t* __restrict__ out_row) {
-  const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
+  const int t = threadIdx.x;
   uint8_t* const cur = src + (size_t)y * stride + 1;
   const uint8_t* const above = y > 0 ? cur - stride : nullptr;
   unsigned carry = 0;                                   // Sub: the reconstructed byte left of this step (every thread)
@@ -457,19 +457,8 @@ __device__ __forceinline__ void unfilter_row(uint8_t* __restrict__ src, size_t s
     if (ft == 2) {
       r = (x + up) & 255u;
     } else if (ft == 1) {
-      unsigned v = x;
-#pragma unroll
-      for (int o = 1; o < 64; o <<= 1) {
-        const unsigned u = __shfl_up(v, o, 64);
-        if (lane >= o) v += u;
-      }
-      if (lane == 63) s_wave[wv] = (int)v;
-      __syncthreads();
-      unsigned before = carry;
-      for (int k = 0; k < wv; ++k) before += s_wave[k];
-      r = (v + before) & 255u;
-      carry = (carry + s_wave[0] + s_wave[1] + s_wave[2] + s_wave[3]) & 255u;
-      __syncthreads();
+      r = (block_excl_scan(x, s_wave, carry) + x) & 255u;
+      carry &= 255u;
     } else if (ft >= 3) {
       s_x[t] = (uint8_t)x;
       s_up[t] = (uint8_t)up;
@@ -513,7 +502,7 @@ __device__ __forceinline__ void unfilter_row(uint8_t* __restrict__ src, size_t s
 __global__ __launch_bounds__(256) void k_pngd_unfilter(const RmemPngDesc* __restrict__ descs, int H, int W, size_t frame_ws, uint8_t* __restrict__ ws,
                                                        const uint8_t* __restrict__ lut, uint8_t* __restrict__ out, int* __restrict__ status) {
   __shared__ uint8_t s_lut[256], s_x[256], s_up[256], s_r[256];
-  __shared__ int s_wave[4];
+  __shared__ unsigned s_wave[4];
   const int f = blockIdx.y, slab = blockIdx.x, nslab = gridDim.x, t = threadIdx.x;
   s_lut[t] = lut ? lut[t] : (uint8_t)t;
   const int y0 = (int)((long)H * slab / nslab), y1 = (int)((long)H * (slab + 1) / nslab);
@@ -552,10 +541,6 @@ __global__ __launch_bounds__(256) void k_pngd_unfilter(const RmemPngDesc* __rest
       unfilter_row(src, stride, y, src[(size_t)y * stride], row_bytes, depth, W, s_lut, s_x, s_up, s_r, s_wave, o + (size_t)y * W);
   }
 }
-
-bool geometry_ok(int frames, int H, int W) { return frames >= 1 && H >= 1 && W >= 1 && (long)H * W <= kMaxPixels; }
-
-inline size_t align16(size_t v) { return (v + 15) & ~(size_t)15; }
 
 inline size_t frame_workspace(int H, int W) { return align16((size_t)H * ((size_t)W + 1)); }
 

@@ -30,22 +30,8 @@ import numpy as np
 import torch
 
 from . import _lib, ops
+from ._codec import davis_palette as _davis_palette, uint8_stack, workspace
 from .networks.engines import build_engine
-
-
-def _davis_palette() -> List[int]:
-    """The 256-colour DAVIS palette (bit-reversal colour map; the same table utils/image.py:8-62 hard-codes)."""
-    pal = []
-    for i in range(256):
-        r = g = b = 0
-        c = i
-        for j in range(8):
-            r |= ((c >> 0) & 1) << (7 - j)
-            g |= ((c >> 1) & 1) << (7 - j)
-            b |= ((c >> 2) & 1) << (7 - j)
-            c >>= 3
-        pal += [r, g, b]
-    return pal
 
 
 def save_mask(mask_u8: np.ndarray, path: str, squeeze_idx: Optional[Sequence[int]] = None):
@@ -117,19 +103,12 @@ def region_similarity(pred_u8: torch.Tensor, gt_u8: torch.Tensor, num_ids: int =
     return {i: (1.0 if c[i, 1] == 0 else float(c[i, 0]) / float(c[i, 1])) for i in range(1, num_ids) if c[i, 1] > 0}
 
 
-_score_ws: Dict[Tuple[int, int], torch.Tensor] = {}      # (device index, stream) -> boundary bit planes of clip_counts, grow-only
-
-
 def _label_stacks(pred_u8, gt_u8, what):
-    for t in (pred_u8, gt_u8):
-        if not isinstance(t, torch.Tensor) or t.dtype != torch.uint8 or not t.is_cuda:
-            raise _lib.RmemError(f'{what}: pred and gt must be uint8 device tensors')
-    if pred_u8.shape != gt_u8.shape or pred_u8.dim() not in (2, 3) or pred_u8.numel() == 0 or pred_u8.device != gt_u8.device:
+    pred, gt = uint8_stack(pred_u8, what, 'pred'), uint8_stack(gt_u8, what, 'gt')
+    if pred_u8.shape != gt_u8.shape or pred.device != gt.device:
         raise _lib.RmemError(f'{what}: pred and gt must have one shape, [n, H, W] or [H, W], on one device '
                              f'(got {tuple(pred_u8.shape)} and {tuple(gt_u8.shape)})')
-    if pred_u8.dim() == 2:
-        pred_u8, gt_u8 = pred_u8[None], gt_u8[None]
-    return pred_u8.contiguous(), gt_u8.contiguous()
+    return pred.contiguous(), gt.contiguous()
 
 
 def boundary_radius(H: int, W: int, bound_th: float = 0.008) -> int:
@@ -154,11 +133,7 @@ def clip_counts(pred_u8: torch.Tensor, gt_u8: torch.Tensor, num_ids: int = 11, v
     if nbytes == 0:
         raise _lib.RmemError(f'clip_counts: num_ids must be in 2..32 (got {num_ids})')
     stream = torch.cuda.current_stream(pred.device)
-    key = (pred.device.index, stream.cuda_stream)
-    ws = _score_ws.get(key)
-    if ws is None or ws.numel() < nbytes:
-        with torch.cuda.stream(stream):
-            ws = _score_ws[key] = torch.empty(nbytes, dtype=torch.uint8, device=pred.device)
+    ws = workspace('score', pred.device, stream, nbytes)        # the boundary bit planes
     counts = torch.empty(n, int(num_ids), 6, dtype=torch.int64, device=pred.device)
     _lib.check(L.rmem_clip_score_counts(pred.data_ptr(), gt.data_ptr(), n, H, W, int(num_ids), int(void_label), radius,
                                         ws.data_ptr(), counts.data_ptr(), stream.cuda_stream),

@@ -25,6 +25,7 @@ import numpy as np
 import torch
 
 from . import _lib, ops
+from ._codec import Packed, davis_palette, fetch_files, stream_of, uint8_stack, workspace
 from ._lib import JPEG_FORCE_FALLBACK, JpegDesc, JpegInfo as _CInfo, JpegPlan, RmemError
 
 ST_COUNT, ST_CODE, ST_DESC = 1, 2, 4
@@ -64,47 +65,7 @@ def parse(data) -> JpegInfo:
                     (i.scan_begin, i.scan_end))
 
 
-class _DeviceCopy:
-    """A packed clip on one device: the whole clip buffer's allocation (filled range by range), the descriptor table and a
-    per-frame status word."""
-
-    def __init__(self, packed: 'PackedJpegs', device):
-        self.bits = torch.empty(max(packed.buf.numel(), 1), dtype=torch.uint8, device=device)
-        self.descs = packed.desc_bytes.to(device)                      # once per clip and device
-        self.status = torch.zeros(len(packed), dtype=torch.int32, device=device)
-        torch.cuda.current_stream(device).synchronize()                # the zeroed status before any decode stream reads it
-
-    def used_on(self, stream: torch.cuda.Stream):
-        """these buffers are read / written on ``stream``: freeing the clip must not hand them out before it catches up"""
-        for t in (self.bits, self.descs, self.status):
-            t.record_stream(stream)
-
-
-_WORKSPACES: Dict[Tuple[int, int], torch.Tensor] = {}
 _PTR_TABLES: Dict[Tuple, torch.Tensor] = {}
-_STREAMS: Dict[Tuple[int, int], torch.cuda.Stream] = {}
-
-
-def _torch_stream(device, stream: int) -> torch.cuda.Stream:
-    key = (device.index or 0, stream)
-    st = _STREAMS.get(key)
-    if st is None:
-        st = _STREAMS[key] = torch.cuda.ExternalStream(stream, device=device)
-    return st
-
-
-# Device buffers that only the decode kernels touch are ALLOCATED ON THE STREAM THAT RUNS THOSE KERNELS: when one is dropped
-# (a workspace grown, a pointer table evicted), the caching allocator hands its block back only to later allocations on that
-# same stream, which run after the queued kernels that still read or write it.
-
-def _workspace(device, stream: int, nbytes: int) -> torch.Tensor:
-    """decode calls on one stream run in order, so they share one workspace"""
-    key = (device.index or 0, stream)
-    ws = _WORKSPACES.get(key)
-    if ws is None or ws.numel() < nbytes:
-        with torch.cuda.stream(_torch_stream(device, stream)):
-            ws = _WORKSPACES[key] = torch.empty(nbytes, dtype=torch.uint8, device=device)
-    return ws
 
 
 def _ptr_table(device, stream: int, ptrs: Sequence[int]) -> torch.Tensor:
@@ -114,14 +75,15 @@ def _ptr_table(device, stream: int, ptrs: Sequence[int]) -> torch.Tensor:
     if t is None:
         if len(_PTR_TABLES) > 4096:
             _PTR_TABLES.clear()
-        with torch.cuda.stream(_torch_stream(device, stream)):      # copied in stream order from pinned memory: no host stall
+        with torch.cuda.stream(stream_of(device, stream)):          # copied in stream order from pinned memory: no host stall
             t = torch.tensor(list(ptrs), dtype=torch.int64).pin_memory().to(device, non_blocking=True)
         _PTR_TABLES[key] = t
     return t
 
 
-class PackedJpegs:
+class PackedJpegs(Packed):
     """Frames parsed and packed once (rmem_jpeg_pack) into one pinned buffer plus a descriptor table; sizes may differ."""
+    NOUN, STATUS_NAMES = 'JPEG', {ST_COUNT: 'block count', ST_CODE: 'invalid Huffman code', ST_DESC: 'descriptor outside the plan'}
 
     def __init__(self, frames: Sequence):
         datas = [_as_bytes(f) for f in frames]
@@ -148,10 +110,7 @@ class PackedJpegs:
         self.compressed_bytes = sum(len(d) for d in datas)
         self.sizes = [(int(d.height), int(d.width)) for d in descs]
         self._plans: Dict[int, JpegPlan] = {}
-        self._dev: Dict[int, _DeviceCopy] = {}
-
-    def __len__(self):
-        return len(self.descs)
+        self._dev = {}
 
     def plan(self, batch: int) -> Tuple[JpegPlan, int]:
         """(plan, workspace bytes) for decoding up to ``batch`` of these frames per call"""
@@ -162,13 +121,6 @@ class PackedJpegs:
                 raise RmemError(_lib.lib().rmem_last_error_string().decode())
             self._plans[batch] = (p, int(nb))
         return self._plans[batch]
-
-    def on_device(self, device) -> _DeviceCopy:
-        device = torch.device(device)
-        key = device.index or 0
-        if key not in self._dev:
-            self._dev[key] = _DeviceCopy(self, device)
-        return self._dev[key]
 
     def upload(self, i: int, m: int, stream: int, device):
         """H2D copy of the compressed bytes of frames i .. i+m-1 (one contiguous range) on ``stream``"""
@@ -198,9 +150,9 @@ class PackedJpegs:
         dc = self.on_device(device)
         if upload:
             self.upload(i, m, stream, device)
-        ws = _workspace(device, stream, nbytes)
+        ws = workspace('jpeg.decode', device, stream, nbytes)
         ptrs = _ptr_table(device, stream, [o.data_ptr() for o in outs])
-        dc.used_on(_torch_stream(device, stream))
+        dc.used_on(stream_of(device, stream))
         rc = _lib.lib().rmem_jpeg_decode_batch(dc.bits.data_ptr(), dc.descs.data_ptr(), i, m, C.byref(plan), ws.data_ptr(),
                                                ptrs.data_ptr(), dc.status.data_ptr() + 4 * i,
                                                None if stats is None else stats.data_ptr(), stream)
@@ -234,24 +186,10 @@ class PackedJpegs:
             out.append(ws[a:a + nb * 128].view(torch.int16).view(nb, 64).clone())
         return out
 
-    def status(self, device) -> torch.Tensor:
-        return self.on_device(device).status
-
     def check(self, device, i: int = 0, m: Optional[int] = None, stream: Optional[int] = None):
         """Synchronise ``stream`` (the one the frames were decoded on; default: the current stream) and raise RmemError if a
         frame of i .. i+m-1 did not decode cleanly."""
-        device = torch.device(device)
-        m = len(self) - i if m is None else m
-        if stream is not None:
-            _torch_stream(device, stream).synchronize()
-        st = self.status(device)[i:i + m].cpu()
-        bad = torch.nonzero(st).flatten().tolist()
-        if bad:
-            k = bad[0]
-            why = {ST_COUNT: 'block count', ST_CODE: 'invalid Huffman code', ST_DESC: 'descriptor outside the plan'}
-            reasons = ', '.join(v for b, v in why.items() if int(st[k]) & b)
-            raise RmemError(f'JPEG frame {i + k} failed to decode on the GPU (status {int(st[k])}: {reasons})'
-                            + (f'; {len(bad)} frames bad' if len(bad) > 1 else ''))
+        super().check(device, i, m, stream)
 
 
 class JpegClip(PackedJpegs):
@@ -296,7 +234,7 @@ def decode(frames_or_bytes, device, stream: Optional[int] = None, check: bool = 
     if stream is None:
         stream = torch.cuda.current_stream(device).cuda_stream
     n = len(clip)
-    with torch.cuda.stream(_torch_stream(device, stream)):
+    with torch.cuda.stream(stream_of(device, stream)):
         out = torch.empty(n, h, w, 3, dtype=torch.uint8, device=device)
     for k in range(0, n, CHUNK):
         m = min(CHUNK, n - k)
@@ -317,10 +255,8 @@ def _decode_on_host(frames, device) -> torch.Tensor:
 
 # ---------------------------------------------------------------------------------------------------------------- writing
 
-_enc_ws: Dict[Tuple[int, int], torch.Tensor] = {}          # (device index, stream) -> encoder workspace, grow-only
 _enc_tables: Dict[Tuple, torch.Tensor] = {}                # (device index, H, W, quality, restart_rows) -> device table blob
 _enc_palettes: Dict[Tuple, torch.Tensor] = {}              # (device index, palette bytes or None) -> 768 device bytes
-_enc_pinned: Dict[int, List[torch.Tensor]] = {}            # device index -> [offsets, bytes] pinned host buffers, grow-only
 
 
 def _header_and_tables(H: int, W: int, quality: int, restart_rows: int) -> Tuple[bytes, np.ndarray]:
@@ -355,11 +291,7 @@ def _device_palette(dev, palette) -> torch.Tensor:
     key = (dev.index, None if palette is None else bytes(bytearray(int(v) & 255 for v in palette)))
     t = _enc_palettes.get(key)
     if t is None:
-        if key[1] is None:
-            from .evaluator import _davis_palette
-            data = bytes(bytearray(_davis_palette()))
-        else:
-            data = key[1]
+        data = bytes(bytearray(davis_palette())) if key[1] is None else key[1]
         if len(data) != 768:
             raise RmemError(f'jpeg: the palette must have 256 RGB entries (got {len(data)} values)')
         if len(_enc_palettes) > 64:
@@ -384,12 +316,10 @@ def _frames_and_labels(rgb_u8, labels_u8, what):
     rgb = rgb_u8[None] if rgb_u8.dim() == 3 else rgb_u8
     if labels_u8 is None:
         return rgb, None
-    if not isinstance(labels_u8, torch.Tensor) or labels_u8.dtype != torch.uint8 or not labels_u8.is_cuda:
-        raise RmemError(f'{what}: labels must be a uint8 device tensor')
-    if labels_u8.device != rgb.device:
-        raise RmemError(f'{what}: rgb is on {rgb.device} but labels on {labels_u8.device}')
-    labels = labels_u8[None] if labels_u8.dim() == 2 else labels_u8
-    if labels.dim() != 3 or tuple(labels.shape) != tuple(rgb.shape[:3]):
+    labels = uint8_stack(labels_u8, what)
+    if labels.device != rgb.device:
+        raise RmemError(f'{what}: rgb is on {rgb.device} but labels on {labels.device}')
+    if tuple(labels.shape) != tuple(rgb.shape[:3]):
         raise RmemError(f'{what}: labels must be [n, H, W] matching rgb {tuple(rgb.shape)} (got {tuple(labels_u8.shape)})')
     return rgb, labels
 
@@ -430,28 +360,13 @@ def encode_files(rgb_u8: torch.Tensor, labels_u8: Optional[torch.Tensor] = None,
     if bound == 0 or nbytes == 0:
         raise RmemError(f'jpeg.encode_files: bad geometry {n} x {H}x{W}')
     stream = torch.cuda.current_stream(dev)
-    key = (dev.index, stream.cuda_stream)
-    ws = _enc_ws.get(key)
-    if ws is None or ws.numel() < nbytes:
-        with torch.cuda.stream(stream):
-            ws = _enc_ws[key] = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    ws = workspace('jpeg.encode', dev, stream, nbytes)
     out = torch.empty(n * bound, dtype=torch.uint8, device=dev)
     offsets = torch.empty(n + 1, dtype=torch.int64, device=dev)
     _lib.check(L.rmem_jpeg_encode_rgb8(rgb.data_ptr(), None if labels is None else labels.data_ptr(),
                                        None if pal is None else pal.data_ptr(), a, n, H, W, tables.data_ptr(), ws.data_ptr(),
                                        out.data_ptr(), offsets.data_ptr(), stream.cuda_stream), 'rmem_jpeg_encode_rgb8')
     return out, offsets
-
-
-def _enc_pinned_buffers(dev_index: int, nbytes: int, noffsets: int) -> List[torch.Tensor]:
-    bufs = _enc_pinned.get(dev_index)
-    if bufs is None:
-        bufs = _enc_pinned[dev_index] = [torch.empty(CHUNK + 1, dtype=torch.int64).pin_memory(), torch.empty(0, dtype=torch.uint8)]
-    if bufs[0].numel() < noffsets:
-        bufs[0] = torch.empty(noffsets, dtype=torch.int64).pin_memory()
-    if bufs[1].numel() < nbytes:
-        bufs[1] = torch.empty(nbytes, dtype=torch.uint8).pin_memory()
-    return bufs
 
 
 def encode_rgb_stack(rgb_u8: torch.Tensor, labels_u8: Optional[torch.Tensor] = None, quality: int = 90, restart_rows: int = 1,
@@ -466,16 +381,5 @@ def encode_rgb_stack(rgb_u8: torch.Tensor, labels_u8: Optional[torch.Tensor] = N
     for k in range(0, n, CHUNK):
         m = min(CHUNK, n - k)
         out, offsets = encode_files(rgb[k:k + m], None if labels is None else labels[k:k + m], quality, restart_rows, alpha, palette)
-        off_h, _ = _enc_pinned_buffers(dev.index, 0, m + 1)
-        off_h[:m + 1].copy_(offsets, non_blocking=True)
-        stream.synchronize()
-        off = off_h[:m + 1].tolist()
-        total = off[m]
-        if off[0] != 0 or total > out.numel() or any(b <= a for a, b in zip(off, off[1:])):
-            raise RmemError(f'jpeg.encode_rgb_stack: bad file offsets from the device ({off[:4]} ... {total})')
-        _, data_h = _enc_pinned_buffers(dev.index, total, m + 1)
-        data_h[:total].copy_(out[:total], non_blocking=True)
-        stream.synchronize()
-        data = data_h[:total].numpy().tobytes()
-        files += [data[off[i]:off[i + 1]] for i in range(m)]
+        files += fetch_files(out, offsets, m, stream, 'jpeg.encode_rgb_stack')
     return files

@@ -30,11 +30,10 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._codec import Packed, davis_palette, fetch_files, stream_of, uint8_stack, workspace
 
 CHUNK = 64                                                 # frames per encode call of encode_label_stack
 _SIGNATURE = b'\x89PNG\r\n\x1a\n'
-_ws: Dict[Tuple[int, int], torch.Tensor] = {}              # (device index, stream) -> row bits / Adler partials, grow-only
-_pinned: Dict[int, List[torch.Tensor]] = {}                # device index -> [offsets, bytes] pinned host buffers, grow-only
 
 
 def _chunk(kind: bytes, data: bytes) -> bytes:
@@ -44,10 +43,7 @@ def _chunk(kind: bytes, data: bytes) -> bytes:
 def wrap(zlib_stream: bytes, H: int, W: int, palette: Optional[Sequence[int]] = None) -> bytes:
     """A complete PNG file around one frame's zlib stream: signature, IHDR (8 bit, colour type 3 = indexed), PLTE (256 entries, the
     DAVIS palette unless `palette` gives 768 values), IDAT, IEND.  Pure host code."""
-    if palette is None:
-        from .evaluator import _davis_palette
-        palette = _davis_palette()
-    pal = bytes(bytearray(int(v) & 255 for v in palette))
+    pal = bytes(bytearray(int(v) & 255 for v in (davis_palette() if palette is None else palette)))
     if len(pal) != 768:
         raise _lib.RmemError(f'png.wrap: the palette must have 256 RGB entries (got {len(pal)} values)')
     if H < 1 or W < 1:
@@ -64,20 +60,12 @@ def squeeze_lut(squeeze_idx: Sequence[int]) -> np.ndarray:
     return lut
 
 
-def _stack(labels_u8, what):
-    if not isinstance(labels_u8, torch.Tensor) or labels_u8.dtype != torch.uint8 or not labels_u8.is_cuda:
-        raise _lib.RmemError(f'{what}: labels must be a uint8 device tensor')
-    if labels_u8.dim() not in (2, 3) or labels_u8.numel() == 0:
-        raise _lib.RmemError(f'{what}: labels must be a non-empty [n, H, W] or [H, W] stack (got {tuple(labels_u8.shape)})')
-    return labels_u8[None] if labels_u8.dim() == 2 else labels_u8
-
-
 def encode_zlib(labels_u8: torch.Tensor, lut: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
     """One zlib stream per frame of a uint8 device label stack [n, H, W] or [H, W] (a non-contiguous view is copied first):
     returns (out, offsets), device tensors; stream f is out[offsets[f]:offsets[f + 1]] (offsets: int64 [n + 1]), out is sized for the
     worst case n * rmem_png_zlib_bound(H, W).  lut: 256 uint8 device values applied to every label, or None.  Enqueued on the current
     stream, no host sync.  The workspace is one buffer per (device, stream) that only grows."""
-    labels = _stack(labels_u8, 'png.encode_zlib').contiguous()
+    labels = uint8_stack(labels_u8, 'png.encode_zlib').contiguous()
     n, H, W = labels.shape
     dev = labels.device
     if lut is not None and (not isinstance(lut, torch.Tensor) or lut.dtype != torch.uint8 or lut.device != dev or lut.numel() != 256
@@ -88,11 +76,7 @@ def encode_zlib(labels_u8: torch.Tensor, lut: Optional[torch.Tensor] = None) -> 
     if bound == 0 or nbytes == 0:
         raise _lib.RmemError(f'png.encode_zlib: frame too large (H * W must not exceed 2^26, got {H}x{W})')
     stream = torch.cuda.current_stream(dev)
-    key = (dev.index, stream.cuda_stream)
-    ws = _ws.get(key)
-    if ws is None or ws.numel() < nbytes:
-        with torch.cuda.stream(stream):
-            ws = _ws[key] = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    ws = workspace('png.encode', dev, stream, nbytes)           # row bits / Adler partials
     out = torch.empty(n * bound, dtype=torch.uint8, device=dev)
     offsets = torch.empty(n + 1, dtype=torch.int64, device=dev)
     _lib.check(L.rmem_png_encode_labels(labels.data_ptr(), n, H, W, None if lut is None else lut.data_ptr(), ws.data_ptr(),
@@ -100,23 +84,12 @@ def encode_zlib(labels_u8: torch.Tensor, lut: Optional[torch.Tensor] = None) -> 
     return out, offsets
 
 
-def _pinned_buffers(dev_index: int, nbytes: int, noffsets: int) -> List[torch.Tensor]:
-    bufs = _pinned.get(dev_index)
-    if bufs is None:
-        bufs = _pinned[dev_index] = [torch.empty(CHUNK + 1, dtype=torch.int64).pin_memory(), torch.empty(0, dtype=torch.uint8)]
-    if bufs[0].numel() < noffsets:
-        bufs[0] = torch.empty(noffsets, dtype=torch.int64).pin_memory()
-    if bufs[1].numel() < nbytes:
-        bufs[1] = torch.empty(nbytes, dtype=torch.uint8).pin_memory()
-    return bufs
-
-
 def encode_label_stack(labels_u8: torch.Tensor, squeeze_idx: Optional[Sequence[int]] = None,
                        palette: Optional[Sequence[int]] = None) -> List[bytes]:
     """Complete PNG files (bytes), one per frame of a uint8 device label stack [n, H, W] or [H, W].  Per chunk of at most CHUNK
     frames: one encode call, then exactly two device-to-host copies into pinned memory -- the offsets, then the offsets[n] bytes
     of the streams -- and `wrap` on the host.  squeeze_idx: save_mask's un-squeeze, applied on the device as a table."""
-    labels = _stack(labels_u8, 'png.encode_label_stack')
+    labels = uint8_stack(labels_u8, 'png.encode_label_stack')
     n, H, W = labels.shape
     dev = labels.device
     stream = torch.cuda.current_stream(dev)
@@ -125,18 +98,7 @@ def encode_label_stack(labels_u8: torch.Tensor, squeeze_idx: Optional[Sequence[i
     for k in range(0, n, CHUNK):
         m = min(CHUNK, n - k)
         out, offsets = encode_zlib(labels[k:k + m], lut)
-        off_h, _ = _pinned_buffers(dev.index, 0, m + 1)
-        off_h[:m + 1].copy_(offsets, non_blocking=True)
-        stream.synchronize()
-        off = off_h[:m + 1].tolist()
-        total = off[m]
-        if off[0] != 0 or total > out.numel() or any(b <= a for a, b in zip(off, off[1:])):
-            raise _lib.RmemError(f'png.encode_label_stack: bad stream offsets from the device ({off[:4]} ... {total})')
-        _, data_h = _pinned_buffers(dev.index, total, m + 1)
-        data_h[:total].copy_(out[:total], non_blocking=True)
-        stream.synchronize()
-        data = data_h[:total].numpy().tobytes()
-        files += [wrap(data[off[i]:off[i + 1]], H, W, palette) for i in range(m)]
+        files += [wrap(z, H, W, palette) for z in fetch_files(out, offsets, m, stream, 'png.encode_label_stack')]
     return files
 
 
@@ -147,7 +109,6 @@ STATUS_NAMES = {ST_INPUT: 'the stream ends too early', ST_SIZE: 'wrong number of
                 ST_CODE: 'invalid block or code', ST_HEADER: 'bad zlib header', ST_ADLER: 'Adler-32 mismatch',
                 ST_FILTER: 'filter type above 4', ST_DESC: 'bad descriptor'}
 MAX_PIXELS = 1 << 26
-_dec_ws: Dict[Tuple[int, int], torch.Tensor] = {}          # (device index, stream) -> inflated bytes, grow-only
 
 
 class PngUnsupported(_lib.RmemError):
@@ -234,20 +195,11 @@ def parse(data, check: bool = True) -> PngInfo:
     return info
 
 
-class _DevicePngs:
-    """a pack on one device: the stream bytes (filled range by range), the descriptor table, one status word per frame"""
-
-    def __init__(self, packed: 'PackedPngs', device):
-        self.bits = torch.empty(packed.buf.numel(), dtype=torch.uint8, device=device)
-        self.descs = packed.desc_bytes.to(device)
-        self.status = torch.zeros(len(packed), dtype=torch.int32, device=device)
-        torch.cuda.current_stream(device).synchronize()                # both are complete before any decode stream reads them
-
-
-class PackedPngs:
+class PackedPngs(Packed):
     """Annotation files (paths or bytes) of one size, parsed once: the IDAT payloads of every file concatenated into its zlib
     stream, the streams packed back to back into one pinned buffer -- each 8-byte aligned and followed by at least 8 zero bytes --
     and the descriptor table (RmemPngDesc).  Bit depth and colour type may differ per frame."""
+    NOUN, STATUS_NAMES = 'PNG', STATUS_NAMES
 
     def __init__(self, files: Sequence):
         datas = [_read(f) for f in files]
@@ -277,43 +229,7 @@ class PackedPngs:
         self.ends = self.offsets[1:] + [at]                            # a frame's range includes its padding
         self.palettes = [i.palette for i in self.infos]
         self.compressed_bytes = sum(len(st) for st in streams)
-        self._dev: Dict[int, _DevicePngs] = {}
-
-    def __len__(self):
-        return len(self.descs)
-
-    def on_device(self, device) -> _DevicePngs:
-        device = torch.device(device)
-        key = device.index or 0
-        if key not in self._dev:
-            self._dev[key] = _DevicePngs(self, device)
-        return self._dev[key]
-
-    def status(self, device) -> torch.Tensor:
-        return self.on_device(device).status
-
-    def check(self, device, first: int = 0, count: Optional[int] = None, stream=None):
-        """Synchronise ``stream`` (the one the frames were decoded on; default: the current stream) and raise RmemError naming the
-        first frame of first .. first+count-1 whose status word is not zero, and its bits."""
-        device = torch.device(device)
-        count = len(self) - first if count is None else count
-        _stream_of(device, stream).synchronize()
-        st = self.status(device)[first:first + count].cpu()
-        bad = torch.nonzero(st).flatten().tolist()
-        if bad:
-            k = bad[0]
-            reasons = ', '.join(v for b, v in STATUS_NAMES.items() if int(st[k]) & b)
-            raise _lib.RmemError(f'PNG frame {first + k} failed to decode on the GPU (status {int(st[k])}: {reasons})'
-                                 + (f'; {len(bad)} frames bad' if len(bad) > 1 else ''))
-
-
-def _stream_of(device, stream) -> torch.cuda.Stream:
-    if stream is None:
-        return torch.cuda.current_stream(device)
-    if isinstance(stream, torch.cuda.Stream):
-        return stream
-    from .jpeg import _torch_stream
-    return _torch_stream(device, int(stream))
+        self._dev = {}
 
 
 def _device_lut(lut, dev, what) -> Optional[torch.Tensor]:
@@ -344,18 +260,15 @@ def decode_labels_into(packed: PackedPngs, out: torch.Tensor, first: int = 0, co
         raise _lib.RmemError(f'png.decode_labels_into: out must be a contiguous [{count}, {H}, {W}] tensor (got {tuple(out.shape)})')
     dev = out.device
     lut = _device_lut(lut, dev, 'png.decode_labels_into')
-    ts = _stream_of(dev, stream)
+    ts = stream_of(dev, stream)
     L = _lib.lib()
     nbytes = L.rmem_png_decode_workspace_bytes(count, H, W)
     if nbytes == 0:
         raise _lib.RmemError(f'png.decode_labels_into: frame too large (H * W must not exceed 2^26, got {H}x{W})')
     dc = packed.on_device(dev)
-    key = (dev.index or 0, ts.cuda_stream)
-    ws = _dec_ws.get(key)
-    if ws is None or ws.numel() < nbytes:
-        with torch.cuda.stream(ts):
-            ws = _dec_ws[key] = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-    for t in (dc.bits, dc.descs, dc.status, out) + (() if lut is None else (lut,)):
+    ws = workspace('png.decode', dev, ts, nbytes)               # the inflated bytes
+    dc.used_on(ts)
+    for t in (out,) + (() if lut is None else (lut,)):
         t.record_stream(ts)
     a, b = packed.offsets[first], packed.ends[first + count - 1]
     from . import ops

@@ -89,6 +89,29 @@ def test_65_frames_cross_the_chunk():
         same(files[i], E.file_bytes(frames[i], 80, 1), f'frame {i}')
 
 
+def test_257_frames_cross_the_offsets_scan_step():
+    """the frame-offsets scan carries its total over a 256-frame step: three frames of different file sizes, cycled"""
+    kinds = [E._smooth(np.random.RandomState(s), 16, 16) for s in (1, 2, 3)]
+    want = [E.file_bytes(k, 90, 1) for k in kinds]
+    assert len({len(w) for w in want}) == 3
+    got, off = device_files(np.stack([kinds[i % 3] for i in range(257)]), quality=90, restart_rows=1)
+    assert off == np.concatenate(([0], np.cumsum([len(want[i % 3]) for i in range(257)]))).tolist()
+    for i in range(257):
+        same(got[i], want[i % 3], f'frame {i}')
+
+
+def test_257_intervals_cross_the_interval_scan_step():
+    """257 MCU rows, one restart interval each: the scan of the interval sizes carries over a 256-interval step"""
+    from rmem_ocu_amd import _lib
+    rgb = E._smooth(np.random.RandomState(1), 4112, 16)
+    want = E.file_bytes(rgb, 90, 1)
+    assert len(want) == 42295 and sum(want[i] == 0xFF and 0xD0 <= want[i + 1] <= 0xD7 for i in range(len(want) - 1)) == 256
+    got, off = device_files(rgb, quality=90, restart_rows=1)
+    assert off == [0, len(want)]
+    same(got[0], want, '4112x16')
+    assert len(got[0]) <= _lib.lib().rmem_jpeg_encode_bound(4112, 16)
+
+
 def test_round_trip_through_the_device_decoder():
     from rmem_ocu_amd import jpeg
     for name in ('odd_37x53', 'tall_150x35', 'noise_q100_64x50'):
@@ -188,7 +211,7 @@ def test_bad_inputs_raise_with_a_message():
 
 
 def test_two_streams_at_once():
-    from rmem_ocu_amd import jpeg
+    from rmem_ocu_amd import _codec, jpeg, png
     frames = three_frames()
     rgb_b, lab_b = overlay_inputs(37, 53, seed=41)
     want_a, off_a = device_files(frames)
@@ -204,14 +227,17 @@ def test_two_streams_at_once():
         out_a2, offs_a2 = jpeg.encode_files(ta)
     sa.synchronize()
     sb.synchronize()
-    assert (DEV.index, sa.cuda_stream) in jpeg._enc_ws and (DEV.index, sb.cuda_stream) in jpeg._enc_ws
-    assert jpeg._enc_ws[(DEV.index, sa.cuda_stream)].data_ptr() != jpeg._enc_ws[(DEV.index, sb.cuda_stream)].data_ptr()
+    ws, ka, kb = _codec._workspaces, ('jpeg.encode', DEV.index, sa.cuda_stream), ('jpeg.encode', DEV.index, sb.cuda_stream)
+    assert ka in ws and kb in ws
+    assert ws[ka].data_ptr() != ws[kb].data_ptr()
     for out, offs, want, off in ((out_a, offs_a, want_a, off_a), (out_b, offs_b, want_b, off_b), (out_a2, offs_a2, want_a, off_a)):
         o = offs.cpu().tolist()
         data = out.cpu().numpy().tobytes()
         assert o == off and [data[o[i]:o[i + 1]] for i in range(len(want))] == want
-    before = jpeg._enc_ws[(DEV.index, sa.cuda_stream)]
+    before = ws[ka]
     with torch.cuda.stream(sa):
         jpeg.encode_files(ta[:1])                                           # a smaller call keeps the workspace
+        png.encode_zlib(tl)                                                 # another codec on the same stream: a buffer of its own
     sa.synchronize()
-    assert jpeg._enc_ws[(DEV.index, sa.cuda_stream)] is before
+    assert ws[ka] is before
+    assert ws[('png.encode', DEV.index, sa.cuda_stream)].data_ptr() != ws[ka].data_ptr()

@@ -87,6 +87,20 @@ def test_65_frames_cross_the_chunk():
         assert decodes_to(files[i], labels[i])
 
 
+def test_257_frames_cross_the_offsets_scan_step():
+    """the frame-offsets scan carries its total over a 256-frame step: three maps of different stream sizes, cycled, one call"""
+    from rmem_ocu_amd import png
+    kinds = [np.zeros((4, 70), np.uint8), blobs(4, 70, 3, seed=1), np.random.RandomState(2).randint(0, 256, (4, 70)).astype(np.uint8)]
+    want = [P.zlib_stream(k) for k in kinds]
+    assert len({len(w) for w in want}) == 3
+    got, off = device_streams(np.stack([kinds[i % 3] for i in range(257)]))
+    assert off == np.concatenate(([0], np.cumsum([len(want[i % 3]) for i in range(257)]))).tolist()
+    for i in range(257):
+        assert got[i] == want[i % 3], i
+    for i in range(3):
+        assert decodes_to(png.wrap(got[254 + i], 4, 70), kinds[(254 + i) % 3])
+
+
 def test_non_contiguous_view():
     labels = np.stack([blobs(40, 50, 5, seed=40 + i) for i in range(3)])
     view = torch.from_numpy(labels).to(DEV)[:, ::2]
