@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define RMEM_ABI_VERSION 14
+#define RMEM_ABI_VERSION 15
 
 int rmem_abi_version(void);
 const char* rmem_last_error_string(void);
@@ -564,6 +564,16 @@ int rmem_resize_nearest_flip_f32(const float* src, int planes, int Hs, int Ws, f
  * logits_nchw / flips are HOST arrays of n_aug entries.  Replaces managers/evaluator.py:427-441 (flip / multi-scale TTA). */
 int rmem_tta_merge(const float* const* logits_nchw, const int* flips, int n_aug, int num_classes, int H, int W,
                    unsigned char* label_u8, float* label_f32, float* prob_nchw, void* stream);
+
+/* Flip test-time augmentation inside a clip group, fused: logits fp32 [rows][Hi * Wi][16], rows = 2P, row p a clip and row P + p its
+ * horizontally mirrored twin.  Per output pixel (y, x) of pair p: row p blended at (y, x) and row P + p at (y, Wo - 1 - x) (bilinear,
+ * ids > keep_max_id forced to -1e10, as rmem_logits_post_images), softmax of each over the num_classes channels, mean, argmax (first
+ * maximum) -- what rmem_logits_post + rmem_tta_merge compute for the pair, without the full-size fp32 maps.  label_u8 [rows][Ho][Wo]:
+ * label_u8[p][y][x] = the merged label, label_u8[P + p][y][Wo - 1 - x] = the same value (the twin's row holds the mirror, what its
+ * memory update takes).  Refused (non-zero, nothing launched): odd rows, num_classes > 16, keep_max_id >= num_classes, null
+ * pointers, logits not 16-byte aligned. */
+int rmem_logits_post_flip_pairs(const float* logits_nhwc16, int rows, int num_classes, int keep_max_id, int Hi, int Wi, int Ho, int Wo,
+                                int align_corners, unsigned char* label_u8, void* stream);
 
 /* Region-similarity (Jaccard) counts per object id for one mask pair: counts[2*id] += |pred==id & gt==id|,
  * counts[2*id+1] += |pred==id | gt==id| over the n pixels whose ground truth is not `void_label`; the caller zeroes

@@ -11,7 +11,7 @@ import subprocess
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('RMEM_LIB_PATH') or os.path.join(_HERE, 'librmem_hip.so')   # override: kernel experiments only
-ABI_VERSION = 14
+ABI_VERSION = 15
 
 
 class RmemError(RuntimeError):
@@ -152,6 +152,7 @@ SIGNATURES = {
     'rmem_evict_scores': (_i, [_vp, _i, _i, _i, _i, _i, _i, _i, _vp, _i, _vp, _vp]),
     'rmem_resize_nearest_flip_f32': (_i, [_vp, _i, _i, _i, _vp, _i, _i, _i, _vp]),
     'rmem_tta_merge': (_i, [C.POINTER(_vp), C.POINTER(_i), _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
+    'rmem_logits_post_flip_pairs': (_i, [_vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp]),
     'rmem_mask_iou_counts': (_i, [_vp, _vp, _ll, _i, _i, _vp, _vp]),
     'rmem_clip_score_workspace_bytes': (C.c_size_t, [_i, _i, _i, _i]),
     'rmem_boundary_radius': (_i, [_i, _i, C.c_double]),

@@ -274,11 +274,21 @@ class GroupSlot:
     labels: uint8 [B, n, Ho, Wo] on the device, labels[c, i] = the prediction of frame i of clip c (row 0 stays zero: frame 0 is the
     given annotation).  Once the engine has been synchronised a clip is scored where it lies:
     evaluator.score_clip(slot.labels[c, :n], gt_stack) -> J, F, J&F, decay, tail J; and its masks leave as palette PNGs encoded
-    on the device: png.encode_label_stack(slot.labels[c, 1:n]) -> one PNG file per frame (evaluator.save_masks writes them)."""
+    on the device: png.encode_label_stack(slot.labels[c, 1:n]) -> one PNG file per frame (evaluator.save_masks writes them).
+
+    FLIP TESTING: on a GroupEngine(flip_tta=True) of B = 2P rows the slot takes P clips and delivers labels [P, n, Ho, Wo]; rows
+    P..2P-1 are the clips' horizontally mirrored twins, which the slot makes on the device: the twins' frames are mirrored look-ahead
+    batch by look-ahead batch on the encoder stream (into staging rows per look-ahead buffer for fp32 device frames, whose
+    lifetime the encoder events cover; next to the ingested frames in the encoder's input for uint8 / JPEG sources) -- a frame
+    crosses PCIe once, a JPEG is decoded once, no mirrored clip is kept; the twins' first masks are the mirrored network-size
+    masks (resized, THEN mirrored: evaluator.py:319-323); cur_label stays [2P, Ho, Wo] with the merged label in row p and its
+    mirror in row P + p (the engine's fused pair kernel writes both), so the twins' memory updates take it as it is."""
 
     def __init__(self, engine, out_hw, device):
         self.engine = engine
         self.B = engine.B
+        self.flip = bool(getattr(engine, 'flip_tta', False))
+        self.clips = self.B // 2 if self.flip else self.B        # clips the caller hands in (rows beyond them are mirrored twins)
         self.out_hw = out_hw
         self.device = device
         self.cur_label = torch.zeros(self.B, out_hw[0], out_hw[1], dtype=torch.uint8, device=device)   # fixed address (graph-captured)
@@ -296,7 +306,7 @@ class GroupSlot:
         network size.  new_objects: {clip index: (frame index, uint8 [Ho, Wo] device map: the new object's label on its pixels, 0
         elsewhere)} -- the evaluator's protocol for an object that appears mid-clip (managers/evaluator.py:484-508): the frame is
         propagated, the new label is laid over the prediction and the frame is re-added as a reference frame for that clip."""
-        assert len(frames) == self.B and len({int(f.shape[0]) for f in frames}) == 1
+        assert len(frames) == self.clips and len({int(f.shape[0]) for f in frames}) == 1
         n = int(frames[0].shape[0])
         self.check_frames()                       # JPEG clips: waits for their decodes, so they can be let go of
         if getattr(self, '_frames_by_pointer', False):
@@ -307,7 +317,7 @@ class GroupSlot:
         if self.new_objects and self.host_u8:
             raise ValueError('new_objects: frames must be fp32 device tensors at the network size')
         if self.labels is None or self.labels.shape[1] < n:
-            self.labels = torch.zeros(self.B, n, self.out_hw[0], self.out_hw[1], dtype=torch.uint8, device=self.device)
+            self.labels = torch.zeros(self.clips, n, self.out_hw[0], self.out_hw[1], dtype=torch.uint8, device=self.device)
         eng = self.engine
         self._frames_by_pointer = not self.host_u8 and eng.lookahead > 1
         eng.restart_engine()
@@ -321,15 +331,18 @@ class GroupSlot:
                 if getattr(self, '_stage', None) is None or tuple(self._stage.shape[1:3]) != (hs, ws):
                     self._stage = torch.empty(la * self.B, hs, ws, 3, dtype=torch.uint8, device=self.device)
                     self._first = torch.empty(self.B, 3, H, W, dtype=torch.float32, device=self.device)
-                for c in range(self.B):
+                for c in range(self.clips):
                     if not frames[c].is_pinned():
                         raise ValueError('uint8 host frames must be in pinned memory')
                     _load_frames(self._stage[c:c + 1], frames[c], 0, 1, s)
-                ops.run([ops.ingest_rgb8(self._stage[c], Hs=hs, Ws=ws, Hd=H, Wd=W, out_chw=self._first[c]) for c in range(self.B)], s)
+                ops.run([ops.ingest_rgb8(self._stage[c], Hs=hs, Ws=ws, Hd=H, Wd=W, out_chw=self._first[c]) for c in range(self.clips)], s)
                 imgs = self._first
             else:
-                imgs = torch.cat([f[0:1] for f in frames], 0)
-            masks = torch.cat([m.reshape(1, 1, m.shape[-2], m.shape[-1]).float() for m in first_masks], 0)
+                imgs = torch.cat([f[0:1] for f in frames] * (2 if self.flip else 1), 0)
+            masks = torch.cat([m.reshape(1, 1, m.shape[-2], m.shape[-1]).float() for m in first_masks] * (2 if self.flip else 1), 0)
+            if self.flip:                                       # the twins' reference frames and first masks
+                self._mirror_twins(imgs, s)
+                self._mirror_twins(masks, s)
         eng.add_reference_frames(imgs, masks, num_objs)
         self.frames_encoded += self.B
         self.cursor = 1
@@ -346,6 +359,10 @@ class GroupSlot:
             torch.cuda.current_stream(self.device).synchronize()
             for c in clips:
                 c.check(self.device)
+
+    def _mirror_twins(self, rows: torch.Tensor, stream: int):
+        """rows fp32 [B, planes, H, W]: rows P..2P-1 := rows 0..P-1 mirrored along W (rmem_resize_nearest_flip_f32 at equal size)."""
+        ops.run(ops.resize_nearest_flip(rows[:self.clips], rows[self.clips:], flip=True), stream)
 
     def _kick_encoder(self, buf: int, i: int):
         """Encode frames i .. i + lookahead - 1 of every clip into look-ahead buffer ``buf`` on the engine's side stream."""
@@ -366,7 +383,20 @@ class GroupSlot:
             # the encoder reads the frames where the clips are (device table of pointers, row k * B + c = frame i + k of clip c): no
             # staging copy; rows beyond the clip's end name its last frame again (encoded, never used)
             last = self.frames[0].shape[0] - 1
-            enc.set_frames([self.frames[c][min(i + k, last)] for k in range(eng.lookahead) for c in range(self.B)], eng.enc_stream.cuda_stream)
+            la, es = eng.lookahead, eng.enc_stream.cuda_stream
+            rows = [[self.frames[c][min(i + k, last)] for c in range(self.clips)] for k in range(la)]
+            if self.flip:
+                # the twins' frames of this batch: mirrored here, on the encoder stream, into this look-ahead buffer's staging rows
+                # (clip-major, one launch per clip).  The rows are read by the encoder launch that follows and rewritten on this
+                # stream only after it, and that launch is what _enc_done / _enc_free order against the propagation.
+                H, W = int(self.frames[0].shape[-2]), int(self.frames[0].shape[-1])
+                if getattr(self, '_twin_stage', None) is None or tuple(self._twin_stage.shape[-2:]) != (H, W):
+                    self._twin_stage = torch.empty(2, self.clips, la, 3, H, W, dtype=torch.float32, device=self.device)
+                st = self._twin_stage[buf]
+                ops.run([ops.resize_nearest_flip(self.frames[c][i:i + m], st[c, :m], flip=True) for c in range(self.clips)], es)
+                for k in range(la):
+                    rows[k] += [st[c, min(k, m - 1)] for c in range(self.clips)]
+            enc.set_frames([f for r in rows for f in r], es)
         eng.encode_ahead(buf)
 
     def _fill_encoder_inputs(self, dst: torch.Tensor, i: int, m: int, stream=None, stage=None):
@@ -378,21 +408,25 @@ class GroupSlot:
         if self.host_u8:
             hs, ws = int(self.frames[0].shape[1]), int(self.frames[0].shape[2])
             H, W = int(dst.shape[-2]), int(dst.shape[-1])
-            for c in range(B):
+            for c in range(self.clips):
                 _load_frames(stage[c * m:(c + 1) * m], self.frames[c], i, m, s)
-            ops.run([ops.ingest_rgb8(stage[c * m + k], Hs=hs, Ws=ws, Hd=H, Wd=W, out_chw=dst[k * B + c]) for c in range(B)
+            ops.run([ops.ingest_rgb8(stage[c * m + k], Hs=hs, Ws=ws, Hd=H, Wd=W, out_chw=dst[k * B + c]) for c in range(self.clips)
                      for k in range(m)], s)
         else:
             fb = dst[0].numel() * 4
-            for c in range(B):
+            for c in range(self.clips):
                 for k in range(m):
                     ops.copy_async(dst[k * B + c], self.frames[c][i + k], fb)(s)
+        if self.flip:                     # the twins' rows: the mirror of what was just ingested / copied, frame by frame
+            for k in range(m):
+                self._mirror_twins(dst[k * B:(k + 1) * B], s)
 
     def step(self, feed: Optional[torch.Tensor] = None):
-        """Propagate frame ``cursor`` of every clip, deliver its labels and update the memories.  feed: uint8 [B, Ho, Wo] device
+        """Propagate frame ``cursor`` of every clip, deliver its labels and update the memories.  feed: uint8 [clips, Ho, Wo] device
         labels that go into the memory update INSTEAD of the prediction (the delivered labels stay the prediction): given masks,
-        e.g. the reference's own in the parity tests, so that every frame is an independent comparison."""
-        eng, B, i = self.engine, self.B, self.cursor
+        e.g. the reference's own in the parity tests, so that every frame is an independent comparison (flip testing: the twins
+        are fed the mirror)."""
+        eng, B, i, P = self.engine, self.B, self.cursor, self.clips
         la = eng.lookahead
         s = eng.stream.cuda_stream
         if la > 1:
@@ -407,22 +441,35 @@ class GroupSlot:
                 imgs = self._first
             else:
                 with torch.cuda.stream(eng.stream):
-                    imgs = torch.cat([f[i:i + 1] for f in self.frames], 0)
+                    imgs = torch.cat([f[i:i + 1] for f in self.frames] * (B // P), 0)
+                    if self.flip:
+                        self._mirror_twins(imgs, s)
             eng.propagate_to_labels(self.cur_label, imgs=imgs)
         inject = [c for c, (fi, _) in self.new_objects.items() if fi == i]
         nb = self.cur_label[0].numel()                # frame i of every clip's label stack: one pitched copy
         if feed is not None:                          # deliver the prediction, then continue from the given labels
-            ops.copy2d_async(self.labels.view(-1)[i * nb:], self.labels.shape[1] * nb, self.cur_label, nb, nb, B)(s)
-            ops.copy_async(self.cur_label, feed.contiguous(), B * nb)(s)
+            ops.copy2d_async(self.labels.view(-1)[i * nb:], self.labels.shape[1] * nb, self.cur_label, nb, nb, P)(s)
+            ops.copy_async(self.cur_label, feed.contiguous(), P * nb)(s)
+            if self.flip:
+                with torch.cuda.stream(eng.stream):
+                    self.cur_label[P:].copy_(self.cur_label[:P].flip(-1))
         if inject:
             with torch.cuda.stream(eng.stream):
                 for c in inject:                      # the new object's label over the prediction (evaluator.py:484-497)
                     new = self.new_objects[c][1]
                     self.cur_label[c].copy_(torch.where(new > 0, new, self.cur_label[c]))
-        eng.update_from_labels(self.cur_label, skip=inject)
+                    if self.flip:                     # and its mirror over the twin's row, which holds the mirrored prediction
+                        self.cur_label[P + c].copy_(self.cur_label[c].flip(-1))
+        rows = inject + [P + c for c in inject] if self.flip else inject
+        eng.update_from_labels(self.cur_label, skip=rows)
         for c in inject:
             eng.add_reference_frame_for(c, self.frames[c][i], self.cur_label[c])
+            if self.flip:                             # the twin is re-initialised from the mirrored frame and the mirrored label
+                if getattr(self, '_twin_ref', None) is None or self._twin_ref.shape != self.frames[c][i:i + 1].shape:
+                    self._twin_ref = torch.empty_like(self.frames[c][i:i + 1])
+                ops.run(ops.resize_nearest_flip(self.frames[c][i:i + 1], self._twin_ref, flip=True), s)
+                eng.add_reference_frame_for(P + c, self._twin_ref[0], self.cur_label[P + c])
         if feed is None:
-            ops.copy2d_async(self.labels.view(-1)[i * nb:], self.labels.shape[1] * nb, self.cur_label, nb, nb, B)(s)
+            ops.copy2d_async(self.labels.view(-1)[i * nb:], self.labels.shape[1] * nb, self.cur_label, nb, nb, P)(s)
         self.cursor += 1
         self.done = self.cursor >= self.frames[0].shape[0]

@@ -423,6 +423,167 @@ __global__ __launch_bounds__(256) void k_tta_merge(TtaParams p) {
   if (p.label_f32) p.label_f32[i] = (float)arg;
 }
 
+// Flip test-time augmentation inside a clip group: rows p and P + p of the group's 16-float logit rows are a clip and its
+// horizontally mirrored twin.  Per output pixel (y, x) of pair p: the plain row blended at (y, x) and the twin at (y, Wo - 1 - x)
+// (k_logits_labels_tile's blend, ids above `keep` masked), each soft-maxed in k_tta_merge's order (max, expf, sum, one
+// reciprocal), plain + twin, * 0.5, first maximum -- k_logits_post + k_tta_merge + the mirror of the merged label for the twin's
+// memory update (managers/evaluator.py:427-441, 490-522) in one pass that writes labels only: label[p][y][x] and the same
+// value at label[P + p][y][Wo - 1 - x].
+__device__ __forceinline__ void flip_softmax_acc(const float* a, const float* b, const float* c, const float* d, float wx, float wy,
+                                                 int nc, int keep, float (&acc)[16]) {
+  float v[16], mx = -3.0e38f, den = 0.f;
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    const f32x4 ta = *reinterpret_cast<const f32x4*>(a + 4 * q), tb = *reinterpret_cast<const f32x4*>(b + 4 * q);
+    const f32x4 tc = *reinterpret_cast<const f32x4*>(c + 4 * q), td = *reinterpret_cast<const f32x4*>(d + 4 * q);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int ch = 4 * q + j;
+      float f = -3.0e38f;
+      if (ch < nc) {
+        if (ch > keep) f = -1.0e10f;
+        else {
+          const float top = ta[j] * (1.f - wx) + tb[j] * wx;
+          const float bot = tc[j] * (1.f - wx) + td[j] * wx;
+          f = top * (1.f - wy) + bot * wy;
+        }
+      }
+      v[ch] = f; mx = fmaxf(mx, f);
+    }
+  }
+#pragma unroll
+  for (int ch = 0; ch < 16; ++ch) { v[ch] = ch < nc ? expf(v[ch] - mx) : 0.f; den += v[ch]; }
+  const float inv = 1.f / den;
+#pragma unroll
+  for (int ch = 0; ch < 16; ++ch) acc[ch] += v[ch] * inv;
+}
+
+__device__ __forceinline__ int flip_merged_label(const float (&acc)[16], int nc) {
+  float best = -1.f; int arg = 0;
+#pragma unroll
+  for (int ch = 0; ch < 16; ++ch) {
+    if (ch < nc) {
+      const float pr = acc[ch] * 0.5f;
+      if (pr > best) { best = pr; arg = ch; }
+    }
+  }
+  return arg;
+}
+
+// >= 2 x upsampling: a workgroup of 128 threads makes a 16 x 32 tile of output pixels of one pair.  The source pixels under the
+// tile (plain row) and under the mirrored tile (twin row), <= FP_SRC each, go to LDS once -- 24 KB per workgroup, less than
+// k_logits_labels_tile's stage: this kernel runs beside the GEMMs of other groups, so the tile shrank instead of the stage
+// doubling.  A thread's 4 consecutive pixels leave as one packed store per row (byte-reversed for the twin) where the address
+// is 4-byte aligned, as byte stores at ragged edges.
+constexpr int FP_H = 16, FP_W = 32, FP_SRC = 192;
+__global__ __launch_bounds__(128) void k_logits_flip_pairs_tile(const float* lg, int P, int nc, int keep, int Hi, int Wi, int Ho, int Wo,
+                                                                int align, uint8_t* label) {
+  __shared__ __attribute__((aligned(16))) float src[2 * FP_SRC * 16];
+  float* const srct = src + FP_SRC * 16;
+  const int tiles_x = (Wo + FP_W - 1) / FP_W;
+  const int ty = blockIdx.x / tiles_x, tx = blockIdx.x - ty * tiles_x;
+  const long total = (long)Ho * Wo, in = (long)Hi * Wi * 16;
+  const float* lgp = lg + (long)blockIdx.y * in;                // blockIdx.y = pair
+  const float* lgt = lg + ((long)P + blockIdx.y) * in;
+  uint8_t* lp = label + (long)blockIdx.y * total;
+  uint8_t* lt = label + ((long)P + blockIdx.y) * total;
+  const int oy0 = ty * FP_H, ox0 = tx * FP_W;
+  const int oy1 = min(oy0 + FP_H, Ho) - 1, ox1 = min(ox0 + FP_W, Wo) - 1;
+  int ylo, yhi, xlo, xhi, mlo, mhi, t0, t1; float tw;
+  src_coord(oy0, Hi, Ho, align, ylo, t1, tw);
+  src_coord(oy1, Hi, Ho, align, t0, yhi, tw);
+  src_coord(ox0, Wi, Wo, align, xlo, t1, tw);
+  src_coord(ox1, Wi, Wo, align, t0, xhi, tw);
+  src_coord(Wo - 1 - ox1, Wi, Wo, align, mlo, t1, tw);          // the mirrored tile: output columns Wo - 1 - ox1 .. Wo - 1 - ox0
+  src_coord(Wo - 1 - ox0, Wi, Wo, align, t0, mhi, tw);
+  const int nrows = yhi - ylo + 1, ncols = xhi - xlo + 1, mcols = mhi - mlo + 1;   // <= FP_SRC pixels each: fp_tiles_fit() on the host
+  for (int i = threadIdx.x; i < nrows * ncols * 4; i += 128) {
+    const int pix = i >> 2, q = i & 3;
+    const int r = pix / ncols, c = pix - r * ncols;
+    *reinterpret_cast<f32x4*>(&src[pix * 16 + 4 * q]) = *reinterpret_cast<const f32x4*>(lgp + ((long)(ylo + r) * Wi + xlo + c) * 16 + 4 * q);
+  }
+  for (int i = threadIdx.x; i < nrows * mcols * 4; i += 128) {
+    const int pix = i >> 2, q = i & 3;
+    const int r = pix / mcols, c = pix - r * mcols;
+    *reinterpret_cast<f32x4*>(&srct[pix * 16 + 4 * q]) = *reinterpret_cast<const f32x4*>(lgt + ((long)(ylo + r) * Wi + mlo + c) * 16 + 4 * q);
+  }
+  __syncthreads();
+  const int oy = oy0 + (threadIdx.x >> 3), oxb = ox0 + (threadIdx.x & 7) * 4;
+  if (oy >= Ho || oxb >= Wo) return;
+  int y0, y1; float wy;
+  src_coord(oy, Hi, Ho, align, y0, y1, wy);
+  const int r0 = y0 - ylo, r1 = y1 - ylo;
+  unsigned pk = 0; int n = 0;
+#pragma unroll 1
+  for (int k = 0; k < 4; ++k) {
+    const int ox = oxb + k;
+    if (ox >= Wo) break;
+    int x0, x1, m0, m1; float wx, wm;
+    src_coord(ox, Wi, Wo, align, x0, x1, wx);
+    src_coord(Wo - 1 - ox, Wi, Wo, align, m0, m1, wm);
+    float acc[16];
+#pragma unroll
+    for (int ch = 0; ch < 16; ++ch) acc[ch] = 0.f;
+    flip_softmax_acc(&src[(r0 * ncols + (x0 - xlo)) * 16], &src[(r0 * ncols + (x1 - xlo)) * 16], &src[(r1 * ncols + (x0 - xlo)) * 16],
+                     &src[(r1 * ncols + (x1 - xlo)) * 16], wx, wy, nc, keep, acc);
+    flip_softmax_acc(&srct[(r0 * mcols + (m0 - mlo)) * 16], &srct[(r0 * mcols + (m1 - mlo)) * 16], &srct[(r1 * mcols + (m0 - mlo)) * 16],
+                     &srct[(r1 * mcols + (m1 - mlo)) * 16], wm, wy, nc, keep, acc);
+    pk |= (unsigned)flip_merged_label(acc, nc) << (8 * k);
+    n = k + 1;
+  }
+  uint8_t* dp = lp + (long)oy * Wo + oxb;                       // pixels oxb .. oxb + n - 1 of the plain row, left to right
+  uint8_t* dt = lt + (long)oy * Wo + (Wo - 1 - oxb);            // the same pixels of the twin's row, right to left
+  if (n == 4 && (reinterpret_cast<uintptr_t>(dp) & 3) == 0) *reinterpret_cast<unsigned*>(dp) = pk;
+  else for (int k = 0; k < n; ++k) dp[k] = (uint8_t)(pk >> (8 * k));
+  if (n == 4 && (reinterpret_cast<uintptr_t>(dt - 3) & 3) == 0) *reinterpret_cast<unsigned*>(dt - 3) = __builtin_bswap32(pk);
+  else for (int k = 0; k < n; ++k) dt[-k] = (uint8_t)(pk >> (8 * k));
+}
+
+// host side of k_logits_flip_pairs_tile: the source pixels under EVERY output tile and under every mirrored tile fit FP_SRC
+bool fp_tiles_fit(int Hi, int Wi, int Ho, int Wo, int align) {
+  int rows = 0, cols = 0, lo, hi, t; float w;
+  for (int o0 = 0; o0 < Ho; o0 += FP_H) {
+    rmem_src_coord(o0, Hi, Ho, align, lo, t, w);
+    rmem_src_coord((o0 + FP_H < Ho ? o0 + FP_H : Ho) - 1, Hi, Ho, align, t, hi, w);
+    rows = hi - lo + 1 > rows ? hi - lo + 1 : rows;
+  }
+  for (int o0 = 0; o0 < Wo; o0 += FP_W) {
+    const int o1 = (o0 + FP_W < Wo ? o0 + FP_W : Wo) - 1;
+    rmem_src_coord(o0, Wi, Wo, align, lo, t, w);
+    rmem_src_coord(o1, Wi, Wo, align, t, hi, w);
+    cols = hi - lo + 1 > cols ? hi - lo + 1 : cols;
+    rmem_src_coord(Wo - 1 - o1, Wi, Wo, align, lo, t, w);
+    rmem_src_coord(Wo - 1 - o0, Wi, Wo, align, t, hi, w);
+    cols = hi - lo + 1 > cols ? hi - lo + 1 : cols;
+  }
+  return rows * cols <= FP_SRC;
+}
+
+// below 2 x upsampling, or where a tile's source pixels do not fit: one output pixel per thread, taps from global memory
+__global__ __launch_bounds__(256) void k_logits_flip_pairs_px(const float* lg, int P, int nc, int keep, int Hi, int Wi, int Ho, int Wo,
+                                                              int align, uint8_t* label) {
+  const long total = (long)Ho * Wo, in = (long)Hi * Wi * 16;
+  const long i = (long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= total) return;
+  const float* lgp = lg + (long)blockIdx.y * in;                // blockIdx.y = pair
+  const float* lgt = lg + ((long)P + blockIdx.y) * in;
+  const int oy = (int)(i / Wo), ox = (int)(i - (long)oy * Wo);
+  int y0, y1, x0, x1, m0, m1; float wy, wx, wm;
+  src_coord(oy, Hi, Ho, align, y0, y1, wy);
+  src_coord(ox, Wi, Wo, align, x0, x1, wx);
+  src_coord(Wo - 1 - ox, Wi, Wo, align, m0, m1, wm);
+  float acc[16];
+#pragma unroll
+  for (int ch = 0; ch < 16; ++ch) acc[ch] = 0.f;
+  flip_softmax_acc(lgp + ((long)y0 * Wi + x0) * 16, lgp + ((long)y0 * Wi + x1) * 16, lgp + ((long)y1 * Wi + x0) * 16,
+                   lgp + ((long)y1 * Wi + x1) * 16, wx, wy, nc, keep, acc);
+  flip_softmax_acc(lgt + ((long)y0 * Wi + m0) * 16, lgt + ((long)y0 * Wi + m1) * 16, lgt + ((long)y1 * Wi + m0) * 16,
+                   lgt + ((long)y1 * Wi + m1) * 16, wm, wy, nc, keep, acc);
+  const uint8_t arg = (uint8_t)flip_merged_label(acc, nc);
+  label[(long)blockIdx.y * total + i] = arg;
+  label[((long)P + blockIdx.y) * total + (long)oy * Wo + (Wo - 1 - ox)] = arg;
+}
+
 // > 10 objects: one AOTEngine per 10 objects (engines/aot_engine.py:604-673).
 // split: the label map of engine e keeps ids start..end renumbered from 1, everything else 0 (separate_mask, 610-628).
 __global__ __launch_bounds__(256) void k_split_label(const float* label, int start_id, int end_id, float* out, long n) {
@@ -672,6 +833,26 @@ extern "C" int rmem_tta_merge(const float* const* logits_nchw, const int* flips,
   p.n_aug = n_aug; p.nc = num_classes; p.H = H; p.W = W; p.label = label_u8; p.label_f32 = label_f32; p.prob = prob_nchw;
   hipLaunchKernelGGL(k_tta_merge, dim3(nblk((long)H * W)), dim3(256), 0, (hipStream_t)stream, p);
   return rmem_check_launch("rmem_tta_merge");
+}
+#endif
+
+#ifndef RMEM_F16
+extern "C" int rmem_logits_post_flip_pairs(const float* logits_nhwc16, int rows, int num_classes, int keep_max_id, int Hi, int Wi, int Ho,
+                                           int Wo, int align_corners, unsigned char* label_u8, void* stream) {
+  RMEM_REQUIRE(logits_nhwc16 && label_u8, "rmem_logits_post_flip_pairs: null pointer");
+  RMEM_REQUIRE(rows >= 2 && rows % 2 == 0, "rmem_logits_post_flip_pairs: rows must be even (row p and row rows / 2 + p are a pair)");
+  RMEM_REQUIRE(num_classes >= 1 && num_classes <= 16 && keep_max_id >= 0 && keep_max_id < num_classes,
+               "rmem_logits_post_flip_pairs: 1..16 classes, 0 <= keep_max_id < num_classes");
+  RMEM_REQUIRE(Hi > 0 && Wi > 0 && Ho > 0 && Wo > 0 && ((uintptr_t)logits_nhwc16 % 16) == 0,
+               "rmem_logits_post_flip_pairs: bad size, or logits not 16-byte aligned");
+  const int P = rows / 2;
+  if (Ho >= 2 * Hi && Wo >= 2 * Wi && fp_tiles_fit(Hi, Wi, Ho, Wo, align_corners))
+    hipLaunchKernelGGL(k_logits_flip_pairs_tile, dim3(((Ho + FP_H - 1) / FP_H) * ((Wo + FP_W - 1) / FP_W), P), dim3(128), 0, (hipStream_t)stream,
+                       logits_nhwc16, P, num_classes, keep_max_id, Hi, Wi, Ho, Wo, align_corners, label_u8);
+  else
+    hipLaunchKernelGGL(k_logits_flip_pairs_px, dim3(nblk((long)Ho * Wo), P), dim3(256), 0, (hipStream_t)stream, logits_nhwc16, P,
+                       num_classes, keep_max_id, Hi, Wi, Ho, Wo, align_corners, label_u8);
+  return rmem_check_launch("rmem_logits_post_flip_pairs");
 }
 #endif
 

@@ -18,7 +18,15 @@ Covered protocols (the reference's evaluator, managers/evaluator.py:385-523):
 R50-DeAOTL models run through group_runtime_deaot.GroupRuntimeDeAOT (same protocols; the eviction policy's scores and visit
 counts then move on EVERY long-term update, deaot_engine.py / transformer.py:880-892).
 SwinB-AOTL models (cfg 5) run through the same GroupRuntime with encoder_batch.SwinBatchEncoder as the look-ahead encoder.
-Clips with > 10 objects and multi-scale / flip testing run on the per-clip engines, which are the drop-in API.
+FLIP TESTING (managers/evaluator.py:342-355, 427-441) runs inside a group too: with ``flip_tta=True`` the B = 2P rows are P
+clips (rows 0..P-1) and their horizontally mirrored twins (rows P..2P-1).  A twin is one more clip of the same length and
+network size, so launch lists, graphs, look-ahead and the per-row bank schedule / eviction policy / ``long_memories_indexes``
+are unchanged (the reference gives every augmentation its own engine); the one coupling, after the decoder, is
+ops.logits_post_flip_pairs in place of ops.logits_post: the mean of the pair's softmaxes, arg-maxed, written to the clip's
+label row and mirrored to the twin's, with no full-size fp32 map in between.  clip_runner.GroupSlot mirrors the twins' frames,
+first masks, new-object overlays and fed labels.
+Clips with > 10 objects and multi-scale testing (one network size per scale, so no shared runtime) run on the per-clip engines,
+which are the drop-in API.
 """
 from __future__ import annotations
 
@@ -34,7 +42,11 @@ F32 = torch.float32
 
 
 class GroupEngine:
-    def __init__(self, aot_model, clips: int, gpu_id: int = 0, long_term_mem_gap: int = 9999, lookahead: int = 4, streams=None):
+    def __init__(self, aot_model, clips: int, gpu_id: int = 0, long_term_mem_gap: int = 9999, lookahead: int = 4, streams=None,
+                 flip_tta: bool = False):
+        if flip_tta and (clips < 2 or clips % 2):
+            raise ValueError(f'GroupEngine(flip_tta=True): clips is the row count 2P, a clip and its mirrored twin per pair (got {clips})')
+        self.flip_tta = flip_tta
         self.cfg = aot_model.cfg
         self.AOT = aot_model
         self.B = clips
@@ -151,7 +163,7 @@ class GroupEngine:
     # ------------------------------------------------------------------ propagate (aot_engine.py:398-465 + evaluator.py:430-441)
     def propagate_to_labels(self, labels_u8: torch.Tensor, enc_slot: Optional[int] = None, imgs: Optional[torch.Tensor] = None):
         """labels_u8: uint8 [B, Ho, Wo] device buffer at a fixed address.  Either enc_slot (frame encoded by encode_ahead) or
-        imgs [B, 3, H, W] (encoded now)."""
+        imgs [B, 3, H, W] (encoded now).  flip_tta: rows p and B/2 + p are merged; row p gets the label, row B/2 + p its mirror."""
         self.frame_step += 1
         rt, B = self.rt, self.B
         T, wm = self.bank.begin_propagation(rt)
@@ -159,8 +171,13 @@ class GroupEngine:
         with torch.cuda.stream(self.stream):
             pk = f'post_{labels_u8.data_ptr()}_{Ho}_{Wo}'
             if pk not in rt._prog:
-                rt._prog[pk] = [ops.logits_post(rt.logits, ldl=16, nc=rt.nc, keep=self.obj_nums[0], Hi=rt.H4, Wi=rt.W4, Ho=Ho, Wo=Wo,
-                                                align_corners=self.align_corners, label_u8=labels_u8, images=B)]
+                if self.flip_tta:
+                    post = ops.logits_post_flip_pairs(rt.logits, nc=rt.nc, keep=self.obj_nums[0], Hi=rt.H4, Wi=rt.W4, Ho=Ho, Wo=Wo,
+                                                      align_corners=self.align_corners, label_u8=labels_u8, rows=B)
+                else:
+                    post = ops.logits_post(rt.logits, ldl=16, nc=rt.nc, keep=self.obj_nums[0], Hi=rt.H4, Wi=rt.W4, Ho=Ho, Wo=Wo,
+                                           align_corners=self.align_corners, label_u8=labels_u8, images=B)
+                rt._prog[pk] = [post]
             if enc_slot is None:
                 ops.copy_async(rt.enc_now.img_in, imgs.contiguous(), B * 3 * rt.H * rt.W * 4)(self._s())
                 prog = rt.prog_encode() + rt.prog_project(None) + rt.prog_lstt(False, T, wm) + rt.prog_decode(None) + rt._prog[pk]

@@ -504,6 +504,21 @@ def logits_post(logits, *, ldl, nc, keep, Hi, Wi, Ho, Wo, align_corners=True, ou
     return Op(_lib.lib().rmem_logits_post_images, args, 'rmem_logits_post', (logits, out, label_u8, label_f32))
 
 
+def logits_post_flip_pairs(logits, *, nc, keep, Hi, Wi, Ho, Wo, label_u8, rows, align_corners=True) -> Op:
+    """Flip test-time augmentation of a clip group, fused: logits fp32 [rows, Hi*Wi, 16] with row p a clip and row rows/2 + p its
+    mirrored twin -> label_u8 [rows, Ho, Wo]: the argmax of the pair's mean softmax in row p, its mirror in row rows/2 + p
+    (rmem_logits_post_flip_pairs; no full-size fp32 map is written)."""
+    if rows < 2 or rows % 2:
+        raise RmemError(f'logits_post_flip_pairs: rows must be even, a clip and its mirrored twin per pair (got {rows})')
+    if not (1 <= nc <= 16 and 0 <= keep < nc):
+        raise RmemError(f'logits_post_flip_pairs: 1..16 classes and 0 <= keep < nc (got nc={nc}, keep={keep})')
+    _dev(logits, label_u8)
+    assert logits.dtype == F32 and logits.is_contiguous() and logits.numel() >= rows * Hi * Wi * 16
+    assert label_u8.dtype == torch.uint8 and label_u8.is_contiguous() and label_u8.numel() >= rows * Ho * Wo
+    args = (_ptr(logits), rows, nc, keep, Hi, Wi, Ho, Wo, int(align_corners), _ptr(label_u8))
+    return Op(_lib.lib().rmem_logits_post_flip_pairs, args, 'rmem_logits_post_flip_pairs', (logits, label_u8))
+
+
 def label_to_onehot16(label, out, *, Hs, Ws, Hd, Wd, ncls=11, images=1) -> Op:
     """label [images, Hs, Ws] uint8 / fp32 -> bf16 [images, Hd*Wd, 16]"""
     _dev(label, out)
