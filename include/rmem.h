@@ -575,6 +575,25 @@ int rmem_tta_merge(const float* const* logits_nchw, const int* flips, int n_aug,
 int rmem_logits_post_flip_pairs(const float* logits_nhwc16, int rows, int num_classes, int keep_max_id, int Hi, int Wi, int Ho, int Wo,
                                 int align_corners, unsigned char* label_u8, void* stream);
 
+/* Label routing of a RAGGED clip group (clip_runner.RaggedGroupSlot): the rows of a group run clips of different lengths, so after
+ * the decoder every row delivers its label map to another address, and a row may take a new object's overlay, continue from fed
+ * labels, mirror into its flip twin or be idle.  One launch, driven by a device table of `rows` entries; rows_u8 [rows][Ho * Wo]
+ * (the group's label rows, what the memory update reads) is rewritten in place.  Per row of mode 0, pred = the row on entry:
+ *   x = feed ? feed : pred;   overlay: x = overlay > 0 ? overlay : x;   dst (if set) := feed ? pred : x;   row := x;
+ *   twin >= 0: rows_u8[twin] := x mirrored along W (the twin's own entry has mode 2: its row is written by its primary only).
+ * mode 1 (idle): row := 0, nothing is delivered, twin / feed / overlay / dst are not looked at.  dst, overlay and feed name Ho * Wo
+ * bytes each and may not overlap rows_u8.  Rows start at any byte, so 4-byte accesses are used where every address of a row allows
+ * them and single bytes otherwise.  Replaces the per-row torch.where / flip / copy of clip_runner.GroupSlot.step (evaluator.py:
+ * 484-497).  Refused (non-zero, nothing launched): rows outside 1..65535, null rows_u8 / routes, non-positive Ho / Wo. */
+typedef struct {
+  unsigned char* dst;           /* this row's label map of this step goes here (Ho * Wo bytes), or NULL */
+  const unsigned char* overlay; /* new object's map: its non-zero pixels replace the row's, or NULL */
+  const unsigned char* feed;    /* labels to continue from instead of the prediction, or NULL */
+  int twin;                     /* row that receives this row's final map mirrored along W, or -1 */
+  int mode;                     /* 0 live, 1 idle (row := 0, nothing delivered), 2 written by its primary (skip) */
+} rmem_label_route;
+int rmem_route_labels(unsigned char* rows_u8, int rows, int Ho, int Wo, const rmem_label_route* routes, void* stream);
+
 /* Region-similarity (Jaccard) counts per object id for one mask pair: counts[2*id] += |pred==id & gt==id|,
  * counts[2*id+1] += |pred==id | gt==id| over the n pixels whose ground truth is not `void_label`; the caller zeroes
  * counts (uint64 [2 * num_ids]).  Replaces evaluation/source/metrics.py:6-37 (db_eval_iou) per object. */

@@ -77,6 +77,13 @@ class PngDesc(C.Structure):
     _fields_ = [('offset', C.c_longlong), ('bytes', C.c_longlong), ('bit_depth', C.c_int), ('colour_type', C.c_int)]
 
 
+class LabelRoute(C.Structure):
+    _fields_ = [('dst', C.c_void_p), ('overlay', C.c_void_p), ('feed', C.c_void_p), ('twin', C.c_int), ('mode', C.c_int)]
+
+
+ROUTE_LIVE, ROUTE_IDLE, ROUTE_SKIP = 0, 1, 2                           # rmem_label_route.mode
+
+
 def _desc(name, ints, ptrs):
     """ctypes mirror of an rmem_chain_*_desc: (int, int, float, int) header + device pointers, in include/rmem.h's order."""
     return type(name, (C.Structure,), {'_fields_': [(ints[0], _i), (ints[1], _i), ('eps', _f), (ints[2], _i)] + [(n, _vp) for n in ptrs]})
@@ -153,6 +160,7 @@ SIGNATURES = {
     'rmem_resize_nearest_flip_f32': (_i, [_vp, _i, _i, _i, _vp, _i, _i, _i, _vp]),
     'rmem_tta_merge': (_i, [C.POINTER(_vp), C.POINTER(_i), _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
     'rmem_logits_post_flip_pairs': (_i, [_vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp]),
+    'rmem_route_labels': (_i, [_vp, _i, _i, _i, _vp, _vp]),
     'rmem_mask_iou_counts': (_i, [_vp, _vp, _ll, _i, _i, _vp, _vp]),
     'rmem_clip_score_workspace_bytes': (C.c_size_t, [_i, _i, _i, _i]),
     'rmem_boundary_radius': (_i, [_i, _i, C.c_double]),

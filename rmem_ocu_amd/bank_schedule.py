@@ -10,6 +10,12 @@ stand-in for those drives the whole schedule without a GPU (tests/test_host_logi
 The eviction decision is deferred: ``commit_update`` only issues the score readback, ``resolve`` takes the decision right
 before the bank is used again, so the host never waits in the update.  Between the two a restricted bank holds N + 1 entries
 (``bank_slots``).
+
+RAGGED groups (clip_runner.RaggedGroupSlot): the rows of a group may run clips of different lengths, each at its own frame index
+with its own gap.  A row then has a frame counter and a gap of its own (``row_step`` / ``row_gap``, set by ``start_clips``, moved
+by ``advance``); a row without them reads the owner's shared ``frame_step`` / ``long_term_mem_gap``, so an engine that never
+starts a clip per row behaves as before.  A row whose clip has ended is IDLE until the next clip moves in (``finish_clips``): its
+bank is cut back to its first entry and frozen -- it never appends, is never scored and never lengthens the group's T.
 """
 from __future__ import annotations
 
@@ -70,7 +76,8 @@ def device_scores(rt, stream, clips: List[int], T: int, keep: int):
 
 
 class BankSchedule:
-    """The banks of ``clips`` clips of one engine.  ``owner`` is the engine: ``frame_step``, ``long_term_mem_gap``, ``cfg`` (bank
+    """The banks of ``clips`` clips (rows) of one engine.  ``owner`` is the engine: ``frame_step``, ``long_term_mem_gap`` (the defaults
+    of rows without a counter / gap of their own), ``cfg`` (bank
     length, NO_LONG_MEMORY), ``policy_every_update`` and ``stream`` are read from it when a decision is taken (callers set the gap
     on a started engine).  The runtime whose ``slots`` / ``free`` / ``S`` the decisions act on is an argument: an engine may
     replace its runtime, the index lists outlive it."""
@@ -86,6 +93,9 @@ class BankSchedule:
         self.indexes: List[List[int]] = [[] for _ in range(B)]
         self.policies = [MemoryPolicy() for _ in range(B)]
         self.drop_trace: List[List[int]] = [[] for _ in range(B)]
+        self.row_step: List[Optional[int]] = [None] * B    # the row's own frame counter (None: the owner's frame_step)
+        self.row_gap: List[Optional[int]] = [None] * B     # the row's own gap (None: the owner's long_term_mem_gap)
+        self.idle: set = set()                             # rows whose clip has ended and has not been replaced
         self._pending = None
         self._mass_valid = False
         self._T_at_propagate = 0                         # the group's T: layout of the mass buffer
@@ -99,6 +109,19 @@ class BankSchedule:
 
     def _s(self) -> int:
         return self.owner.stream.cuda_stream
+
+    def step_of(self, c: int) -> int:
+        """Frame index row ``c`` is at, counted from its clip's frame 0."""
+        return self.owner.frame_step if self.row_step[c] is None else self.row_step[c]
+
+    def gap_of(self, c: int) -> int:
+        return self.owner.long_term_mem_gap if self.row_gap[c] is None else self.row_gap[c]
+
+    def advance(self):
+        """The next frame is propagated: rows with a frame counter of their own move on by one frame (idle rows stay)."""
+        for c in range(self.B):
+            if self.row_step[c] is not None and c not in self.idle:
+                self.row_step[c] += 1
 
     def long_memories_indexes(self, clip: int) -> List[int]:
         """Frame indexes of the clip's bank entries (aot_engine.py:323, 351); resolves a deferred eviction first."""
@@ -130,17 +153,51 @@ class BankSchedule:
         on, which ``rt`` may have replaced (a frame of another size)."""
         self.resolve()
         clips = list(range(self.B) if clips is None else clips)
-        step = self.owner.frame_step
         for c in clips:
+            step = self.step_of(c)
             self.last_mem_step[c] = step if mem_step is None else mem_step
             self.policies[c] = MemoryPolicy()
             self.indexes[c].append(step)
         return self.restart_banks(rt, clips, self._s(), append_table)
 
+    # ------------------------------------------------------------------ ragged groups: a NEW CLIP per row
+    def start_clips(self, rt, rows: Iterable[int], gaps: Iterable[int], append_table: bool = False) -> List[int]:
+        """A new clip starts in ``rows`` with the per-row ``gaps``.  Unlike a mid-clip reference frame (start_reference keeps the
+        row's index list growing, which is why a later eviction of that clip raises) the row starts over: index list [0], empty
+        drop trace, a fresh policy, last long-term update and frame counter at the clip's own frame 0, bank := one entry.  A
+        pending eviction is resolved first (it may belong to another row; a finished row's traces were handed out by
+        finish_clips).  -> per-row bank slot of the entry (-1: row not started); the caller writes the entry."""
+        self.resolve()
+        rows = list(rows)
+        for c, gap in zip(rows, gaps):
+            self.idle.discard(c)
+            self.row_step[c], self.row_gap[c] = 0, int(gap)
+            self.last_mem_step[c] = 0
+            self.policies[c] = MemoryPolicy()
+            self.indexes[c] = [0]
+            self.drop_trace[c] = []
+        return self.restart_banks(rt, rows, self._s(), append_table)
+
+    def finish_clips(self, rt, rows: Iterable[int]) -> List[Tuple[List[int], List[int]]]:
+        """The clips of ``rows`` have ended: -> their (long_memories_indexes, drop_trace), a deferred eviction resolved first.  The
+        rows are idle from here on; their banks keep the first entry only (a bank the memory read has run on, of the shortest
+        length there is), so an idle row never lengthens T."""
+        self.resolve()
+        rows = list(rows)
+        out = [(list(self.indexes[c]), list(self.drop_trace[c])) for c in rows]
+        for c in rows:
+            self.idle.add(c)
+            rt.free[c] = sorted(rt.free[c] + rt.slots[c][1:])
+            del rt.slots[c][1:]
+        if rows:
+            rt.upload_chunks(self._s())
+        return out
+
     # ------------------------------------------------------------------ propagate
     def _will_append(self, c: int) -> bool:
-        o = self.owner
-        return not getattr(o.cfg, 'NO_LONG_MEMORY', False) and o.frame_step - self.last_mem_step[c] >= o.long_term_mem_gap
+        if c in self.idle or getattr(self.owner.cfg, 'NO_LONG_MEMORY', False):
+            return False
+        return self.step_of(c) - self.last_mem_step[c] >= self.gap_of(c)
 
     def begin_propagation(self, rt) -> Tuple[int, bool]:
         """-> (bank size T the launches are built for: the longest bank; whether the attention mass of layer 0 is wanted).  The
@@ -179,9 +236,9 @@ class BankSchedule:
         scored, over = [], set()            # clips whose policy state moves / whose bank overflows
         for c, slot in enumerate(slots):
             if slot >= 0:
-                self.last_mem_step[c] = self.owner.frame_step
+                self.last_mem_step[c] = self.step_of(c)
                 rt.slots[c].append(slot)
-                self.indexes[c].append(self.owner.frame_step)
+                self.indexes[c].append(self.step_of(c))
                 if len(rt.slots[c]) > self.n_keep:
                     over.add(c)
                 if c in over or self.owner.policy_every_update:

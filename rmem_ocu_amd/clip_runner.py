@@ -10,11 +10,11 @@ hipGraphs; the host only enqueues.
 """
 from __future__ import annotations
 
-from typing import List, Optional, Sequence
+from typing import List, NamedTuple, Optional, Sequence
 
 import torch
 
-from . import ops
+from . import _lib, ops
 from .jpeg import JpegClip
 
 
@@ -473,3 +473,392 @@ class GroupSlot:
             ops.copy2d_async(self.labels.view(-1)[i * nb:], self.labels.shape[1] * nb, self.cur_label, nb, nb, P)(s)
         self.cursor += 1
         self.done = self.cursor >= self.frames[0].shape[0]
+
+
+class FinishedClip(NamedTuple):
+    """A clip a RaggedGroupSlot has finished: labels uint8 [n, Ho, Wo] on the device (row 0 zero), ``event`` recorded on the engine's
+    stream behind the clip's last delivery (a consumer stream waits on it, then scores / saves the stack while the group runs on),
+    and the clip's bank traces."""
+    clip_id: object
+    labels: torch.Tensor
+    event: object
+    long_memories_indexes: List[int]
+    drop_trace: List[int]
+    twin_traces: Optional[tuple] = None        # flip testing: (long_memories_indexes, drop_trace) of the mirrored twin's row
+
+
+class _RaggedClip:
+    __slots__ = ('id', 'frames', 'mask', 'new_objects', 'gap', 'n', 'labels', 'host_u8', 'ready')
+
+
+class _Row:
+    __slots__ = ('clip', 'i', 'live')
+
+    def __init__(self):
+        self.clip, self.i, self.live = None, 0, False
+
+
+class RaggedGroupSlot:
+    """Clips of ANY length in flight on one GroupEngine: continuous batching for clip groups.  The group is a set of rows; each row
+    runs its own clip at its own frame index with its own gap, and when a row's clip ends the next queued clip moves into that row
+    (GroupEngine.start_clips: reference frame through the one-clip side runtime, fresh bank schedule for the row) while the other
+    rows keep going.  Same protocol per clip as GroupSlot; every clip owns its label stack [n, Ho, Wo] (allocated at submit, row 0
+    zero) and is handed out as a FinishedClip when its last frame has been enqueued.
+
+    Look-ahead n > 1: rows are re-assigned at look-ahead batch boundaries.  When batch k + 1 is kicked (at the first step of batch
+    k) the slot knows which rows end inside batch k and puts frames 1..n of the next queued clips into those rows of batch k + 1;
+    their frame 0 goes through the row-start path at the boundary.  A row whose clip ends mid-batch idles for at most n - 1 steps
+    (route mode idle: its label row is zeroed, nothing is delivered; its bank is frozen at one entry).  Look-ahead 1: a row is
+    refilled before the next step.  Per step the labels of all rows are routed by ONE launch (ops.LabelRoutes, rmem_route_labels):
+    delivery into each clip's stack, a new object's overlay, fed labels, the mirror into a flip twin.
+
+    Frame sources: fp32 device frames at the network size, or uint8 frames in pinned host memory (staged and ingested as in
+    GroupSlot).  All clips of a slot share the network size and the output size.  With GroupEngine(flip_tta=True) the slot takes
+    B / 2 rows of clips and makes their mirrored twins itself (frames and masks resized, THEN mirrored).
+
+    Counters: row_steps_live / row_steps_idle (rows that propagated a frame of a clip / did not, per step), refills (clips that moved
+    into a row another clip had run in), frames_encoded (as in GroupSlot: every row of the group per encoded frame index)."""
+
+    def __init__(self, engine, out_hw, device):
+        self.engine = engine
+        self.B = engine.B
+        self.flip = bool(getattr(engine, 'flip_tta', False))
+        self.clips = self.B // 2 if self.flip else self.B
+        self.out_hw = (int(out_hw[0]), int(out_hw[1]))
+        self.device = device
+        self._queue: List[_RaggedClip] = []
+        self._trivial: List[_RaggedClip] = []          # single-frame clips: nothing to propagate
+        self._rows = [_Row() for _ in range(self.clips)]
+        self._net_hw = None
+        self._src_hw = None                            # uint8 sources: their frame size
+        self._started = False
+        self._k, self._e = 0, 0                        # look-ahead batch counter, frame inside the batch
+        self._plan = None                              # {row: (clip, first frame, is new)} of the batch kicked ahead
+        self._retired = []                             # (events, clip): frames queued launches may still read in place
+        self.cur_label = None
+        self._inputs_zeroed = False                    # uint8 sources: the look-ahead encoders' inputs have been zeroed once
+        self.row_steps_live = self.row_steps_idle = self.refills = self.frames_encoded = 0
+
+    # ------------------------------------------------------------------ queue
+    def submit(self, clip_id, frames, first_mask, new_objects=None, gap: Optional[int] = None):
+        """Queue a clip: frames fp32 [n, 3, H, W] on the device at the network size (work that produces them must have been enqueued
+        on the current stream before this call: the engine's streams wait for an event recorded here), or uint8 [n, Hs, Ws, 3] in
+        pinned host memory;
+        first_mask [1, 1, H, W] at the network size; new_objects {frame index: uint8 [Ho, Wo] device map} (or one (frame index, map)
+        pair); gap: the clip's long_term_mem_gap, default max(round(n / 30), 5) (evaluator.py:330-335)."""
+        if isinstance(frames, JpegClip):
+            raise ValueError(f'RaggedGroupSlot: clip {clip_id!r} is a JpegClip; JPEG sources are out of scope for ragged groups '
+                             '(decode the clip first, or run it on GroupSlot / ClipSlot)')
+        c = _RaggedClip()
+        c.id, c.frames, c.n = clip_id, frames, int(frames.shape[0])
+        c.host_u8 = frames.dtype == torch.uint8
+        hw = (int(first_mask.shape[-2]), int(first_mask.shape[-1]))
+        if not c.host_u8 and tuple(frames.shape[1:]) != (3,) + hw:
+            raise ValueError(f'RaggedGroupSlot: clip {clip_id!r}: fp32 frames {tuple(frames.shape)} are not [n, 3, H, W] at the size of the first mask {hw}')
+        if self._net_hw is not None and hw != self._net_hw:
+            raise ValueError(f'RaggedGroupSlot: clip {clip_id!r} has network size {hw}, the slot runs {self._net_hw}: all clips of a '
+                             'slot share one network size (bucket the clip list by size, one slot per size)')
+        if c.host_u8:
+            src = (int(frames.shape[1]), int(frames.shape[2]))
+            if frames.dim() != 4 or frames.shape[3] != 3:
+                raise ValueError(f'RaggedGroupSlot: clip {clip_id!r}: uint8 frames must be [n, Hs, Ws, 3]')
+            if self._src_hw is not None and src != self._src_hw:
+                raise ValueError(f'RaggedGroupSlot: clip {clip_id!r} has uint8 frames of {src}, the slot stages {self._src_hw}: all '
+                                 'clips of a slot share one frame size')
+            if self.device.type == 'cuda' and not frames.is_pinned():
+                raise ValueError('uint8 host frames must be in pinned memory')
+            if new_objects:
+                raise ValueError('new_objects: frames must be fp32 device tensors at the network size')
+            self._src_hw = src
+        self._net_hw = hw
+        if isinstance(new_objects, tuple):
+            new_objects = {new_objects[0]: new_objects[1]}
+        c.new_objects = {int(k): v for k, v in (new_objects or {}).items()}
+        c.mask = first_mask
+        c.gap = max(int(round(c.n / 30)), 5) if gap is None else int(gap)
+        c.labels = torch.zeros(c.n, self.out_hw[0], self.out_hw[1], dtype=torch.uint8, device=self.device)
+        c.ready = None
+        if self.device.type == 'cuda':             # the stack is zeroed on the caller's stream and written on the engine's
+            c.ready = torch.cuda.Event()
+            c.ready.record(torch.cuda.current_stream(self.device))
+        (self._queue if c.n > 1 else self._trivial).append(c)
+
+    @property
+    def done(self) -> bool:
+        """Queue empty and no live row."""
+        return not self._queue and not self._trivial and not self._plan and not any(r.live for r in self._rows)
+
+    def run(self, clips):
+        """submit / step / yield until the iterable of (clip_id, frames, first_mask[, new_objects[, gap]]) and the rows are drained;
+        the queue is kept two clips per row ahead."""
+        it, dry = iter(clips), False
+        while True:
+            while not dry and len(self._queue) < 2 * self.clips:
+                try:
+                    self.submit(*next(it))
+                except StopIteration:
+                    dry = True
+            if dry and self.done:
+                return
+            yield from self.step()
+
+    # ------------------------------------------------------------------ device buffers
+    def _buffers(self):
+        if self.cur_label is not None:
+            return
+        B, P, dev, (H, W) = self.B, self.clips, self.device, self._net_hw
+        self.cur_label = torch.zeros(B, self.out_hw[0], self.out_hw[1], dtype=torch.uint8, device=dev)   # fixed address (graph-captured)
+        self.routes = ops.LabelRoutes(self.cur_label, dev)
+        self._first = torch.zeros(B, 3, H, W, dtype=torch.float32, device=dev)      # row-start frames (uint8 sources), look-ahead 1 input
+        if self.flip:
+            self._twin_img = torch.zeros(P, 3, H, W, dtype=torch.float32, device=dev)
+            self._twin_mask = torch.zeros(P, 1, H, W, dtype=torch.float32, device=dev)
+        if self._src_hw is not None:
+            la = max(self.engine.lookahead, 1)
+            self._stage = torch.zeros(P, *self._src_hw, 3, dtype=torch.uint8, device=dev)
+            self._stage_la = torch.zeros(la * P, *self._src_hw, 3, dtype=torch.uint8, device=dev)
+        if self._src_hw is None:
+            # what the encoder rows of idle rows name (fp32 sources are read in place): a frame the slot owns, so that no finished
+            # clip's frames are named after its end
+            self._idle_frame = torch.zeros(3, H, W, dtype=torch.float32, device=dev)
+        if self.flip and self.engine.lookahead > 1 and self._src_hw is None:
+            self._twin_stage = torch.zeros(2, P, self.engine.lookahead, 3, H, W, dtype=torch.float32, device=dev)
+        # the buffers were zeroed on the current stream; the engine's streams use them from here on
+        for st in (self.engine.stream, self.engine.enc_stream):
+            st.wait_stream(torch.cuda.current_stream(dev))
+
+    def _mirror(self, src: torch.Tensor, dst: torch.Tensor, stream: int):
+        ops.run(ops.resize_nearest_flip(src, dst, flip=True), stream)
+
+    def _release(self):
+        """Let go of finished clips whose frames no queued launch reads any more (no host wait: the events are only queried)."""
+        self._retired = [(evs, c) for evs, c in self._retired if not all(e.query() for e in evs)]
+
+    # ------------------------------------------------------------------ a new clip per row
+    def _start(self, assign):
+        """assign [(row, clip)]: frame 0 of each clip through the engine's row-start path; rows that have never held a clip and get
+        none now take a copy of the first clip's reference frame as their bank entry and idle (a row the memory read has never run
+        on is not built on); they hold no clip, so the first clip that moves into one is no refill."""
+        eng, P = self.engine, self.clips
+        if not self._started:
+            eng.restart_engine()
+        self._buffers()
+        H, W = self._net_hw
+        spare = []
+        if not self._started:
+            taken = {p for p, _ in assign}
+            spare = [p for p in range(P) if p not in taken]
+        rows, imgs, masks, gaps = [], [], [], []
+        with torch.cuda.stream(eng.stream):
+            s = eng.stream.cuda_stream
+            for j, (p, c) in enumerate(assign):
+                if c.ready is not None:
+                    eng.stream.wait_event(c.ready)
+                if c.host_u8:
+                    hs, ws = self._src_hw
+                    _load_frames(self._stage[p:p + 1], c.frames, 0, 1, s)
+                    ops.run(ops.ingest_rgb8(self._stage[p], Hs=hs, Ws=ws, Hd=H, Wd=W, out_chw=self._first[p]), s)
+                    img = self._first[p]
+                else:
+                    img = c.frames[0]
+                mask = c.mask.reshape(1, H, W).float().contiguous()
+                mine = [p] + (spare if j == 0 else [])
+                rows.append(mine); imgs.append(img); masks.append(mask); gaps.append(c.gap)
+                if self.flip:                                   # the twin: frame and first mask at the network size, THEN mirrored
+                    self._mirror(img, self._twin_img[p], s)
+                    self._mirror(mask, self._twin_mask[p], s)
+                    rows.append([P + q for q in mine]); imgs.append(self._twin_img[p]); masks.append(self._twin_mask[p]); gaps.append(c.gap)
+                row = self._rows[p]
+                row.clip, row.i, row.live = c, 1, True
+        eng.start_clips(rows, imgs, masks, gaps)
+        self.frames_encoded += len(rows)
+        if spare:
+            eng.finish_clips(spare + ([P + q for q in spare] if self.flip else []))
+        self._started = True
+
+    def _take(self, p: int) -> Optional[_RaggedClip]:
+        """The next queued clip for row p (None: queue dry)."""
+        if not self._queue:
+            return None
+        if self._rows[p].clip is not None:
+            self.refills += 1
+        return self._queue.pop(0)
+
+    # ------------------------------------------------------------------ look-ahead encoder
+    def _kick(self, buf: int, plan):
+        """Encode look-ahead batch ``plan`` ({row: (clip, first frame, new)}) into buffer ``buf`` on the engine's side stream: frames
+        first .. first + lookahead - 1 of each planned row (beyond the clip's end its last frame again: encoded, never used); rows
+        without a plan name the slot's own idle frame (uint8 sources: keep what their input rows hold).  frames_encoded counts as
+        GroupSlot does: every row of the group for each frame index of the batch that some row needs."""
+        eng, B, P = self.engine, self.B, self.clips
+        la, es = eng.lookahead, eng.enc_stream.cuda_stream
+        enc = eng.rt.enc_bufs[buf]
+        H, W = self._net_hw
+        for c, _, is_new in plan.values():
+            if is_new and c.ready is not None:                  # the first time this stream touches the clip
+                eng.enc_stream.wait_event(c.ready)
+        self.frames_encoded += B * max(min(la, c.n - i) for c, i, _ in plan.values())
+        if self._src_hw is not None:
+            enc.point_at_img_in(es)
+            dst = eng.encode_inputs(buf)
+            if not self._inputs_zeroed:                         # rows that are never ingested into must still hold numbers
+                with torch.cuda.stream(eng.enc_stream):       # (on the encoder stream, ahead of the ingests that follow)
+                    for b in eng.rt.enc_bufs:
+                        b.img_in.zero_()
+                self._inputs_zeroed = True
+            hs, ws = self._src_hw
+            for p, (c, i, _) in plan.items():
+                m = min(la, c.n - i)
+                _load_frames(self._stage_la[p * la:p * la + m], c.frames, i, m, es)
+                ops.run([ops.ingest_rgb8(self._stage_la[p * la + k], Hs=hs, Ws=ws, Hd=H, Wd=W, out_chw=dst[k * B + p]) for k in range(m)], es)
+            if self.flip:
+                for k in range(la):
+                    self._mirror(dst[k * B:k * B + P], dst[k * B + P:(k + 1) * B], es)
+        else:
+            rows = [[None] * B for _ in range(la)]
+            for p in range(P):
+                if p not in plan:
+                    for k in range(la):
+                        rows[k][p] = self._idle_frame
+                        if self.flip:
+                            rows[k][P + p] = self._idle_frame
+                    continue
+                c, i, _ = plan[p]
+                m = min(la, c.n - i)
+                for k in range(la):
+                    rows[k][p] = c.frames[min(i + k, c.n - 1)]
+                if self.flip:
+                    # the twin's frames of this batch, mirrored on the encoder stream into this buffer's staging rows; they are read by
+                    # the encoder launch that follows and rewritten on this stream only after it
+                    st = self._twin_stage[buf]
+                    self._mirror(c.frames[i:i + m], st[p, :m], es)
+                    for k in range(la):
+                        rows[k][P + p] = st[p, min(k, m - 1)]
+            enc.set_frames([f for r in rows for f in r], es)
+        eng.encode_ahead(buf)
+
+    def _boundary(self):
+        """Look-ahead batch boundary: the clips planned for this batch start in their rows (cold: the rows are filled from the queue
+        and the batch is encoded now), then the NEXT batch is planned -- rows that run on get their next frames, rows that end
+        inside this batch (or idle) get the next queued clips' frames 1..lookahead -- and kicked."""
+        eng, la = self.engine, self.engine.lookahead
+        self._e = 0
+        plan = self._plan
+        cold = not plan
+        if cold:
+            plan = {}
+            for p in range(self.clips):
+                c = None if self._rows[p].live else self._take(p)
+                if c is not None:
+                    plan[p] = (c, 1, True)
+            if not plan:
+                return
+        new = [(p, c) for p, (c, _, is_new) in plan.items() if is_new]
+        if new:
+            self._start(new)
+        self._k += 1
+        if cold:
+            self._kick(self._k % 2, plan)
+        nxt = {}
+        for p, row in enumerate(self._rows):
+            if row.live and row.i + la < row.clip.n:
+                nxt[p] = (row.clip, row.i + la, False)
+            else:
+                c = self._take(p)
+                if c is not None:
+                    nxt[p] = (c, 1, True)
+        self._plan = nxt or None
+        if nxt:
+            self._kick((self._k + 1) % 2, nxt)
+
+    # ------------------------------------------------------------------ one frame of every live row
+    def step(self, feed=None) -> List[FinishedClip]:
+        """Every live row advances one frame: propagate, route the labels, update the memories.  feed: {clip_id: uint8 [Ho, Wo] device
+        labels that go into that clip's memory update INSTEAD of the prediction} (the delivered labels stay the prediction).
+        -> the clips that ended with this step."""
+        eng, B, P = self.engine, self.B, self.clips
+        la = eng.lookahead
+        out: List[FinishedClip] = []
+        self._release()
+        for c in self._trivial:
+            out.append(FinishedClip(c.id, c.labels, None, [0], []))
+        self._trivial = []
+        live = [p for p, r in enumerate(self._rows) if r.live]
+        if la > 1:
+            if self._e == 0 or not live:
+                self._boundary()
+        else:
+            new = []
+            for p, r in enumerate(self._rows):
+                if not r.live:
+                    c = self._take(p)
+                    if c is not None:
+                        new.append((p, c))
+            if new:
+                self._start(new)
+        live = [p for p, r in enumerate(self._rows) if r.live]
+        if not live:
+            return out
+        s = eng.stream.cuda_stream
+        H, W = self._net_hw
+        if la > 1:
+            eng.propagate_to_labels(self.cur_label, enc_slot=(self._k % 2) * la + self._e)
+            self._e = (self._e + 1) % la
+        else:
+            nb = 3 * H * W * 4
+            for p in live:
+                r = self._rows[p]
+                if r.clip.host_u8:
+                    hs, ws = self._src_hw
+                    _load_frames(self._stage[p:p + 1], r.clip.frames, r.i, 1, s)
+                    ops.run(ops.ingest_rgb8(self._stage[p], Hs=hs, Ws=ws, Hd=H, Wd=W, out_chw=self._first[p]), s)
+                else:
+                    ops.copy_async(self._first[p], r.clip.frames[r.i], nb)(s)
+            if self.flip:
+                self._mirror(self._first[:P], self._first[P:], s)
+            self.frames_encoded += B
+            eng.propagate_to_labels(self.cur_label, imgs=self._first)
+        self.row_steps_live += len(live)
+        self.row_steps_idle += P - len(live)
+        # ---- one launch routes every row's labels
+        routes, inject = [], []
+        for p, r in enumerate(self._rows):
+            if not r.live:
+                routes.append((None, None, None, -1, _lib.ROUTE_IDLE))
+                continue
+            ov = r.clip.new_objects.get(r.i)
+            fd = feed.get(r.clip.id) if feed else None
+            if ov is not None:
+                inject.append(p)
+            twin = P + p if self.flip and (ov is not None or fd is not None) else -1      # else the pair kernel wrote the twin's row
+            routes.append((r.clip.labels[r.i], ov, fd, twin, _lib.ROUTE_LIVE))
+        if self.flip:
+            routes += [(None, None, None, -1, _lib.ROUTE_SKIP if r.live else _lib.ROUTE_IDLE) for r in self._rows]
+        self.routes.upload(routes, s)
+        self.routes.op(s)
+        eng.update_from_labels(self.cur_label, skip=inject + [P + p for p in inject] if self.flip else inject)
+        for p in inject:                          # the frame is re-added as a reference frame for that row (evaluator.py:484-508)
+            r = self._rows[p]
+            eng.add_reference_frame_for(p, r.clip.frames[r.i], self.cur_label[p])
+            if self.flip:
+                self._mirror(r.clip.frames[r.i], self._twin_img[p], s)
+                eng.add_reference_frame_for(P + p, self._twin_img[p], self.cur_label[P + p])
+        ended = []
+        for p in live:
+            r = self._rows[p]
+            r.i += 1
+            if r.i >= r.clip.n:
+                ended.append(p)
+        if ended:
+            traces = eng.finish_clips(ended + ([P + p for p in ended] if self.flip else []))
+            ev = torch.cuda.Event()
+            ev.record(eng.stream)
+            ee = torch.cuda.Event()
+            ee.record(eng.enc_stream)
+            for j, p in enumerate(ended):
+                r = self._rows[p]
+                r.live = False
+                idx, drops = traces[j]
+                out.append(FinishedClip(r.clip.id, r.clip.labels, ev, idx, drops, traces[len(ended) + j] if self.flip else None))
+                self._retired.append(((ev, ee), r.clip))
+        return out

@@ -348,3 +348,36 @@ class SequenceEvaluator:
                         e.update_memory(resized(label_f, e.input_size_2d, fl))
             outs.append(label_u8)
         return outs
+
+
+def run_clips(model, clips, rows: int = 8, lookahead: int = 4, flip: bool = False, out_hw: Optional[Tuple[int, int]] = None):
+    """A clip list of ANY lengths at group speed: one GroupEngine of ``rows`` rows and one clip_runner.RaggedGroupSlot; a clip
+    moves into a row as soon as the row's clip has ended (at most ``lookahead`` - 1 frames later).  clips: an iterable of
+    (clip_id, frames, first_label, new_objects) -- frames fp32 [n, 3, H, W] on the device at the network size or uint8
+    [n, Hs, Ws, 3] in pinned host memory, first_label [1, 1, H, W] fp32 label map at the network size, new_objects None or
+    {frame index: uint8 [Ho, Wo] device map}.  All clips share the network size.  out_hw: the size of the delivered label maps
+    (default: the network size; uint8 frames: the frames' size).  flip: flip testing, ``rows`` clips and their mirrored twins in
+    a group of 2 * rows.  Yields (clip_id, labels uint8 [n, Ho, Wo] on the device, row 0 zero) as clips finish, in the order they
+    finish; the current stream has been made to wait for the clip's last frame, so the stack can be scored / saved right away
+    while the group runs on."""
+    from .clip_runner import RaggedGroupSlot
+    from .networks.engines.group_engine import GroupEngine
+    it = iter(clips)
+    head = next(it, None)
+    if head is None:
+        return
+    dev = torch.device('cuda', 0)
+    if out_hw is None:
+        out_hw = tuple(head[1].shape[1:3]) if head[1].dtype == torch.uint8 else tuple(head[2].shape[-2:])
+    eng = GroupEngine(model, 2 * rows if flip else rows, 0, lookahead=lookahead, flip_tta=flip)
+    slot = RaggedGroupSlot(eng, out_hw, dev)
+
+    def every():
+        yield head
+        yield from it
+
+    for fin in slot.run(every()):
+        if fin.event is not None:
+            torch.cuda.current_stream(dev).wait_event(fin.event)
+        yield fin.clip_id, fin.labels
+    eng.synchronize()

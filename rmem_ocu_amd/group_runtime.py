@@ -17,8 +17,8 @@ The lists are pure functions of the buffers' addresses, so each one is built onc
 hipGraph).  Everything that changes from frame to frame (slot table, temporal-PE slots, append slots) lives in device memory.
 
 At HW = 1674 tokens a launch costs about as much as its arithmetic and only four kernels are in flight on the GPU
-(DESIGN.md §7b), so the throughput path does not run one clip per launch list: B clips of equal length share one
-``GroupRuntime``.  Every activation buffer has a leading clip dimension ([B * rows, C], clip-major), which turns
+(DESIGN.md §7b), so the throughput path does not run one clip per launch list: the B rows of a group (clips of equal length
+under clip_runner.GroupSlot, of any lengths under RaggedGroupSlot) share one ``GroupRuntime``.  Every activation buffer has a leading clip dimension ([B * rows, C], clip-major), which turns
 
     every linear / LayerNorm / add      into the same launch over B * HW rows,
     every convolution                   into one launch over a batch of B images (rmem_conv_desc.batch),
@@ -28,8 +28,8 @@ At HW = 1674 tokens a launch costs about as much as its arithmetic and only four
 The clips are independent; what differs between them is the memory bank's content and, after evictions, its slot order:
 the bank is [B * slots, HW, 256] per layer, clip c owns slots c * S .. c * S + S - 1, the chunk table has one block of rows
 per clip, and appends go through a device table of destination slots (rmem_scatter_blocks), so ONE captured hipGraph per
-bank size serves the whole group.  Frame counters, append schedule and bank size T are the same for all clips of a group
-(equal length => same gap, evaluator.py:330-335); the eviction decision is per clip (engines/group_engine.py).
+bank size serves the whole group.  The launches are laid out for the longest bank T; frame counters, gaps, append schedule and
+the eviction decision are host state per row (bank_schedule.BankSchedule, engines/group_engine.py).
 """
 from __future__ import annotations
 

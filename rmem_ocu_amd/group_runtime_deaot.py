@@ -18,7 +18,7 @@ with one GEMM.  The bank stores what the reference concatenates at read time: K 
 previous frame.  Appends go through the device table of destination slots (rmem_scatter_blocks) exactly as in GroupRuntime, so
 one captured graph per bank size serves every frame.
 
-As in group_runtime.GroupRuntime, B clips of equal length share one set of launch lists, so a frame of the whole group costs the
+As in group_runtime.GroupRuntime, the B rows of a group share one set of launch lists, so a frame of the whole group costs the
 host one hipGraph launch:
 
     every linear / LayerNorm / copy         one launch over B * HW rows (weights are shared, rows are independent);

@@ -1,10 +1,20 @@
-"""Throughput engine: B clips of equal length advance in lockstep through ONE set of launch lists.
+"""Throughput engine: the B rows of a group advance in lockstep through ONE set of launch lists.
+
+The rows need not run clips of equal length.  The device side never asked for it: banks of different sizes share a key table
+(rows padded with key_count 0), appends go through a per-row destination table, and one row can be restarted from a reference
+frame while the others carry on (add_reference_frame_for).  ``start_clips`` is the per-row counterpart of
+add_reference_frames: a NEW clip moves into a row, with its own frame counter and gap (bank_schedule.BankSchedule.start_clips),
+while the other rows keep going; ``finish_clips`` hands out an ended clip's bank traces and leaves the row idle (its bank cut to
+one frozen entry: never appended to, never scored, never part of T) until the next clip moves in.
+clip_runner.RaggedGroupSlot drives a clip list of any lengths through a group this way (continuous batching); equal length is a
+precondition of clip_runner.GroupSlot only, which starts all rows together with one shared frame counter and gap.
 
 ``GroupEngine`` is the batched counterpart of AOTEngine/AOTInferEngine (aot_engine.py) for clips with <= 10 objects whose
 label masks are fed back.  Per clip it keeps exactly the host state AOTEngine keeps -- bank slot order,
 ``long_memories_indexes``, the eviction policy's EMA scores and visit counts (networks/layers/transformer.py:338-411), the
 frame of the last long-term update (aot_engine.py:338-343), all in one rmem_ocu_amd.bank_schedule.BankSchedule with
-clips = B -- while the frame counter is shared, because clips of one length get one gap (managers/evaluator.py:330-335).
+clips = B.  Rows started together (add_reference_frames) share the engine's frame counter and gap, as clips of one length do
+(managers/evaluator.py:330-335); rows started one by one (start_clips) count their own frames.
 All device work goes through rmem_ocu_amd.group_runtime.GroupRuntime: one launch per layer for the whole group.
 
 Covered protocols (the reference's evaluator, managers/evaluator.py:385-523):
@@ -68,6 +78,7 @@ class GroupEngine:
         self.use_graphs = True
         self.rt: Optional[GroupRuntime] = None
         self._side: Optional[GroupRuntime] = None
+        self._start_mask: Optional[torch.Tensor] = None      # start_clips: the first mask of the clip being started
         self._graphs = ops.GraphCache()
         self.bank = BankSchedule(self, clips)
         self.restart_engine()
@@ -92,6 +103,7 @@ class GroupEngine:
         slots = bank_slots(self.bank.n_keep)
         if self.rt is None or (self.rt.H, self.rt.W) != (H, W) or self.rt.S != slots:
             self.rt = runtime_for(self.AOT, (H, W), slots, self.device, self.B, self.lookahead)
+            self._start_mask = None
             self.label_in = torch.empty(self.B, H, W, dtype=F32, device=self.device)
             self._graphs = ops.GraphCache()
             self._side = None
@@ -123,26 +135,67 @@ class GroupEngine:
         one-clip runtime of the group's class in reference mode (the same launch lists with clips = 1); its K / V become the clip's
         only bank entry and its short-term memory, the clip's long-term schedule restarts here, ``long_memories_indexes`` keeps
         growing (the reference's quirk, 323), the eviction policy's state is reset (init_memory, transformer.py:438-443)."""
-        rt, c = self.rt, clip
+        with torch.cuda.stream(self.stream):
+            src = self._side_reference(img, label_u8)
+            # the clip's bank := this frame only (aot_engine.py:322), short-term memory := this frame's (transformer.py:675-678)
+            new = self.bank.start_reference(self.rt, [clip], append_table=False)[clip]      # the entry is copied in, not appended by a launch
+            self._adopt_side_entry(clip, new, src)
+
+    def _side_reference(self, img: torch.Tensor, label: torch.Tensor) -> int:
+        """One frame through the one-clip side runtime in reference mode on the engine's stream (img fp32 [3, H, W], label uint8 or
+        fp32 [hs, ws] at a FIXED address) -> the side bank slot that holds its K / V; its short-term memory is side.short_K / V."""
+        rt = self.rt
         if self._side is None:
             self._side = runtime_for(self.AOT, (rt.H, rt.W), 1, self.device, 1, 1)         # one bank slot, one clip, no look-ahead
-        side = self._side
-        hs, ws = int(label_u8.shape[-2]), int(label_u8.shape[-1])
-        L = rt.L
+        side, s = self._side, self._s()
+        hs, ws = int(label.shape[-2]), int(label.shape[-1])
+        ops.copy_async(side.enc_now.img_in, img.contiguous(), 3 * rt.H * rt.W * 4)(s)
+        side.prepare_pos(s)
+        src = BankSchedule.restart_banks(side, [0], s)[0]
+        ops.run(side.prog_encode() + side.prog_id_emb(label, hs, ws) + side.prog_project(None) + side.prog_lstt(True, 1), s)
+        return src
+
+    def _adopt_side_entry(self, c: int, new: int, src: int):
+        """Row c's bank slot ``new`` and short-term memory := the side runtime's reference frame (stream-ordered copies)."""
+        rt, side, s, L = self.rt, self._side, self._s(), self.rt.L
+        for i in range(rt.NL):
+            nk, nv = L * rt.bank_kw * 2, L * rt.bank_vw * 2          # bytes of one bank entry's keys / values
+            ops.copy_async(rt.bank_K[i][c * rt.S + new], side.bank_K[i][src], nk)(s)
+            ops.copy_async(rt.bank_V[i][c * rt.S + new], side.bank_V[i][src], nv)(s)
+            ops.copy_async(rt.short_K[i][c * L:(c + 1) * L], side.short_K[i], nk)(s)
+            ops.copy_async(rt.short_V[i][c * L:(c + 1) * L], side.short_V[i], nv)(s)
+
+    # ------------------------------------------------------------------ ragged groups: a new clip per row
+    def start_clips(self, rows: List[List[int]], imgs: List[torch.Tensor], masks: List[torch.Tensor], gaps: List[int]):
+        """Per-row counterpart of add_reference_frames: clip j starts in the rows ``rows[j]`` (one row; several when the same clip
+        fills rows that would otherwise never have held a bank entry) while the other rows carry on.  imgs[j] fp32 [3, H, W] and
+        masks[j] fp32 [H, W] label map, both at the network size; gaps[j] the clip's long_term_mem_gap.  With flip_tta the caller
+        passes a clip for row p and its mirrored twin (frame and mask resized, THEN mirrored) for row P + p in the same call.  The
+        frame runs through the one-clip side runtime (add_reference_frame_for's machinery); the rows' index lists, drop traces,
+        policies and frame counters start over (BankSchedule.start_clips), which is what tells a new clip from a mid-clip
+        reference frame."""
+        H, W = int(imgs[0].shape[-2]), int(imgs[0].shape[-1])
+        rt = self._ensure_runtime(H, W)
+        self.obj_nums = [self.max_obj_num]            # AOTInferEngine forces this (aot_engine.py:697)
+        if self._start_mask is None or tuple(self._start_mask.shape) != (H, W):
+            # fixed address: the side launch list names it.  empty, not zeros: every byte is written on the engine's stream before
+            # it is read there, and a fill enqueued on the caller's stream would not be ordered against that copy
+            self._start_mask = torch.empty(H, W, dtype=F32, device=self.device)
         with torch.cuda.stream(self.stream):
             s = self._s()
-            ops.copy_async(side.enc_now.img_in, img.contiguous(), 3 * rt.H * rt.W * 4)(s)
-            side.prepare_pos(s)
-            src = BankSchedule.restart_banks(side, [0], s)[0]
-            ops.run(side.prog_encode() + side.prog_id_emb(label_u8, hs, ws) + side.prog_project(None) + side.prog_lstt(True, 1), s)
-            # the clip's bank := this frame only (aot_engine.py:322), short-term memory := this frame's (transformer.py:675-678)
-            new = self.bank.start_reference(rt, [c], append_table=False)[c]      # the entry is copied in, not appended by a launch
-            for i in range(rt.NL):
-                nk, nv = L * rt.bank_kw * 2, L * rt.bank_vw * 2          # bytes of one bank entry's keys / values
-                ops.copy_async(rt.bank_K[i][c * rt.S + new], side.bank_K[i][src], nk)(s)
-                ops.copy_async(rt.bank_V[i][c * rt.S + new], side.bank_V[i][src], nv)(s)
-                ops.copy_async(rt.short_K[i][c * L:(c + 1) * L], side.short_K[i], nk)(s)
-                ops.copy_async(rt.short_V[i][c * L:(c + 1) * L], side.short_V[i], nv)(s)
+            rt.prepare_pos(s)
+            flat = [r for rs in rows for r in rs]
+            first = self.bank.start_clips(rt, flat, [g for rs, g in zip(rows, gaps) for _ in rs])
+            for rs, img, mask in zip(rows, imgs, masks):
+                ops.copy_async(self._start_mask, mask.reshape(H, W).contiguous(), H * W * 4)(s)
+                src = self._side_reference(img, self._start_mask)
+                for r in rs:
+                    self._adopt_side_entry(r, first[r], src)
+
+    def finish_clips(self, rows: List[int]):
+        """The clips of ``rows`` have ended -> [(long_memories_indexes, drop_trace)]; the rows idle until start_clips."""
+        with torch.cuda.stream(self.stream):
+            return self.bank.finish_clips(self.rt, rows)
 
     # ------------------------------------------------------------------ look-ahead encoder
     def encode_inputs(self, buf: int = 0) -> torch.Tensor:
@@ -165,6 +218,7 @@ class GroupEngine:
         """labels_u8: uint8 [B, Ho, Wo] device buffer at a fixed address.  Either enc_slot (frame encoded by encode_ahead) or
         imgs [B, 3, H, W] (encoded now).  flip_tta: rows p and B/2 + p are merged; row p gets the label, row B/2 + p its mirror."""
         self.frame_step += 1
+        self.bank.advance()                           # rows started by start_clips count their own frames
         rt, B = self.rt, self.B
         T, wm = self.bank.begin_propagation(rt)
         Ho, Wo = int(labels_u8.shape[-2]), int(labels_u8.shape[-1])

@@ -604,6 +604,57 @@ class PinnedRing:
         ev.record(torch.cuda.ExternalStream(stream, device=self.device))
 
 
+class LabelRoutes:
+    """The device table of rmem_route_labels for a group of ``rows`` label rows [rows, Ho, Wo] (uint8, in place) and the launch
+    over it.  ``upload`` takes one entry per row, (dst, overlay, feed, twin, mode) with uint8 [Ho, Wo] device tensors or None and
+    mode one of _lib.ROUTE_LIVE / ROUTE_IDLE / ROUTE_SKIP, checks them on the host and sends them through a PinnedRing (a staging row
+    is rewritten only after the copy that read it has executed); ``op`` is the launch, the same every step."""
+
+    def __init__(self, rows_u8: torch.Tensor, device):
+        _dev(rows_u8)
+        if rows_u8.dtype != torch.uint8 or rows_u8.dim() != 3 or not rows_u8.is_contiguous():
+            raise RmemError('LabelRoutes: rows_u8 must be a contiguous uint8 [rows, Ho, Wo] tensor')
+        self.rows, self.Ho, self.Wo = (int(v) for v in rows_u8.shape)
+        self.rows_u8 = rows_u8
+        self.table = torch.zeros(self.rows, 4, dtype=torch.int64, device=device)       # rmem_label_route: 3 pointers, (twin, mode)
+        self.ring = PinnedRing(4, (self.rows, 4), torch.int64, device)
+        self.op = route_labels(rows_u8, self.table, rows=self.rows, Ho=self.Ho, Wo=self.Wo)
+
+    def _map(self, t, what: str) -> int:
+        if t is None:
+            return 0
+        _dev(t)
+        if t.dtype != torch.uint8 or not t.is_contiguous() or t.numel() != self.Ho * self.Wo:
+            raise RmemError(f'LabelRoutes: {what} must be a contiguous uint8 map of {self.Ho} x {self.Wo}')
+        return t.data_ptr()
+
+    def upload(self, routes: Sequence, stream: int):
+        if len(routes) != self.rows:
+            raise RmemError(f'LabelRoutes: {self.rows} rows, got {len(routes)} entries')
+        modes = [int(r[4]) for r in routes]
+        host = self.ring.next()
+        for i, (dst, overlay, feed, twin, mode) in enumerate(routes):
+            twin = int(twin)
+            if mode not in (_lib.ROUTE_LIVE, _lib.ROUTE_IDLE, _lib.ROUTE_SKIP):
+                raise RmemError(f'LabelRoutes: row {i}: mode {mode}')
+            if twin >= 0 and (twin >= self.rows or twin == i or modes[twin] != _lib.ROUTE_SKIP):
+                raise RmemError(f'LabelRoutes: row {i}: twin {twin} must be another row of the group whose own entry has mode 2')
+            host[i, 0], host[i, 1], host[i, 2] = self._map(dst, 'dst'), self._map(overlay, 'overlay'), self._map(feed, 'feed')
+            host[i, 3] = (twin & 0xffffffff) | (int(mode) << 32)
+        self.ring.upload(self.table, self.rows * 32, stream)
+
+
+def route_labels(rows_u8, table, *, rows, Ho, Wo) -> Op:
+    """rmem_route_labels over uint8 [rows, Ho * Wo] label rows (in place) and a device table of ``rows`` rmem_label_route entries
+    (int64 [rows, 4]: dst, overlay, feed, twin | mode << 32); LabelRoutes fills the table."""
+    if rows <= 0 or Ho <= 0 or Wo <= 0:
+        raise RmemError(f'route_labels: rows, Ho and Wo must be positive (got {rows}, {Ho}, {Wo})')
+    _dev(rows_u8, table)
+    assert rows_u8.dtype == torch.uint8 and rows_u8.is_contiguous() and rows_u8.numel() >= rows * Ho * Wo
+    assert table.dtype == torch.int64 and table.is_contiguous() and table.numel() >= rows * 4
+    return Op(_lib.lib().rmem_route_labels, (_ptr(rows_u8), rows, Ho, Wo, _ptr(table)), 'rmem_route_labels', (rows_u8, table))
+
+
 def scatter_blocks(src, dst, slots, *, nclips, block_bytes, slot_bytes) -> Op:
     """block c of src -> dst + slots[c] * slot_bytes (slots: device int32 table, negative = skip)."""
     _dev(src, dst, slots)
