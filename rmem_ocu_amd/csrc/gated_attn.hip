@@ -626,6 +626,18 @@ __device__ __forceinline__ void gp_select_clip(GpCombine& p, int clip) {
   if (p.mass) p.mass += clip * p.mass_cs;
 }
 
+// The gated value's store rounding, the same function in both combine kernels: the product rounded to fp32, then to e16.  Left to
+// the compiler, the half flavour folds the last multiply into v_fma_mixlo/hi_f16 for some of a thread's 8 columns and converts the
+// others with v_cvt_pk_f16_f32 -- a different choice in each kernel, and on MI355X the fused depth-wise path then was not
+// bit-identical to k_gp_combine + rmem_dwconv5x5 (test_gated_attn_clips_vs_reference[empty-groups-float16]).  The empty asm keeps
+// the product out of the conversion's pattern; bfloat16 has no such instruction and compiles as before.
+__device__ __forceinline__ e16 gp_store_round(float x) {
+#ifdef RMEM_F16
+  asm("" : "+v"(x));
+#endif
+  return (e16)x;
+}
+
 // out[q, c] = (sum_g slab[g][q][c]) / l[q] * U[q][c]; thread = 8 columns of one query
 __global__ __launch_bounds__(256) void k_gp_combine(GpCombine p) {
   gp_select_clip(p, blockIdx.z);
@@ -647,14 +659,14 @@ __global__ __launch_bounds__(256) void k_gp_combine(GpCombine p) {
   if (c < p.usplit) {
     const e16x8 u = *reinterpret_cast<const e16x8*>(p.ua + (long)q * p.ldua + c);
 #pragma unroll
-    for (int j = 0; j < 8; ++j) o[j] = (e16)(v[j] * inv * (float)u[j]);
+    for (int j = 0; j < 8; ++j) o[j] = gp_store_round(v[j] * inv * (float)u[j]);
   } else if (p.ub) {
     const e16x8 u = *reinterpret_cast<const e16x8*>(p.ub + (long)q * p.ldub + (c - p.usplit));
 #pragma unroll
-    for (int j = 0; j < 8; ++j) o[j] = (e16)(v[j] * inv * (float)u[j]);
+    for (int j = 0; j < 8; ++j) o[j] = gp_store_round(v[j] * inv * (float)u[j]);
   } else {                                          // torch.ones_like(curr_U) half of layer 0 (transformer.py:1117-1118)
 #pragma unroll
-    for (int j = 0; j < 8; ++j) o[j] = (e16)(v[j] * inv);
+    for (int j = 0; j < 8; ++j) o[j] = gp_store_round(v[j] * inv);
   }
   *reinterpret_cast<e16x8*>(p.out + (long)q * p.ldo + c) = o;
 }
@@ -706,10 +718,10 @@ __global__ __launch_bounds__(256) void k_gp_combine_dwconv(GpCombine p) {
       if (up) {
         const e16x8 u = *reinterpret_cast<const e16x8*>(up + (long)q * ldu + ch8 * 8);
 #pragma unroll
-        for (int j = 0; j < 8; ++j) o[j] = (e16)(v[j] * inv * (float)u[j]);
+        for (int j = 0; j < 8; ++j) o[j] = gp_store_round(v[j] * inv * (float)u[j]);
       } else {
 #pragma unroll
-        for (int j = 0; j < 8; ++j) o[j] = (e16)(v[j] * inv);
+        for (int j = 0; j < 8; ++j) o[j] = gp_store_round(v[j] * inv);
       }
     }
     *reinterpret_cast<e16x8*>(&tile[pix * CT_C + ch8 * 8]) = o;

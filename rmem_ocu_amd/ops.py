@@ -678,6 +678,15 @@ def gated_workspace(Lq: int, DV: int, frames: int, keys_per_frame: int, nchunks:
     return torch.empty(nclips * n // 4 + 64, dtype=F32, device=device)
 
 
+def _gated_extent(who, nclips, rows, operands):
+    """[clip][rows][ld] operands of the gated attentions: the last element a launch touches, (nclips * rows - 1) * ld + width, must
+    exist -- the kernels index from the clip count alone, a short buffer would be read or written past its end."""
+    for name, t, ld, width in operands:
+        if t is not None and t.numel() < ((nclips - 1) * rows + rows - 1) * ld + width:
+            raise RmemError(f'{who}: {name} has {t.numel()} elements, {nclips} clip(s) of {rows} rows with row stride {ld} and '
+                            f'{width} columns need {((nclips - 1) * rows + rows - 1) * ld + width}')
+
+
 def gated_attn(q, k_bank, v_bank, u_a, out, workspace, *, Lq, DV, ldq, ldk, ldv, ldua, ldo, k_slot_stride=0, v_slot_stride=0,
                chunks=None, nchunks=1, frames=1, keys_per_frame, pe_cur=None, pe_mem=None, u_b=None, ldub=0, usplit=None,
                mass=None, dw=None, H=0, W=0, nclips=1) -> Op:
@@ -689,8 +698,11 @@ def gated_attn(q, k_bank, v_bank, u_a, out, workspace, *, Lq, DV, ldq, ldk, ldv,
     assert workspace.numel() * 4 >= nclips * _lib.lib().rmem_gated_attn_workspace_bytes(Lq, DV, frames, keys_per_frame, nchunks)
     assert chunks is None or (chunks.dtype == torch.int32 and chunks.numel() >= nclips * nchunks * 8)
     assert mass is None or (mass.dtype == F32 and mass.numel() >= nclips * Lq * frames)
-    assert out.numel() >= ((nclips - 1) * Lq + Lq - 1) * ldo + DV
     usplit = DV if usplit is None else usplit
+    _gated_extent('gated_attn', nclips, Lq, (('out', out, ldo, DV), ('q', q, ldq, 128), ('u_a', u_a, ldua, usplit),
+                                             ('u_b', u_b, ldub, DV - usplit)))
+    if chunks is None:      # one key frame per clip, [clip][keys][ld]; with a table the bank is addressed through its slots
+        _gated_extent('gated_attn', nclips, keys_per_frame, (('k', k_bank, ldk, 128), ('v', v_bank, ldv, DV)))
     args = (_ptr(q), ldq, _ptr(k_bank), k_slot_stride, ldk, _ptr(v_bank), v_slot_stride, ldv, _ptr(chunks), nchunks, frames,
             keys_per_frame, _ptr(pe_cur), _ptr(pe_mem), Lq, DV, _ptr(u_a), ldua, _ptr(u_b), ldub, usplit, _ptr(out), ldo,
             _ptr(mass), _ptr(dw), H, W, nclips, _ptr(workspace))
@@ -707,6 +719,8 @@ def local_gated_attn(q, k, v, rel, u_a, out, workspace, *, H, W, DV, ldq, ldk, l
     assert all(t.dtype == dt for t in (q, k, v, u_a, out)) and rel.dtype == F32
     assert workspace.numel() * 4 >= nclips * _lib.lib().rmem_gated_attn_workspace_bytes(H * W, DV, 1, H * W, 8)
     usplit = DV if usplit is None else usplit
+    _gated_extent('local_gated_attn', nclips, H * W, (('q', q, ldq, 128), ('k', k, ldk, 128), ('v', v, ldv, DV), ('rel', rel, ldrel, 225),
+                                                      ('u_a', u_a, ldua, usplit), ('u_b', u_b, ldub, DV - usplit), ('out', out, ldo, DV)))
     args = (_ptr(q), ldq, _ptr(k), ldk, _ptr(v), ldv, _ptr(rel), ldrel, H, W, DV, _ptr(u_a), ldua, _ptr(u_b), ldub, usplit,
             _ptr(out), ldo, _ptr(dw), nclips, _ptr(workspace))
     return Op(_fn('rmem_local_gated_attn_clips', dt), args, 'rmem_local_gated_attn', (q, k, v, rel, u_a, u_b, out, workspace, dw))

@@ -1,5 +1,6 @@
 """GPU parity of the DeAOT kernels (gated propagation attention, 15x15 local flavour, SiLU / column-range GEMM epilogues)
-against the reference's golden vectors (tests/golden/deaot_ops.npz), the CPU oracle and torch fp32 primitives."""
+against the reference's golden vectors (tests/golden/deaot_ops.npz), the CPU oracle and torch fp32 primitives; the clip dimension,
+the half flavour, the launch plans of larger clip counts and a dirty workspace against the float64 references of tests/gated_ref.py."""
 import math
 import os
 
@@ -8,12 +9,14 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+import gated_ref as G
 from conftest import GOLDEN
+from gated_ref import DV, LOCAL_CASES, LONG_CASES, MASS_TOL, SELF_CASES, TOL
 from test_hip_ops import assert_close, rb, seeded
 
 pytestmark = pytest.mark.gpu
 
-BF16, F32 = torch.bfloat16, torch.float32
+BF16, F16, F32 = torch.bfloat16, torch.float16, torch.float32
 
 
 @pytest.fixture(scope='module')
@@ -294,3 +297,269 @@ def test_gated_attn_fused_dwconv_is_bit_identical(dev, h, wd):
     ops.run(ops.gated_attn(*args, c, ws, dw=dw, H=h, W=wd, **common))
     torch.cuda.synchronize()
     assert torch.equal(b, c)
+
+
+# ------------------------------------------------------------------ clips, half flavour, plan variants, dirty workspace
+# Inputs and float64 references come from tests/gated_ref.py (tests/test_gated_ref_host.py checks both on the CPU); every clip is
+# compared with assert_close on its own, so a wrong clip cannot hide behind another clip's scale.
+NAN = float('nan')
+_refs = {}
+
+
+def cached_ref(key, make):
+    """A case's reference, computed once and shared by the tests that launch the case (never modified)."""
+    if key not in _refs:
+        _refs[key] = make()
+    return _refs[key]
+
+
+def clips_close(got, ref, tol, what):
+    worst = max(((got[c].double() - ref[c]).abs().max() / ref[c].abs().max()).item() for c in range(len(ref)))
+    print(f'{what}: worst clip max err / max |ref| = {worst:.3g} (bound {tol})')
+    for c in range(len(ref)):
+        assert_close(got[c], ref[c], tol, f'{what}, clip {c}')
+
+
+def case_dts(cases):
+    """Every case in bfloat16; the 3-clip cases in IEEE half too."""
+    return [pytest.param(c, dt, id=f'{c.name}-{str(dt)[6:]}') for c in cases for dt in (BF16, F16) if dt is BF16 or c.clips == 3]
+
+
+def long_ref(dev, case, dt):
+    def make():
+        from rmem_ocu_amd.runtime import temporal_slots
+        x = G.long_inputs(case, dt)
+        r = [G.gated_ref(x['q'][c], x['k'][c], x['v'][c], x['u'][c] if case.ub else x['u'][c][:, :512], x['pe_cur'], x['pe_mem'],
+                         temporal_slots(case.T), device=dev) for c in range(case.clips)]
+        return torch.stack([o for o, _ in r]), torch.stack([m for _, m in r])
+    return cached_ref((case, dt), make)
+
+
+def run_long(dev, case, dt, fill=None, dw=None):
+    """The long-term launch of the group engine: q and u_a column ranges of one [clips * L, 2176] buffer, a K / V bank with free (NaN)
+    slots, a table per clip over its own slots in its own frame order.  fill: value the whole workspace holds before the launch."""
+    from rmem_ocu_amd import ops
+    from rmem_ocu_amd.runtime import temporal_slots
+    L, T, n = case.H * case.W, case.T, case.clips
+    x = G.long_inputs(case, dt)
+    S, phys, order = G.long_slots(case)
+    pes = temporal_slots(T)
+    kb, vb = torch.full((S, L, 128), NAN), torch.full((S, L, DV), NAN)
+    rows = []
+    for c in range(n):
+        for t in range(T):
+            kb[phys[c][t]], vb[phys[c][t]] = x['k'][c, t], x['v'][c, t]
+        rows += G.frame_rows(T, L, case.splits, phys[c], pes, order[c])
+    nchunks = len(rows) // n
+    buf = torch.full((n * L, 2176), NAN)
+    buf[:, :128], buf[:, 1152:1664] = x['q'].reshape(n * L, 128), x['u'].reshape(n * L, DV)[:, :512]
+    buf = buf.to(dt).to(dev)
+    ub = x['u'].reshape(n * L, DV)[:, 512:].contiguous().to(dt).to(dev) if case.ub else None
+    ws = ops.gated_workspace(L, DV, T, L, nchunks, dev, nclips=n)
+    if fill is not None:
+        ws.fill_(fill)
+    out = torch.zeros(n, L, DV, dtype=dt, device=dev)
+    mass = torch.zeros(n, L, T, dtype=F32, device=dev)
+    ops.run(ops.gated_attn(buf, kb.to(dt).to(dev), vb.to(dt).to(dev), buf.view(-1)[1152:], out, ws, Lq=L, DV=DV, ldq=2176, ldk=128, ldv=DV,
+                           ldua=2176, ldo=DV, k_slot_stride=L * 128, v_slot_stride=L * DV, chunks=chunk_table(rows, dev), nchunks=nchunks,
+                           frames=T, keys_per_frame=L, pe_cur=x['pe_cur'].to(dev), pe_mem=x['pe_mem'].to(dev), u_b=ub, ldub=512, usplit=512,
+                           mass=mass, dw=dw, H=case.H if dw is not None else 0, W=case.W if dw is not None else 0, nclips=n))
+    torch.cuda.synchronize()
+    return out, mass
+
+
+def check_long(out, mass, ref, mass_ref, dt, what):
+    clips_close(out, ref, TOL[dt], what)
+    print(f'{what}: max |mass - ref| = {(mass - mass_ref).abs().max().item():.3g}')
+    for c in range(len(ref)):
+        assert (mass[c] - mass_ref[c]).abs().max().item() < MASS_TOL, f'{what}: mass of clip {c}'
+        assert (mass[c].sum(1) - 1).abs().max().item() < 1e-4
+
+
+@pytest.mark.parametrize('case,dt', case_dts(LONG_CASES))
+def test_gated_attn_clips_vs_reference(dev, case, dt):
+    """Chunk-table launches with a clip dimension: 8 key groups of which 3 are empty; 3 groups whose ranges begin inside table rows
+    (T > 4 slot table, two rows per frame); one group (the plan of the benchmark geometry).  Output and mass against the float64
+    reference per clip; dw=: the same bits as this launch followed by the stand-alone depth-wise 5x5 on every clip, and within the
+    bound the gated output's own tolerance implies of the float64 depth-wise 5x5 of the reference."""
+    from rmem_ocu_amd import ops
+    ref, mass_ref = long_ref(dev, case, dt)
+    out, mass = run_long(dev, case, dt)
+    check_long(out, mass, ref, mass_ref, dt, f'long {case.name} {dt}')
+    w = seeded(case.seed + 9, (25, DV), 0.2).to(dev)
+    two = torch.zeros_like(out)
+    ops.run([ops.dwconv5x5(out[c], w, two[c], H=case.H, W=case.W, C=DV) for c in range(case.clips)])
+    fused, mass2 = run_long(dev, case, dt, dw=w)
+    assert torch.equal(fused, two) and torch.equal(mass2, mass)
+    # |dw(x + e) - dw(x)| <= max |e| * max_c sum_taps |w|, plus the e16 rounding of the result (unit roundoff: 2^-8 bf16, 2^-11 half)
+    ulp = 2.0 ** -8 if dt is BF16 else 2.0 ** -11
+    for c in range(case.clips):
+        y = G.dwconv5x5_ref(ref[c], w, case.H, case.W)
+        bound = TOL[dt] * ref[c].abs().max().item() * w.abs().sum(0).max().item() + ulp * y.abs().max().item()
+        assert (fused[c].double() - y).abs().max().item() <= bound, f'fused depth-wise 5x5, clip {c}'
+
+
+def self_ref(dev, case, dt):
+    def make():
+        x = G.self_inputs(case, dt)
+        return torch.stack([G.gated_ref(x[c, :, :128], x[c, :, :128][None], x[c, :, 128:128 + DV][None], x[c, :, 128 + DV:], device=dev)[0]
+                            for c in range(case.clips)])
+    return cached_ref((case, dt), make)
+
+
+def run_self(dev, case, dt, fill=None):
+    """The self-attention launch of the group engine on the fused [clips * L, 2176] buffer: q = k at column 0, v at 128, u at 1152."""
+    from rmem_ocu_amd import ops
+    L, n = case.H * case.W, case.clips
+    buf = G.self_inputs(case, dt).reshape(n * L, 2176).to(dt).to(dev)
+    ws = ops.gated_workspace(L, DV, 1, L, case.nchunks, dev, nclips=n)
+    if fill is not None:
+        ws.fill_(fill)
+    out = torch.zeros(n, L, DV, dtype=dt, device=dev)
+    ops.run(ops.gated_attn(buf, buf, buf.view(-1)[128:], buf.view(-1)[1152:], out, ws, Lq=L, DV=DV, ldq=2176, ldk=2176, ldv=2176,
+                           ldua=2176, ldo=DV, nchunks=case.nchunks, frames=1, keys_per_frame=L, nclips=n))
+    torch.cuda.synchronize()
+    return out
+
+
+@pytest.mark.parametrize('case,dt', case_dts(SELF_CASES))
+def test_self_gated_attn_clips_vs_reference(dev, case, dt):
+    """No table, clip strides of the fused buffer: 3 clips / 8 ranges asked (3 rows of 64 keys, 3 key groups); 17 clips / 2 ranges
+    (rows of 128 + 15 keys, one key group)."""
+    clips_close(run_self(dev, case, dt), self_ref(dev, case, dt), TOL[dt], f'self {case.name} {dt}')
+
+
+def local_ref(dev, case, dt, clips=None):
+    def make():
+        x = G.local_inputs(case, dt, clips)
+        return torch.stack([G.local_gated_ref(x['q'][c], x['k'][c], x['v'][c], x['rel'][c], x['u'][c] if case.ub else x['u'][c][:, :512],
+                                              case.H, case.W, device=dev) for c in range(len(x['q']))])
+    return cached_ref((case, dt, clips), make) if (clips or case.clips) <= 3 else make()
+
+
+def run_local(dev, case, dt, fill=None, clips=None):
+    """The local launch of the group engine: rel fp32 with row stride 256 (the 31 pad columns hold NaN), the gate as two halves."""
+    from rmem_ocu_amd import ops
+    x = G.local_inputs(case, dt, clips)
+    n, L = x['q'].shape[:2]
+    e16 = lambda t: t.reshape(n * L, -1).contiguous().to(dt).to(dev)      # noqa: E731
+    rel = torch.full((n * L, 256), NAN)
+    rel[:, :225] = x['rel'].reshape(n * L, 225)
+    ws = ops.gated_workspace(L, DV, 1, L, 8, dev, nclips=n)
+    if fill is not None:
+        ws.fill_(fill)
+    out = torch.zeros(n, L, DV, dtype=dt, device=dev)
+    ops.run(ops.local_gated_attn(e16(x['q']), e16(x['k']), e16(x['v']), rel.to(dev), e16(x['u'][..., :512]), out, ws, H=case.H, W=case.W,
+                                 DV=DV, ldq=128, ldk=128, ldv=DV, ldrel=256, ldua=512, ldo=DV,
+                                 u_b=e16(x['u'][..., 512:]) if case.ub else None, ldub=512, usplit=512, nclips=n))
+    torch.cuda.synchronize()
+    return out
+
+
+@pytest.mark.parametrize('case,dt', case_dts(LOCAL_CASES))
+def test_local_gated_attn_clips_vs_reference(dev, case, dt):
+    """15x15 window with a clip dimension (the rel clip stride, both gate forms) and every count of key ranges the entry picks:
+    8 asked at 3 clips (3 rows at 11 x 13; 7 rows and 5 key groups at 18 x 23, where the first query tile's band covers 5 of the 7
+    key tiles), 4 at 32 clips, 2 at 56 clips -- all clips against the float64 reference evaluated on the device."""
+    clips_close(run_local(dev, case, dt), local_ref(dev, case, dt), TOL[dt], f'local {case.name} {dt}')
+
+
+def test_local_gated_attn_single_clip_f16(dev):
+    """Half flavour, one clip of 18 x 23 tokens: 7 rows, 7 key groups (the plan of every single-clip test)."""
+    case = LOCAL_CASES[2]
+    clips_close(run_local(dev, case, F16, clips=1), local_ref(dev, case, F16, clips=1), TOL[F16], 'local 18x23 one clip half')
+
+
+@pytest.mark.parametrize('T,L,splits', [(1, 99, 1), (3, 200, 2)])
+def test_gated_attn_temporal_pe_f16(dev, T, L, splits):
+    """test_gated_attn_temporal_pe through the half flavour (always the exact two passes, P stored in IEEE half)."""
+    from rmem_ocu_amd import ops
+    from rmem_ocu_amd.runtime import temporal_slots
+    x = G.temporal_pe_inputs(T, L, F16)
+    slots = temporal_slots(T)
+    ref, mass_ref = G.gated_ref(x['q'], x['k'], x['v'], x['u'], x['pe_cur'], x['pe_mem'], slots, device=dev)
+    rows = frame_rows(T, L, splits, slots)
+    ws = ops.gated_workspace(L, DV, T, L, len(rows), dev)
+    out = torch.zeros(1, L, DV, dtype=F16, device=dev)
+    mass = torch.zeros(1, L, T, dtype=F32, device=dev)
+    h = lambda t: t.to(F16).to(dev)      # noqa: E731
+    ops.run(ops.gated_attn(h(x['q']), h(x['k']), h(x['v']), h(x['u']), out, ws, Lq=L, DV=DV, ldq=128, ldk=128, ldv=DV, ldua=DV, ldo=DV,
+                           k_slot_stride=L * 128, v_slot_stride=L * DV, chunks=chunk_table(rows, dev), nchunks=len(rows), frames=T,
+                           keys_per_frame=L, pe_cur=x['pe_cur'].to(dev), pe_mem=x['pe_mem'].to(dev), mass=mass))
+    torch.cuda.synchronize()
+    check_long(out, mass, ref[None], mass_ref[None], F16, f'half temporal pe T={T} L={L}')
+
+
+def test_gated_attn_extreme_logits_f16(dev):
+    """test_gated_attn_extreme_logits through the half flavour: with the exact row maximum as reference P stays <= 1."""
+    from rmem_ocu_amd import ops
+    L = 130
+    rh = lambda t: G.through(t, F16)      # noqa: E731
+    q, k = rh(seeded(71, (L, 128))), rh(seeded(72, (1, L, 128)))
+    q[5] = 0
+    q[7] = k[0, 100] * 30
+    v, u = rh(seeded(73, (1, L, DV))), torch.ones(L, DV)
+    ws = ops.gated_workspace(L, DV, 1, L, 2, dev)
+    out = torch.zeros(L, DV, dtype=F16, device=dev)
+    h = lambda t: t.to(F16).to(dev)      # noqa: E731
+    ops.run(ops.gated_attn(h(q), h(k), h(v), h(u), out, ws, Lq=L, DV=DV, ldq=128, ldk=128, ldv=DV, ldua=DV, ldo=DV, nchunks=2, frames=1,
+                           keys_per_frame=L))
+    torch.cuda.synchronize()
+    ref, _ = G.gated_ref(q, k, v, u, device=dev)
+    clips_close(out[None], ref[None], TOL[F16], 'half extreme logits')
+    assert_close(out[7], v[0, 100], 1e-2, 'dominant key row')
+
+
+@pytest.mark.parametrize('dt', [BF16, F16], ids=['bfloat16', 'float16'])
+@pytest.mark.parametrize('mode', ['long', 'self', 'local'])
+def test_gated_attn_dirty_workspace(dev, mode, dt):
+    """The engines reuse one workspace from launch to launch.  Window mode never writes the P tiles outside a query tile's band and
+    k_gp_pv has to skip exactly those; padded P rows, mpart / lpart and the slabs of empty key groups are left over from the
+    previous launch.  A workspace full of NaN must give the bits of a zeroed one, and meet the reference."""
+    if mode == 'long':
+        case = LONG_CASES[0]
+        (a, ma), (b, mb) = run_long(dev, case, dt, fill=NAN), run_long(dev, case, dt, fill=0.0)
+        assert torch.equal(ma, mb)
+        check_long(a, ma, *long_ref(dev, case, dt), dt, f'dirty long {dt}')
+    elif mode == 'self':
+        case = SELF_CASES[0]
+        a, b = run_self(dev, case, dt, fill=NAN), run_self(dev, case, dt, fill=0.0)
+        clips_close(a, self_ref(dev, case, dt), TOL[dt], f'dirty self {dt}')
+    else:
+        case = LOCAL_CASES[2]
+        a, b = run_local(dev, case, dt, fill=NAN), run_local(dev, case, dt, fill=0.0)
+        clips_close(a, local_ref(dev, case, dt), TOL[dt], f'dirty local {dt}')
+    assert torch.equal(a, b)
+
+
+def short(t):
+    return t.view(-1)[:-1]
+
+
+def test_gated_attn_rejects_short_operands(dev):
+    """ops.gated_attn / ops.local_gated_attn refuse, on the host and before anything is launched, any [clip][rows][ld] operand that is
+    one element shorter than the clip count needs (the kernels would read or write past its end)."""
+    from rmem_ocu_amd import ops
+    n, H, W = 2, 2, 3
+    L = H * W
+    e = lambda *shape, dt=BF16: torch.zeros(*shape, dtype=dt, device=dev)      # noqa: E731
+    ws = ops.gated_workspace(L, DV, 1, L, 8, dev, nclips=n)
+    t = dict(q=e(n * L, 128), k=e(n * L, 128), v=e(n * L, DV), u_a=e(n * L, 512), u_b=e(n * L, 512), out=e(n * L, DV))
+
+    def gated(**kw):
+        a = dict(t, **kw)
+        return ops.gated_attn(a['q'], a['k'], a['v'], a['u_a'], a['out'], ws, Lq=L, DV=DV, ldq=128, ldk=128, ldv=DV, ldua=512, ldo=DV,
+                              nchunks=2, frames=1, keys_per_frame=L, u_b=a['u_b'], ldub=512, usplit=512, nclips=n)
+
+    def local(**kw):
+        a = {**t, 'rel': e(n * L, 256, dt=F32), **kw}
+        return ops.local_gated_attn(a['q'], a['k'], a['v'], a['rel'], a['u_a'], a['out'], ws, H=H, W=W, DV=DV, ldq=128, ldk=128, ldv=DV,
+                                    ldrel=256, ldua=512, ldo=DV, u_b=a['u_b'], ldub=512, usplit=512, nclips=n)
+
+    gated(), local()      # exactly long enough: accepted (the Ops are built, never run)
+    for name in t:
+        for entry in (gated, local):
+            with pytest.raises(ops.RmemError, match=rf'\b{name} has'):
+                entry(**{name: short(t[name])})
+    with pytest.raises(ops.RmemError, match=r'\brel has'):
+        local(rel=e(n * L, 256, dt=F32).view(-1)[:(n * L - 1) * 256 + 224])
