@@ -575,6 +575,21 @@ int rmem_tta_merge(const float* const* logits_nchw, const int* flips, int n_aug,
 int rmem_logits_post_flip_pairs(const float* logits_nhwc16, int rows, int num_classes, int keep_max_id, int Hi, int Wi, int Ho, int Wo,
                                 int align_corners, unsigned char* label_u8, void* stream);
 
+/* Multi-scale (x flip) testing inside clip groups, fused: every scale runs a clip group of its own at its own network size, and the
+ * groups meet here once per frame.  members / Hi / Wi / flips are HOST arrays of n_aug (1..8) entries in the evaluator's order (scale
+ * outer, flip inner): member a is a device pointer to fp32 logits [clips][Hi[a] * Wi[a]][16], 16-byte aligned; the mirrored twins of
+ * a flip group are its logits buffer advanced by `clips` rows.  Per output pixel (y, x) of clip p, for a = 0 .. n_aug - 1 in order:
+ * member a blended at (y, x), or at (y, Wo - 1 - x) where flips[a] (bilinear, ids > keep_max_id forced to -1e10, as
+ * rmem_logits_post_images), softmax over the num_classes channels, summed; * 1 / n_aug, argmax (first maximum) -- what rmem_logits_post
+ * per member + rmem_tta_merge compute, without the full-size fp32 maps.  label_u8 [clips][Ho][Wo] gets the merged label; twin_u8
+ * [clips][Ho][Wo], if given, the same value at (y, Wo - 1 - x) (row `clips` of a [2 * clips][Ho][Wo] buffer: what the mirrored
+ * engines' memory updates take).  n_aug = 2, equal sizes, flips (0, 1) gives rmem_logits_post_flip_pairs bit for bit.  Refused
+ * (non-zero, nothing launched): n_aug outside 1..8, num_classes > 16, keep_max_id >= num_classes, clips < 1, non-positive sizes, a
+ * null member or label_u8, a member not 16-byte aligned. */
+int rmem_logits_post_ms_merge(const float* const* members, const int* Hi, const int* Wi, const int* flips, int n_aug, int clips,
+                              int num_classes, int keep_max_id, int Ho, int Wo, int align_corners, unsigned char* label_u8,
+                              unsigned char* twin_u8, void* stream);
+
 /* Label routing of a RAGGED clip group (clip_runner.RaggedGroupSlot): the rows of a group run clips of different lengths, so after
  * the decoder every row delivers its label map to another address, and a row may take a new object's overlay, continue from fed
  * labels, mirror into its flip twin or be idle.  One launch, driven by a device table of `rows` entries; rows_u8 [rows][Ho * Wo]

@@ -426,6 +426,17 @@ class GroupSlot:
         labels that go into the memory update INSTEAD of the prediction (the delivered labels stay the prediction): given masks,
         e.g. the reference's own in the parity tests, so that every frame is an independent comparison (flip testing: the twins
         are fed the mirror)."""
+        self._propagate_step()
+        inject = self._settle_labels(feed)
+        self._update_memories(inject)
+        if feed is None:
+            self._deliver()
+        self._advance()
+
+    # the parts of step(): MultiScaleGroupSlot runs them engine by engine around its merge across engines
+    def _propagate_step(self, to_logits: bool = False):
+        """Frame ``cursor`` of every row through the engine into cur_label -- or, to_logits, as far as the engine's logits (-> the
+        event behind them); before that the look-ahead encoder of the next batch is kicked where one is due."""
         eng, B, i, P = self.engine, self.B, self.cursor, self.clips
         la = eng.lookahead
         s = eng.stream.cuda_stream
@@ -433,6 +444,8 @@ class GroupSlot:
             b, e = divmod(i - 1, la)
             if e == 0 and i + la < self.frames[0].shape[0]:
                 self._kick_encoder((b + 1) % 2, i + la)         # the NEXT batch, on the side stream, beside this batch's frames
+            if to_logits:
+                return eng.propagate_to_logits(enc_slot=(b % 2) * la + e)
             eng.propagate_to_labels(self.cur_label, enc_slot=(b % 2) * la + e)
         else:
             self.frames_encoded += B
@@ -444,11 +457,25 @@ class GroupSlot:
                     imgs = torch.cat([f[i:i + 1] for f in self.frames] * (B // P), 0)
                     if self.flip:
                         self._mirror_twins(imgs, s)
+            if to_logits:
+                return eng.propagate_to_logits(imgs=imgs)
             eng.propagate_to_labels(self.cur_label, imgs=imgs)
+
+    def _deliver(self):
+        """cur_label's clip rows -> frame ``cursor`` of every clip's label stack: one pitched copy on the engine's stream"""
+        nb = self.cur_label[0].numel()
+        ops.copy2d_async(self.labels.view(-1)[self.cursor * nb:], self.labels.shape[1] * nb, self.cur_label, nb, nb, self.clips)(
+            self.engine.stream.cuda_stream)
+
+    def _settle_labels(self, feed: Optional[torch.Tensor]) -> List[int]:
+        """cur_label holds the prediction -> what the memories continue from: the fed labels (the prediction is delivered first),
+        new objects laid over it.  -> the clips that take a new object at this frame."""
+        eng, i, P = self.engine, self.cursor, self.clips
+        s = eng.stream.cuda_stream
         inject = [c for c, (fi, _) in self.new_objects.items() if fi == i]
-        nb = self.cur_label[0].numel()                # frame i of every clip's label stack: one pitched copy
+        nb = self.cur_label[0].numel()
         if feed is not None:                          # deliver the prediction, then continue from the given labels
-            ops.copy2d_async(self.labels.view(-1)[i * nb:], self.labels.shape[1] * nb, self.cur_label, nb, nb, P)(s)
+            self._deliver()
             ops.copy_async(self.cur_label, feed.contiguous(), P * nb)(s)
             if self.flip:
                 with torch.cuda.stream(eng.stream):
@@ -460,6 +487,12 @@ class GroupSlot:
                     self.cur_label[c].copy_(torch.where(new > 0, new, self.cur_label[c]))
                     if self.flip:                     # and its mirror over the twin's row, which holds the mirrored prediction
                         self.cur_label[P + c].copy_(self.cur_label[c].flip(-1))
+        return inject
+
+    def _update_memories(self, inject: List[int]):
+        """The engine's memory update from cur_label; the clips of ``inject`` restart from this frame as their reference frame."""
+        eng, i, P = self.engine, self.cursor, self.clips
+        s = eng.stream.cuda_stream
         rows = inject + [P + c for c in inject] if self.flip else inject
         eng.update_from_labels(self.cur_label, skip=rows)
         for c in inject:
@@ -469,10 +502,146 @@ class GroupSlot:
                     self._twin_ref = torch.empty_like(self.frames[c][i:i + 1])
                 ops.run(ops.resize_nearest_flip(self.frames[c][i:i + 1], self._twin_ref, flip=True), s)
                 eng.add_reference_frame_for(P + c, self._twin_ref[0], self.cur_label[P + c])
-        if feed is None:
-            ops.copy2d_async(self.labels.view(-1)[i * nb:], self.labels.shape[1] * nb, self.cur_label, nb, nb, P)(s)
+
+    def _advance(self):
         self.cursor += 1
         self.done = self.cursor >= self.frames[0].shape[0]
+
+
+class MultiScaleGroupSlot:
+    """MULTI-SCALE TESTING (TEST_MULTISCALE, managers/evaluator.py:342-355, 427-441) of P clips of equal length at group speed: one
+    GroupEngine per scale, each a plain group of P rows or (flip testing) a flip group of 2P rows at its own network size, with its
+    own streams, graphs, banks and look-ahead; what GroupSlot does per engine (reference frames, look-ahead batches, twin
+    mirroring, new objects) is done by one inner GroupSlot per engine.  The scales are coupled at one place per frame: ONE label
+    buffer cur_label [B, Ho, Wo] at a fixed address, written by ops.logits_post_ms_merge from the 1/4-resolution logits of every
+    engine (members in the evaluator's order: scale outer, flip inner; the twins' logits are rows P.. of their engine's buffer),
+    rows P.. with the mirror.  Every engine updates its memory from that buffer: its id-embed kernel resizes to its own network
+    size, the twins from the mirrored rows (mirror, THEN resize).  labels: uint8 [P, n, Ho, Wo], as GroupSlot's.
+
+    ORDER of a step.  Every engine propagates to its logits on its own stream and records an event; engine 0's stream waits for
+    the other engines' events, merges, delivers, applies fed labels and new objects and records "label ready"; the other streams
+    wait for that; every engine updates (and restarts injected rows) on its own stream.  No further event is needed: an engine's
+    ``rt.logits`` is rewritten only by its next propagation, which sits behind its update on the same stream, which sits behind
+    the merge that read them; cur_label is rewritten only by the next merge, which sits behind every engine's next propagation
+    and so behind every update that read it.
+
+    Not taken here (the single-scale slots do): pinned uint8 frames, JpegClips, ragged rows (RaggedGroupSlot)."""
+
+    def __init__(self, engines, out_hw, device):
+        engines = list(engines)
+        if not engines:
+            raise ValueError('MultiScaleGroupSlot: one GroupEngine per scale, at least one')
+        for e in engines:
+            if isinstance(e, (RaggedGroupSlot, GroupSlot)) or not hasattr(e, 'propagate_to_logits'):
+                raise ValueError('MultiScaleGroupSlot takes GroupEngines, one per scale; it does not run on a RaggedGroupSlot (ragged '
+                                 'rows stay single-scale)')
+        e0 = engines[0]
+        for k, e in enumerate(engines[1:], 1):
+            for attr, name in (('B', 'rows'), ('flip_tta', 'flip_tta'), ('lookahead', 'lookahead'), ('device', 'device')):
+                if getattr(e, attr) != getattr(e0, attr):
+                    raise ValueError(f'MultiScaleGroupSlot: engine {k} differs from engine 0 in {name} '
+                                     f'({getattr(e, attr)} against {getattr(e0, attr)})')
+        self.flip = bool(e0.flip_tta)
+        members = len(engines) * (2 if self.flip else 1)
+        if members > 8:
+            raise ValueError(f'MultiScaleGroupSlot: {len(engines)} scales{" x flip" if self.flip else ""} make {members} members, '
+                             'at most 8 are merged')
+        self.engines = engines
+        self.B = e0.B
+        self.clips = self.B // 2 if self.flip else self.B
+        self.out_hw = out_hw
+        self.device = device
+        self.slots = [GroupSlot(e, out_hw, device) for e in engines]
+        self.cur_label = self.slots[0].cur_label              # fixed address; ONE buffer for every engine
+        for sl in self.slots[1:]:
+            sl.cur_label = self.cur_label
+        self._ready = None
+        self._first = [None] * len(engines)
+        self._merge = (None, None)
+
+    labels = property(lambda self: self.slots[0].labels)
+    cursor = property(lambda self: self.slots[0].cursor)
+    done = property(lambda self: self.slots[0].done)
+    frames_encoded = property(lambda self: sum(sl.frames_encoded for sl in self.slots))
+
+    def start(self, frames, first_labels, num_objs: int, new_objects=None):
+        """frames[s][c]: fp32 device tensors [n, 3, H_s, W_s], scale s at engine s's network size, equal n; first_labels[c]: fp32
+        [1, 1, Ho, Wo] at the OUTPUT size -- resized to every scale's network size on the device (nearest,
+        rmem_resize_nearest_flip_f32) and THEN mirrored for the twins, as SequenceEvaluator does.  new_objects: as GroupSlot.start
+        (maps at the output size; every engine restarts that clip's rows from its own scale's frame)."""
+        P, S = self.clips, len(self.engines)
+        if len(frames) != S:
+            raise ValueError(f'MultiScaleGroupSlot.start: frames holds one list of clips per scale ({S} scales, got {len(frames)})')
+        for fs in frames:
+            if isinstance(fs, torch.Tensor) or len(fs) != P:
+                raise ValueError(f'MultiScaleGroupSlot.start: every scale takes {P} clips')
+            for f in fs:
+                if isinstance(f, JpegClip):
+                    raise ValueError('MultiScaleGroupSlot: JpegClip sources are not taken (use GroupSlot per scale, or decode first)')
+                if f.dtype == torch.uint8:
+                    raise ValueError('MultiScaleGroupSlot: pinned uint8 frames are not taken; frames are fp32 device tensors at '
+                                     'each scale\'s network size')
+        if len({int(f.shape[0]) for fs in frames for f in fs}) != 1:
+            raise ValueError('MultiScaleGroupSlot.start: every clip at every scale has the same number of frames')
+        if len(first_labels) != P or any(tuple(m.shape[-2:]) != tuple(self.out_hw) for m in first_labels):
+            raise ValueError(f'MultiScaleGroupSlot.start: {P} first labels [1, 1, {self.out_hw[0]}, {self.out_hw[1]}] at the output size')
+        # held until the next start: the engines' streams read them
+        self._first_src = [m.reshape(1, 1, *self.out_hw).float().contiguous() for m in first_labels]
+        cur = torch.cuda.current_stream(self.device)
+        for k, (eng, sl, fs) in enumerate(zip(self.engines, self.slots, frames)):
+            H, W = int(fs[0].shape[-2]), int(fs[0].shape[-1])
+            if any(tuple(f.shape[-2:]) != (H, W) for f in fs):
+                raise ValueError(f'MultiScaleGroupSlot.start: scale {k}: its clips are not at one network size')
+            eng.stream.wait_stream(cur)                   # the first labels come from the caller's stream
+            with torch.cuda.stream(eng.stream):
+                if self._first[k] is None or tuple(self._first[k].shape[-2:]) != (H, W):
+                    self._first[k] = torch.empty(P, 1, 1, H, W, dtype=torch.float32, device=self.device)
+                ops.run([ops.resize_nearest_flip(m, self._first[k][c], flip=False) for c, m in enumerate(self._first_src)], eng.stream.cuda_stream)
+            if k:
+                sl.labels = self.slots[0].labels          # delivered by engine 0's slot only: no second stack
+            sl.start(fs, list(self._first[k]), num_objs, new_objects=new_objects)
+
+    def _merge_op(self):
+        """the merge across engines, rebuilt when an engine got a new runtime (its logits moved)"""
+        P = self.clips
+        key = tuple(e.rt.logits.data_ptr() for e in self.engines)
+        if self._merge[0] != key:
+            members = []
+            for e in self.engines:
+                rt = e.rt
+                members.append((rt.logits, rt.H4, rt.W4, False))
+                if self.flip:
+                    members.append((rt.logits[P * rt.H4 * rt.W4:], rt.H4, rt.W4, True))
+            e0 = self.engines[0]
+            if any((e.rt.nc, e.obj_nums[0], e.align_corners) != (e0.rt.nc, e0.obj_nums[0], e0.align_corners) for e in self.engines):
+                raise ValueError('MultiScaleGroupSlot: the engines do not share classes, kept ids and align_corners (one model)')
+            op = ops.logits_post_ms_merge(members, e0.rt.nc, e0.obj_nums[0], self.out_hw[0], self.out_hw[1], e0.align_corners,
+                                          self.cur_label, self.cur_label[P:] if self.flip else None, P=P)
+            self._merge = (key, op)
+        return self._merge[1]
+
+    def step(self, feed: Optional[torch.Tensor] = None):
+        """GroupSlot.step across the scales (the class docstring has the order).  feed: uint8 [P, Ho, Wo], as GroupSlot.step."""
+        lead, s0 = self.slots[0], self.engines[0].stream
+        events = [sl._propagate_step(to_logits=True) for sl in self.slots]
+        for ev in events[1:]:
+            s0.wait_event(ev)
+        ops.run(self._merge_op(), s0.cuda_stream)
+        inject = lead._settle_labels(feed)
+        if feed is None:
+            lead._deliver()
+        if self._ready is None:
+            self._ready = torch.cuda.Event()
+        self._ready.record(s0)
+        for e in self.engines[1:]:
+            e.stream.wait_event(self._ready)
+        for sl in self.slots:
+            sl._update_memories(inject)
+            sl._advance()
+
+    def synchronize(self):
+        for e in self.engines:
+            e.synchronize()
 
 
 class FinishedClip(NamedTuple):

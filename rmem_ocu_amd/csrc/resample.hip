@@ -458,12 +458,13 @@ __device__ __forceinline__ void flip_softmax_acc(const float* a, const float* b,
   for (int ch = 0; ch < 16; ++ch) acc[ch] += v[ch] * inv;
 }
 
-__device__ __forceinline__ int flip_merged_label(const float (&acc)[16], int nc) {
+// scale = 1 / members: 0.5f for a flip pair (exact), 1.f / n_aug for the multi-scale merge
+__device__ __forceinline__ int flip_merged_label(const float (&acc)[16], int nc, float scale) {
   float best = -1.f; int arg = 0;
 #pragma unroll
   for (int ch = 0; ch < 16; ++ch) {
     if (ch < nc) {
-      const float pr = acc[ch] * 0.5f;
+      const float pr = acc[ch] * scale;
       if (pr > best) { best = pr; arg = ch; }
     }
   }
@@ -528,7 +529,7 @@ __global__ __launch_bounds__(128) void k_logits_flip_pairs_tile(const float* lg,
                      &src[(r1 * ncols + (x1 - xlo)) * 16], wx, wy, nc, keep, acc);
     flip_softmax_acc(&srct[(r0 * mcols + (m0 - mlo)) * 16], &srct[(r0 * mcols + (m1 - mlo)) * 16], &srct[(r1 * mcols + (m0 - mlo)) * 16],
                      &srct[(r1 * mcols + (m1 - mlo)) * 16], wm, wy, nc, keep, acc);
-    pk |= (unsigned)flip_merged_label(acc, nc) << (8 * k);
+    pk |= (unsigned)flip_merged_label(acc, nc, 0.5f) << (8 * k);
     n = k + 1;
   }
   uint8_t* dp = lp + (long)oy * Wo + oxb;                       // pixels oxb .. oxb + n - 1 of the plain row, left to right
@@ -539,8 +540,9 @@ __global__ __launch_bounds__(128) void k_logits_flip_pairs_tile(const float* lg,
   else for (int k = 0; k < n; ++k) dt[-k] = (uint8_t)(pk >> (8 * k));
 }
 
-// host side of k_logits_flip_pairs_tile: the source pixels under EVERY output tile and under every mirrored tile fit FP_SRC
-bool fp_tiles_fit(int Hi, int Wi, int Ho, int Wo, int align) {
+// host side of k_logits_flip_pairs_tile / k_logits_ms_merge_tile: the source pixels under EVERY output tile (plain) and / or under
+// every mirrored tile (mirrored) fit FP_SRC
+static bool fp_extents_fit(int Hi, int Wi, int Ho, int Wo, int align, bool plain, bool mirrored) {
   int rows = 0, cols = 0, lo, hi, t; float w;
   for (int o0 = 0; o0 < Ho; o0 += FP_H) {
     rmem_src_coord(o0, Hi, Ho, align, lo, t, w);
@@ -549,15 +551,20 @@ bool fp_tiles_fit(int Hi, int Wi, int Ho, int Wo, int align) {
   }
   for (int o0 = 0; o0 < Wo; o0 += FP_W) {
     const int o1 = (o0 + FP_W < Wo ? o0 + FP_W : Wo) - 1;
-    rmem_src_coord(o0, Wi, Wo, align, lo, t, w);
-    rmem_src_coord(o1, Wi, Wo, align, t, hi, w);
-    cols = hi - lo + 1 > cols ? hi - lo + 1 : cols;
-    rmem_src_coord(Wo - 1 - o1, Wi, Wo, align, lo, t, w);
-    rmem_src_coord(Wo - 1 - o0, Wi, Wo, align, t, hi, w);
-    cols = hi - lo + 1 > cols ? hi - lo + 1 : cols;
+    if (plain) {
+      rmem_src_coord(o0, Wi, Wo, align, lo, t, w);
+      rmem_src_coord(o1, Wi, Wo, align, t, hi, w);
+      cols = hi - lo + 1 > cols ? hi - lo + 1 : cols;
+    }
+    if (mirrored) {
+      rmem_src_coord(Wo - 1 - o1, Wi, Wo, align, lo, t, w);
+      rmem_src_coord(Wo - 1 - o0, Wi, Wo, align, t, hi, w);
+      cols = hi - lo + 1 > cols ? hi - lo + 1 : cols;
+    }
   }
   return rows * cols <= FP_SRC;
 }
+bool fp_tiles_fit(int Hi, int Wi, int Ho, int Wo, int align) { return fp_extents_fit(Hi, Wi, Ho, Wo, align, true, true); }
 
 // below 2 x upsampling, or where a tile's source pixels do not fit: one output pixel per thread, taps from global memory
 __global__ __launch_bounds__(256) void k_logits_flip_pairs_px(const float* lg, int P, int nc, int keep, int Hi, int Wi, int Ho, int Wo,
@@ -579,9 +586,111 @@ __global__ __launch_bounds__(256) void k_logits_flip_pairs_px(const float* lg, i
                    lgp + ((long)y1 * Wi + x1) * 16, wx, wy, nc, keep, acc);
   flip_softmax_acc(lgt + ((long)y0 * Wi + m0) * 16, lgt + ((long)y0 * Wi + m1) * 16, lgt + ((long)y1 * Wi + m0) * 16,
                    lgt + ((long)y1 * Wi + m1) * 16, wm, wy, nc, keep, acc);
-  const uint8_t arg = (uint8_t)flip_merged_label(acc, nc);
+  const uint8_t arg = (uint8_t)flip_merged_label(acc, nc, 0.5f);
   label[(long)blockIdx.y * total + i] = arg;
   label[((long)P + blockIdx.y) * total + (long)oy * Wo + (Wo - 1 - ox)] = arg;
+}
+
+// Multi-scale (x flip) testing inside clip groups: every scale runs a group of its own at its own network size; the one coupling
+// per frame is here.  Member a (evaluator order: scale outer, flip inner) is P rows of 16-float logits at Hi[a] x Wi[a].  Per
+// output pixel (y, x) of clip p, members in order: blend at (y, x), or at (y, Wo - 1 - x) for a flipped member, soft-max
+// (flip_softmax_acc), accumulate; * 1 / n_aug, first maximum -> label[p][y][x], and the same value at twin[p][y][Wo - 1 - x] where
+// a twin buffer is given (what the mirrored engines' memory updates take).  With two members of one size and flips (0, 1) this is
+// k_logits_flip_pairs_* operation by operation.
+struct MsParams { const float* lg[8]; int Hi[8], Wi[8], flip[8]; int n_aug, nc, keep, Ho, Wo, align; uint8_t* label; uint8_t* twin; };
+
+// every member upsamples >= 2 x: k_logits_flip_pairs_tile's 16 x 32 tile per 128 threads, the members one after the other.  Member
+// a's source pixels under the tile (under the mirrored tile if it is flipped), <= FP_SRC, go to stage a & 1 -- two alternating
+// stages, 24 KB, so one barrier per member is enough: stage a & 1 is rewritten for member a + 2 behind the barrier of member
+// a + 1, which every thread passes after its taps of member a.  All members at once would not leave room beside the GEMMs of the
+// other groups.  The 4 pixels of a thread keep their 4 x 16 sums in registers across the member loop.
+__global__ __launch_bounds__(128) void k_logits_ms_merge_tile(MsParams p) {
+  __shared__ __attribute__((aligned(16))) float src[2 * FP_SRC * 16];
+  const int Ho = p.Ho, Wo = p.Wo, nc = p.nc, keep = p.keep, align = p.align;
+  const int tiles_x = (Wo + FP_W - 1) / FP_W;
+  const int ty = blockIdx.x / tiles_x, tx = blockIdx.x - ty * tiles_x;
+  const long total = (long)Ho * Wo;
+  const int oy0 = ty * FP_H, ox0 = tx * FP_W;
+  const int oy1 = min(oy0 + FP_H, Ho) - 1, ox1 = min(ox0 + FP_W, Wo) - 1;
+  const int oy = oy0 + (threadIdx.x >> 3), oxb = ox0 + (threadIdx.x & 7) * 4;
+  const bool live = oy < Ho && oxb < Wo;        // threads off the edge stage and keep the barriers, nothing else
+  float acc[4][16];
+#pragma unroll
+  for (int k = 0; k < 4; ++k)
+#pragma unroll
+    for (int ch = 0; ch < 16; ++ch) acc[k][ch] = 0.f;
+#pragma unroll 1
+  for (int a = 0; a < p.n_aug; ++a) {
+    const int Hi = p.Hi[a], Wi = p.Wi[a], fl = p.flip[a];
+    const float* lg = p.lg[a] + (long)blockIdx.y * Hi * Wi * 16;      // blockIdx.y = clip
+    float* const st = src + (a & 1) * (FP_SRC * 16);
+    const int c0 = fl ? Wo - 1 - ox1 : ox0, c1 = fl ? Wo - 1 - ox0 : ox1;   // the tile's columns as this member sees them
+    int ylo, yhi, xlo, xhi, t0, t1; float tw;
+    src_coord(oy0, Hi, Ho, align, ylo, t1, tw);
+    src_coord(oy1, Hi, Ho, align, t0, yhi, tw);
+    src_coord(c0, Wi, Wo, align, xlo, t1, tw);
+    src_coord(c1, Wi, Wo, align, t0, xhi, tw);
+    const int nrows = yhi - ylo + 1, ncols = xhi - xlo + 1;           // <= FP_SRC pixels: fp_extents_fit() on the host
+    for (int i = threadIdx.x; i < nrows * ncols * 4; i += 128) {
+      const int pix = i >> 2, q = i & 3;
+      const int r = pix / ncols, c = pix - r * ncols;
+      *reinterpret_cast<f32x4*>(&st[pix * 16 + 4 * q]) = *reinterpret_cast<const f32x4*>(lg + ((long)(ylo + r) * Wi + xlo + c) * 16 + 4 * q);
+    }
+    __syncthreads();
+    if (live) {
+      int y0, y1; float wy;
+      src_coord(oy, Hi, Ho, align, y0, y1, wy);
+      const int r0 = (y0 - ylo) * ncols - xlo, r1 = (y1 - ylo) * ncols - xlo;
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        const int ox = oxb + k;
+        if (ox < Wo) {
+          int x0, x1; float wx;
+          src_coord(fl ? Wo - 1 - ox : ox, Wi, Wo, align, x0, x1, wx);
+          flip_softmax_acc(&st[(r0 + x0) * 16], &st[(r0 + x1) * 16], &st[(r1 + x0) * 16], &st[(r1 + x1) * 16], wx, wy, nc, keep, acc[k]);
+        }
+      }
+    }
+  }
+  if (!live) return;
+  const float scale = 1.f / (float)p.n_aug;
+  unsigned pk = 0; int n = 0;
+#pragma unroll
+  for (int k = 0; k < 4; ++k)
+    if (oxb + k < Wo) { pk |= (unsigned)flip_merged_label(acc[k], nc, scale) << (8 * k); n = k + 1; }
+  uint8_t* dp = p.label + (long)blockIdx.y * total + (long)oy * Wo + oxb;                    // pixels oxb .. oxb + n - 1, left to right
+  if (n == 4 && (reinterpret_cast<uintptr_t>(dp) & 3) == 0) *reinterpret_cast<unsigned*>(dp) = pk;
+  else for (int k = 0; k < n; ++k) dp[k] = (uint8_t)(pk >> (8 * k));
+  if (p.twin) {
+    uint8_t* dt = p.twin + (long)blockIdx.y * total + (long)oy * Wo + (Wo - 1 - oxb);         // the same pixels of the twin's row, right to left
+    if (n == 4 && (reinterpret_cast<uintptr_t>(dt - 3) & 3) == 0) *reinterpret_cast<unsigned*>(dt - 3) = __builtin_bswap32(pk);
+    else for (int k = 0; k < n; ++k) dt[-k] = (uint8_t)(pk >> (8 * k));
+  }
+}
+
+// a member below 2 x upsampling, or one whose tile does not fit: one output pixel per thread, taps from global memory
+__global__ __launch_bounds__(256) void k_logits_ms_merge_px(MsParams p) {
+  const int Ho = p.Ho, Wo = p.Wo, align = p.align;
+  const long total = (long)Ho * Wo;
+  const long i = (long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= total) return;
+  const int oy = (int)(i / Wo), ox = (int)(i - (long)oy * Wo);
+  float acc[16];
+#pragma unroll
+  for (int ch = 0; ch < 16; ++ch) acc[ch] = 0.f;
+#pragma unroll 1
+  for (int a = 0; a < p.n_aug; ++a) {
+    const int Hi = p.Hi[a], Wi = p.Wi[a];
+    const float* lg = p.lg[a] + (long)blockIdx.y * Hi * Wi * 16;      // blockIdx.y = clip
+    int y0, y1, x0, x1; float wy, wx;
+    src_coord(oy, Hi, Ho, align, y0, y1, wy);
+    src_coord(p.flip[a] ? Wo - 1 - ox : ox, Wi, Wo, align, x0, x1, wx);
+    flip_softmax_acc(lg + ((long)y0 * Wi + x0) * 16, lg + ((long)y0 * Wi + x1) * 16, lg + ((long)y1 * Wi + x0) * 16,
+                     lg + ((long)y1 * Wi + x1) * 16, wx, wy, p.nc, p.keep, acc);
+  }
+  const uint8_t arg = (uint8_t)flip_merged_label(acc, p.nc, 1.f / (float)p.n_aug);
+  p.label[(long)blockIdx.y * total + i] = arg;
+  if (p.twin) p.twin[(long)blockIdx.y * total + (long)oy * Wo + (Wo - 1 - ox)] = arg;
 }
 
 // > 10 objects: one AOTEngine per 10 objects (engines/aot_engine.py:604-673).
@@ -853,6 +962,39 @@ extern "C" int rmem_logits_post_flip_pairs(const float* logits_nhwc16, int rows,
     hipLaunchKernelGGL(k_logits_flip_pairs_px, dim3(nblk((long)Ho * Wo), P), dim3(256), 0, (hipStream_t)stream, logits_nhwc16, P,
                        num_classes, keep_max_id, Hi, Wi, Ho, Wo, align_corners, label_u8);
   return rmem_check_launch("rmem_logits_post_flip_pairs");
+}
+#endif
+
+#ifndef RMEM_F16
+extern "C" int rmem_logits_post_ms_merge(const float* const* members, const int* Hi, const int* Wi, const int* flips, int n_aug, int clips,
+                                         int num_classes, int keep_max_id, int Ho, int Wo, int align_corners, unsigned char* label_u8,
+                                         unsigned char* twin_u8, void* stream) {
+  RMEM_REQUIRE(n_aug >= 1 && n_aug <= 8, "rmem_logits_post_ms_merge: 1..8 members (scales x flips)");
+  RMEM_REQUIRE(members && Hi && Wi && flips && label_u8, "rmem_logits_post_ms_merge: null pointer");
+  RMEM_REQUIRE(num_classes >= 1 && num_classes <= 16 && keep_max_id >= 0 && keep_max_id < num_classes,
+               "rmem_logits_post_ms_merge: 1..16 classes, 0 <= keep_max_id < num_classes");
+  RMEM_REQUIRE(clips >= 1 && clips <= 65535, "rmem_logits_post_ms_merge: 1..65535 clips");
+  RMEM_REQUIRE(Ho > 0 && Wo > 0, "rmem_logits_post_ms_merge: bad output size");
+  MsParams p;
+  bool tile = true;
+  for (int a = 0; a < 8; ++a) {
+    const bool on = a < n_aug;
+    p.lg[a] = on ? members[a] : nullptr; p.Hi[a] = on ? Hi[a] : 0; p.Wi[a] = on ? Wi[a] : 0; p.flip[a] = on ? (flips[a] != 0) : 0;
+    if (!on) continue;
+    RMEM_REQUIRE(members[a], "rmem_logits_post_ms_merge: null member pointer");
+    RMEM_REQUIRE(Hi[a] > 0 && Wi[a] > 0, "rmem_logits_post_ms_merge: bad member size");
+    RMEM_REQUIRE(((uintptr_t)members[a] % 16) == 0, "rmem_logits_post_ms_merge: member logits not 16-byte aligned");
+    // the tile route's stage holds the pixels under a tile as THIS member sees it: mirrored extents only for a flipped member
+    tile = tile && Ho >= 2 * Hi[a] && Wo >= 2 * Wi[a] && fp_extents_fit(Hi[a], Wi[a], Ho, Wo, align_corners, !flips[a], flips[a] != 0);
+  }
+  p.n_aug = n_aug; p.nc = num_classes; p.keep = keep_max_id; p.Ho = Ho; p.Wo = Wo; p.align = align_corners;
+  p.label = label_u8; p.twin = twin_u8;
+  if (tile)
+    hipLaunchKernelGGL(k_logits_ms_merge_tile, dim3(((Ho + FP_H - 1) / FP_H) * ((Wo + FP_W - 1) / FP_W), clips), dim3(128), 0,
+                       (hipStream_t)stream, p);
+  else
+    hipLaunchKernelGGL(k_logits_ms_merge_px, dim3(nblk((long)Ho * Wo), clips), dim3(256), 0, (hipStream_t)stream, p);
+  return rmem_check_launch("rmem_logits_post_ms_merge");
 }
 #endif
 

@@ -381,3 +381,29 @@ def run_clips(model, clips, rows: int = 8, lookahead: int = 4, flip: bool = Fals
             torch.cuda.current_stream(dev).wait_event(fin.event)
         yield fin.clip_id, fin.labels
     eng.synchronize()
+
+
+def run_group_multiscale(model, frames, first_labels, out_hw: Tuple[int, int], flip: bool = False, lookahead: int = 4,
+                         new_objects=None) -> torch.Tensor:
+    """Multi-scale testing (TEST_MULTISCALE, with ``flip`` also TEST_FLIP) of P clips of equal length at group speed: one GroupEngine
+    per scale and one clip_runner.MultiScaleGroupSlot, whose fused merge (rmem_logits_post_ms_merge) takes the place of the
+    per-augmentation full-size logit maps and rmem_tta_merge.  frames[s][c]: fp32 device tensors [n, 3, H_s, W_s], clip c at scale
+    s's network size (synth.network_size(..., scale=s)); first_labels[c]: fp32 [1, 1, Ho, Wo] first-frame annotation at the
+    output size; new_objects: {clip: (frame index, uint8 [Ho, Wo] device map)}.  At most 8 (scale, flip) members and 10 objects;
+    SequenceEvaluator is the per-clip reference of the same protocol and takes the cases beyond.
+    -> labels uint8 [P, n, Ho, Wo] on the device (row 0 zero: frame 0 is the given annotation), synchronised."""
+    from .clip_runner import MultiScaleGroupSlot
+    from .networks.engines.group_engine import GroupEngine
+    P = len(frames[0])
+    dev = frames[0][0].device
+    num_objs = int(max(int(m.max().item()) for m in first_labels))
+    if num_objs > model.max_obj_num:
+        raise ValueError(f'run_group_multiscale: {num_objs} objects; more than {model.max_obj_num} run on SequenceEvaluator')
+    engines = [GroupEngine(model, 2 * P if flip else P, dev.index or 0, lookahead=lookahead, flip_tta=flip) for _ in frames]
+    slot = MultiScaleGroupSlot(engines, tuple(out_hw), dev)
+    slot.start(frames, first_labels, num_objs, new_objects=new_objects)
+    while not slot.done:
+        slot.step()
+    slot.synchronize()
+    n = int(frames[0][0].shape[0])
+    return slot.labels[:, :n]

@@ -35,8 +35,11 @@ are unchanged (the reference gives every augmentation its own engine); the one c
 ops.logits_post_flip_pairs in place of ops.logits_post: the mean of the pair's softmaxes, arg-maxed, written to the clip's
 label row and mirrored to the twin's, with no full-size fp32 map in between.  clip_runner.GroupSlot mirrors the twins' frames,
 first masks, new-object overlays and fed labels.
-Clips with > 10 objects and multi-scale testing (one network size per scale, so no shared runtime) run on the per-clip engines,
-which are the drop-in API.
+MULTI-SCALE TESTING (TEST_MULTISCALE, with or without flip) needs one network size per scale, so one GroupEngine per scale, each
+a plain or flip group with its own runtime, streams and graphs: ``propagate_to_logits`` stops after the decoder and
+clip_runner.MultiScaleGroupSlot merges the engines' logits into ONE label buffer (ops.logits_post_ms_merge), from which every
+engine then updates its memory (update_from_labels resizes to its own network size).
+Clips with > 10 objects run on the per-clip engines, which are the drop-in API.
 """
 from __future__ import annotations
 
@@ -232,18 +235,38 @@ class GroupEngine:
                     post = ops.logits_post(rt.logits, ldl=16, nc=rt.nc, keep=self.obj_nums[0], Hi=rt.H4, Wi=rt.W4, Ho=Ho, Wo=Wo,
                                            align_corners=self.align_corners, label_u8=labels_u8, images=B)
                 rt._prog[pk] = [post]
-            if enc_slot is None:
-                ops.copy_async(rt.enc_now.img_in, imgs.contiguous(), B * 3 * rt.H * rt.W * 4)(self._s())
-                prog = rt.prog_encode() + rt.prog_project(None) + rt.prog_lstt(False, T, wm) + rt.prog_decode(None) + rt._prog[pk]
-            else:
-                buf = enc_slot // rt.lookahead
-                self.stream.wait_event(self._enc_done[buf])
-                prog = rt.prog_project(enc_slot) + rt.prog_lstt(False, T, wm) + rt.prog_decode(enc_slot) + rt._prog[pk]
-            self._run(f'prop{T}{int(wm)}e{enc_slot}_{labels_u8.data_ptr()}', prog)
-            if enc_slot is not None:
-                ev = self._enc_free[buf] or torch.cuda.Event()
-                ev.record(self.stream)
-                self._enc_free[buf] = ev
+            self._propagate(T, wm, rt._prog[pk], f'_{labels_u8.data_ptr()}', enc_slot, imgs)
+
+    def _propagate(self, T: int, wm: bool, post: list, tag: str, enc_slot: Optional[int], imgs: Optional[torch.Tensor]):
+        """(encode,) project, LSTT, decode, then ``post`` on the engine's stream (already current); graph key prop<T><wm>e<slot><tag>"""
+        rt, B = self.rt, self.B
+        if enc_slot is None:
+            ops.copy_async(rt.enc_now.img_in, imgs.contiguous(), B * 3 * rt.H * rt.W * 4)(self._s())
+            prog = rt.prog_encode() + rt.prog_project(None) + rt.prog_lstt(False, T, wm) + rt.prog_decode(None) + post
+        else:
+            buf = enc_slot // rt.lookahead
+            self.stream.wait_event(self._enc_done[buf])
+            prog = rt.prog_project(enc_slot) + rt.prog_lstt(False, T, wm) + rt.prog_decode(enc_slot) + post
+        self._run(f'prop{T}{int(wm)}e{enc_slot}{tag}', prog)
+        if enc_slot is not None:
+            ev = self._enc_free[buf] or torch.cuda.Event()
+            ev.record(self.stream)
+            self._enc_free[buf] = ev
+
+    def propagate_to_logits(self, enc_slot: Optional[int] = None, imgs: Optional[torch.Tensor] = None) -> torch.cuda.Event:
+        """propagate_to_labels without the post-processing launch: the group's 1/4-resolution logits stay in ``rt.logits`` (fp32
+        [B, H4*W4, 16]) for a merge across engines (clip_runner.MultiScaleGroupSlot, ops.logits_post_ms_merge).  Returns an event
+        recorded on the engine's stream behind them; ``rt.logits`` is rewritten by this engine's next propagation only.  Graph keys
+        of its own (prop..._logits): the launch lists of propagate_to_labels are not touched."""
+        self.frame_step += 1
+        self.bank.advance()
+        T, wm = self.bank.begin_propagation(self.rt)
+        with torch.cuda.stream(self.stream):
+            self._propagate(T, wm, [], '_logits', enc_slot, imgs)
+            if getattr(self, '_logits_ready', None) is None:
+                self._logits_ready = torch.cuda.Event()
+            self._logits_ready.record(self.stream)
+        return self._logits_ready
 
     # ------------------------------------------------------------------ memory update (aot_engine.py:327-369)
     def update_from_labels(self, labels_u8: torch.Tensor, skip: Iterable[int] = ()):

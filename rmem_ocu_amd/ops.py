@@ -519,6 +519,30 @@ def logits_post_flip_pairs(logits, *, nc, keep, Hi, Wi, Ho, Wo, label_u8, rows, 
     return Op(_lib.lib().rmem_logits_post_flip_pairs, args, 'rmem_logits_post_flip_pairs', (logits, label_u8))
 
 
+def logits_post_ms_merge(members, nc, keep, Ho, Wo, align_corners, label_u8, twin_u8=None, *, P) -> Op:
+    """Multi-scale (x flip) testing of clip groups, fused: members = [(logits, Hi, Wi, flip)] in the evaluator's order (scale outer,
+    flip inner), logits fp32 [P, Hi*Wi, 16] (or a view of such rows: the twins of a flip group are ``rt.logits[P:]``) at the
+    member's own size -> label_u8 [P, Ho, Wo]: the argmax of the members' mean softmax, and in twin_u8 [P, Ho, Wo] (optional) its
+    mirror along W (rmem_logits_post_ms_merge; no full-size fp32 map is written)."""
+    n = len(members)
+    if not 1 <= n <= 8:
+        raise RmemError(f'logits_post_ms_merge: 1..8 members, scales x flips (got {n})')
+    if not (1 <= nc <= 16 and 0 <= keep < nc):
+        raise RmemError(f'logits_post_ms_merge: 1..16 classes and 0 <= keep < nc (got nc={nc}, keep={keep})')
+    if P < 1:
+        raise RmemError(f'logits_post_ms_merge: at least one clip (got P={P})')
+    lgs = [m[0] for m in members]
+    _dev(*lgs, label_u8, twin_u8)
+    for lg, hi, wi, _ in members:
+        assert lg.dtype == F32 and lg.is_contiguous() and hi > 0 and wi > 0 and lg.numel() >= P * hi * wi * 16
+    for lab in (label_u8, twin_u8):
+        assert lab is None or (lab.dtype == torch.uint8 and lab.is_contiguous() and lab.numel() >= P * Ho * Wo)
+    arrs = (_ptr_array(lgs), (C.c_int * n)(*[int(m[1]) for m in members]), (C.c_int * n)(*[int(m[2]) for m in members]),
+            (C.c_int * n)(*[int(bool(m[3])) for m in members]))
+    args = (arrs[0], arrs[1], arrs[2], arrs[3], n, P, nc, keep, Ho, Wo, int(align_corners), _ptr(label_u8), _ptr(twin_u8))
+    return Op(_lib.lib().rmem_logits_post_ms_merge, args, 'rmem_logits_post_ms_merge', (arrs, lgs, label_u8, twin_u8))
+
+
 def label_to_onehot16(label, out, *, Hs, Ws, Hd, Wd, ncls=11, images=1) -> Op:
     """label [images, Hs, Ws] uint8 / fp32 -> bf16 [images, Hd*Wd, 16]"""
     _dev(label, out)
