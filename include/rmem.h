@@ -609,6 +609,24 @@ typedef struct {
 } rmem_label_route;
 int rmem_route_labels(unsigned char* rows_u8, int rows, int Ho, int Wo, const rmem_label_route* routes, void* stream);
 
+/* Label census of an annotation (or prediction) stack: which ids a frame holds, how large they are and where -- what the clip
+ * protocol (protocol.py: ids, first appearance, squeeze_idx, new-object overlays) and box consumers are built from, and what
+ * dataloaders/eval_datasets.py (VOSTest, np.unique per annotated frame) computes on the host.
+ * Census of uint8 label maps.  labels [n][H][W], contiguous.  out int32 [n][256][5]: for frame f and label value v
+ * area, xmin, ymin, xmax, ymax of the pixels equal to v; a value absent from the frame reads (0, W, H, -1, -1).
+ * Every entry of out is written by the call: the caller initialises nothing, prior contents do not matter.
+ * labels may start at any byte (16-byte loads are used between an unaligned head and tail).  Integer atomics only: the result
+ * does not depend on the order of arrival and is bit-reproducible.  Refused (non-zero, nothing launched): null labels / out, n
+ * outside 1..65535, non-positive H / W, H * W above 2^26. */
+int rmem_label_census(const unsigned char* labels, int n, int H, int W, int* out, void* stream);
+
+/* dst[f][p] = luts[(lut_per_frame ? f : 0) * 256 + src[f][p]] for p < pixels.  luts: device uint8 [n or 1][256].
+ * dst == src (in place) is allowed; partial overlap is not looked for.  src and dst may start at any byte.  The squeeze of sparse
+ * palette ids, and with one table per frame the first-frame label and the new-object overlays of a whole clip in one launch.
+ * Refused (non-zero, nothing launched): null src / dst / luts, n outside 1..65535, pixels outside 1..2^26. */
+int rmem_label_remap(const unsigned char* src, unsigned char* dst, int n, long long pixels, const unsigned char* luts,
+                     int lut_per_frame, void* stream);
+
 /* Region-similarity (Jaccard) counts per object id for one mask pair: counts[2*id] += |pred==id & gt==id|,
  * counts[2*id+1] += |pred==id | gt==id| over the n pixels whose ground truth is not `void_label`; the caller zeroes
  * counts (uint64 [2 * num_ids]).  Replaces evaluation/source/metrics.py:6-37 (db_eval_iou) per object. */

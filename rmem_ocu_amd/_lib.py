@@ -162,6 +162,8 @@ SIGNATURES = {
     'rmem_logits_post_flip_pairs': (_i, [_vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp]),
     'rmem_logits_post_ms_merge': (_i, [C.POINTER(_vp), C.POINTER(_i), C.POINTER(_i), C.POINTER(_i), _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
     'rmem_route_labels': (_i, [_vp, _i, _i, _i, _vp, _vp]),
+    'rmem_label_census': (_i, [_vp, _i, _i, _i, _vp, _vp]),
+    'rmem_label_remap': (_i, [_vp, _vp, _i, _ll, _vp, _i, _vp]),
     'rmem_mask_iou_counts': (_i, [_vp, _vp, _ll, _i, _i, _vp, _vp]),
     'rmem_clip_score_workspace_bytes': (C.c_size_t, [_i, _i, _i, _i]),
     'rmem_boundary_radius': (_i, [_i, _i, C.c_double]),

@@ -18,11 +18,15 @@ Mirrors what networks/managers/evaluator.py:330-568 does for one sequence, witho
   * annotation files are decoded on the device too: only the compressed bytes cross to it -- rmem_png_decode_labels,
     labels_from_pngs, png.decode_label_stack;
   * whole clips are scored on the device with J and the boundary accuracy F (the benchmark toolkit's db_eval_iou /
-    db_eval_boundary and its per-sequence mean, recall and decay) -- rmem_clip_score_counts, score_clip.
+    db_eval_boundary and its per-sequence mean, recall and decay) -- rmem_clip_score_counts, score_clip;
+  * what the dataset class derives from a sequence's annotations (dataloaders/eval_datasets.py, VOSTest: the object list, the
+    squeeze of sparse ids, the first label, objects that appear mid-clip) comes from a census of the decoded stack on the device
+    -- rmem_label_census / rmem_label_remap, protocol.py, run_annotated_clips, score_annotated_clip, object_boxes.
 """
 from __future__ import annotations
 
 import ctypes as C
+import itertools
 from dataclasses import dataclass
 from typing import Dict, List, Optional, Sequence, Tuple
 
@@ -197,6 +201,7 @@ class ClipScore:
     F_decay: float
     JF_mean: float
     J_tail: float
+    obj_frames: Optional[List[np.ndarray]] = None   # summarize_scores_per_object: the frames each object's statistics run over
 
 
 def summarize_scores(J: np.ndarray, F: np.ndarray, frames=slice(1, -1), tail: float = 0.25) -> ClipScore:
@@ -231,6 +236,63 @@ def score_clip(pred_u8: torch.Tensor, gt_u8: torch.Tensor, num_objs: Optional[in
         raise _lib.RmemError(f'score_clip: num_objs must be in 1..31 (got {num_objs})')
     J, F = scores_from_counts(clip_counts(pred, gt, num_objs + 1, void_label, bound_th).cpu().numpy())
     return summarize_scores(J[:, 1:], F[:, 1:], frames, tail)
+
+
+def summarize_scores_per_object(J: np.ndarray, F: np.ndarray, first_frames: Sequence[int], tail: float = 0.25) -> ClipScore:
+    """Host half of score_annotated_clip: summarize_scores with a frame range per object.  Object k (column k - 1) is scored over
+    frames first_frames[k - 1] + 1 .. n - 2: from the frame after the one that shows it to the engine to the last but one, as the
+    semi-supervised protocol does.  With every first frame 0 this is summarize_scores(J, F) field for field.  `frames` is the range
+    of an object given on frame 0, obj_frames[k - 1] the range of object k; an empty range raises RmemError naming the object."""
+    J, F = np.asarray(J, dtype=np.float64), np.asarray(F, dtype=np.float64)
+    n, num_objs = J.shape
+    first = [int(t) for t in first_frames]
+    if len(first) != num_objs or num_objs == 0:
+        raise _lib.RmemError(f'score_annotated_clip: {len(first)} first frames for {num_objs} objects')
+    if not 0.0 < tail <= 1.0:
+        raise _lib.RmemError(f'score_annotated_clip: tail must be in (0, 1] (got {tail})')
+    sels = [np.arange(t + 1, n - 1) for t in first]
+    for k, (t, sel) in enumerate(zip(first, sels), start=1):
+        if t < 0 or sel.size == 0:
+            raise _lib.RmemError(f'score_annotated_clip: object {k} first appears on frame {t} of {n}: no frame to score it on '
+                                 f'(frames {t + 1}..{n - 2})')
+    if not any(first):
+        score = summarize_scores(J, F, slice(1, -1), tail)
+        score.obj_frames = sels
+        return score
+    js = np.array([sequence_statistics(J[sel, o]) for o, sel in enumerate(sels)])
+    fs = np.array([sequence_statistics(F[sel, o]) for o, sel in enumerate(sels)])
+    jt = np.array([J[sel[int(sel.size * (1.0 - tail)):], o].mean() for o, sel in enumerate(sels)])
+    return ClipScore(J=J, F=F, frames=np.arange(n)[1:-1], J_obj_mean=js[:, 0], J_obj_recall=js[:, 1], J_obj_decay=js[:, 2],
+                     F_obj_mean=fs[:, 0], F_obj_recall=fs[:, 1], F_obj_decay=fs[:, 2], J_obj_tail=jt, J_mean=float(js[:, 0].mean()),
+                     J_recall=float(js[:, 1].mean()), J_decay=float(js[:, 2].mean()), F_mean=float(fs[:, 0].mean()),
+                     F_recall=float(fs[:, 1].mean()), F_decay=float(fs[:, 2].mean()),
+                     JF_mean=float(0.5 * (js[:, 0].mean() + fs[:, 0].mean())), J_tail=float(jt.mean()), obj_frames=sels)
+
+
+def score_annotated_clip(pred_u8: torch.Tensor, gt_u8: torch.Tensor, protocol, tail: float = 0.25, bound_th: float = 0.008) -> ClipScore:
+    """score_clip for an annotation-driven run: pred_u8 [n, H, W] in squeezed ids (what run_annotated_clips yields), gt_u8 the
+    full ground-truth stack in ORIGINAL ids, protocol the clip's protocol.ClipProtocol.  The ground truth is squeezed on the device
+    (protocol.remap_labels with lut_all; void stays void), one clip_counts call and one device-to-host copy follow, and every
+    object is summarised over its own frames (summarize_scores_per_object): an object that enters at frame t is not scored
+    against an empty ground truth on frames 1 .. t."""
+    from .protocol import remap_labels
+    pred, gt = _label_stacks(pred_u8, gt_u8, 'score_annotated_clip')
+    if not 1 <= protocol.num_objs <= 31:
+        raise _lib.RmemError(f'score_annotated_clip: num_objs must be in 1..31 (got {protocol.num_objs})')
+    gt = remap_labels(gt, protocol.lut_all)
+    J, F = scores_from_counts(clip_counts(pred, gt, protocol.num_objs + 1, 255, bound_th).cpu().numpy())
+    return summarize_scores_per_object(J[:, 1:], F[:, 1:], protocol.first_frame, tail)
+
+
+def object_boxes(labels_u8: torch.Tensor, num_objs: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Tracks for box-based consumers: (area int32 [n, num_objs], box int32 [n, num_objs, 4] = xmin, ymin, xmax, ymax) of ids
+    1..num_objs in a predicted stack [n, H, W] (uint8, device); an object absent from a frame has area 0 and box (W, H, -1, -1).
+    One census call on the current stream (protocol.label_census), no host sync."""
+    from .protocol import label_census
+    if not 1 <= int(num_objs) <= 255:
+        raise _lib.RmemError(f'object_boxes: num_objs must be in 1..255 (got {num_objs})')
+    area, box = label_census(labels_u8)
+    return area[:, 1:int(num_objs) + 1], box[:, 1:int(num_objs) + 1]
 
 
 def frames_from_jpegs(paths_or_bytes: Sequence, device, scale: float = 1.0) -> torch.Tensor:
@@ -381,6 +443,44 @@ def run_clips(model, clips, rows: int = 8, lookahead: int = 4, flip: bool = Fals
             torch.cuda.current_stream(dev).wait_event(fin.event)
         yield fin.clip_id, fin.labels
     eng.synchronize()
+
+
+def run_annotated_clips(model, clips, rows: int = 8, lookahead: int = 4, flip: bool = False):
+    """run_clips driven by annotations.  clips: an iterable of (clip_id, frames, ann_u8, frame_index) -- frames as run_clips takes
+    them, ann_u8 [m, Ho, Wo] the clip's annotation stack on the device in the files' own (sparse) ids (labels_from_pngs),
+    frame_index the clip frame of every annotated row (None: row j is frame j).  Per clip: protocol.clip_protocol (ids, first
+    appearances, squeeze, the first label and the overlays of objects that appear mid-clip, all on the device), the first label
+    resized to the network size (nearest), then the clip goes to run_clips with out_hw = (Ho, Wo).  Yields (clip_id, labels uint8
+    [n, Ho, Wo] in squeezed ids, ClipProtocol) in finish order; protocol.squeeze_idx is what save_masks takes to write the files
+    in the original ids.  A clip with more than model.max_obj_num objects raises ValueError before it is submitted; the slot's own
+    restrictions (new objects need fp32 device frames) surface as the slot's errors."""
+    from .protocol import clip_protocol
+    from .synth import network_size
+    protocols = {}
+    it = iter(clips)
+    head = next(it, None)
+    if head is None:
+        return
+    out_hw = tuple(int(v) for v in head[2].shape[-2:])
+
+    def prepared():
+        for clip_id, frames, ann_u8, frame_index in itertools.chain([head], it):
+            if tuple(int(v) for v in ann_u8.shape[-2:]) != out_hw:
+                raise ValueError(f'run_annotated_clips: clip {clip_id!r} has annotations of {tuple(ann_u8.shape[-2:])}, the run '
+                                 f'delivers {out_hw}: all clips of a run share one output size')
+            proto, first_u8, new_objects = clip_protocol(ann_u8, frame_index)
+            if proto.num_objs > model.max_obj_num:
+                raise ValueError(f'run_annotated_clips: clip {clip_id!r} has {proto.num_objs} objects, the model takes at most '
+                                 f'{model.max_obj_num}')
+            net = network_size(int(frames.shape[1]), int(frames.shape[2])) if frames.dtype == torch.uint8 else tuple(frames.shape[-2:])
+            src = first_u8.float()[None, None].contiguous()
+            first = torch.empty(1, 1, int(net[0]), int(net[1]), dtype=torch.float32, device=src.device)
+            ops.run(ops.resize_nearest_flip(src, first, flip=False), torch.cuda.current_stream(src.device).cuda_stream)
+            protocols[clip_id] = proto
+            yield clip_id, frames, first, new_objects or None
+
+    for clip_id, labels in run_clips(model, prepared(), rows=rows, lookahead=lookahead, flip=flip, out_hw=out_hw):
+        yield clip_id, labels, protocols.pop(clip_id)
 
 
 def run_group_multiscale(model, frames, first_labels, out_hw: Tuple[int, int], flip: bool = False, lookahead: int = 4,
