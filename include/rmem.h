@@ -720,6 +720,69 @@ int rmem_png_decode_labels(const unsigned char* bits, const RmemPngDesc* descs /
                            const unsigned char* lut /* device, 256 bytes, or NULL */, void* workspace,
                            unsigned char* out /* device [frames][H][W] */, int* status /* device [frames] */, void* stream);
 
+/* COCO run-length masks (maskApi.c's compressed RLE, the 'counts' of {'size': [H, W], 'counts': ...}), written from a uint8 label
+ * stack labels[frames][H][W] (contiguous, device, may start at any byte): one string per (frame, id), id = 1..num_ids; pixels with
+ * any other value belong to no mask.  One call on `stream`, no host sync, no state kept between calls; whatever must be zero is
+ * zeroed on the stream inside the call.
+ * The format: a binary mask is read column-major (position j = x * H + y); counts are the lengths of the alternating runs, zeros
+ *   first (the first count is 0 when pixel (0, 0) is set), the last run always emitted (empty mask: [H*W], full: [0, H*W]).  Count
+ *   i is x = counts[i], minus counts[i-2] when i > 2 (not >= 2); then repeat c = x & 0x1f, x >>= 5 (arithmetic), more = (c & 0x10)
+ *   ? x != -1 : x != 0, c |= 0x20 when more, emit c + 48: characters 48..111, at most 6 per count since H * W <= 2^26.
+ * The strings are packed back to back, frame-major: string (f, k) is out[offsets[f * num_ids + k - 1] : offsets[f * num_ids + k]);
+ * offsets (device, int64 [frames * num_ids + 1]) starts at 0 and grows strictly (every string has at least one byte).  Sizes are
+ * computed exactly before anything is written: offsets is always complete and exact.  When offsets[frames * num_ids] > capacity
+ * (the bytes out holds) nothing is written to out and status[0] (device, int32) is RMEM_RLE_ST_CAPACITY; otherwise it is 0.
+ * The bytes are reproducible: the only atomics are integer adds on counters that one thread owns.
+ * workspace: rmem_rle_workspace_bytes bytes, 16-byte aligned: boundary counters per (frame, id, column, block of 128 rows), the
+ * boundary positions (2 H W int32 per frame, the worst case) and per-string totals.
+ * Refused (non-zero, nothing launched): null pointers, frames outside 1..65535, non-positive H / W, H * W above 2^26, num_ids
+ * outside 1..255, capacity below 0, a misaligned workspace.
+ * Replaces stack.cpu() and a host transpose plus run-length pass per frame and object (pycocotools' encode). */
+#define RMEM_RLE_ST_CAPACITY 1
+size_t rmem_rle_workspace_bytes(int frames, int H, int W, int num_ids);   /* host only, 0 on bad geometry */
+int rmem_rle_encode_labels(const unsigned char* labels, int frames, int H, int W, int num_ids, void* workspace, unsigned char* out,
+                           long long capacity, long long* offsets /* device, int64 [frames * num_ids + 1] */,
+                           int* status /* device, int32 [1] */, void* stream);
+
+/* The inverse: nstrings run-length strings in, uint8 label maps labels[frames][H][W] (contiguous, device) out, in one call on
+ * `stream`, no host sync, no state kept between calls.  bits: total_bytes bytes on the device that hold the strings; descs[s]
+ * (device) says where string s lies, which frame it belongs to and which label value (1..255) its mask paints.  Strings are listed
+ * frame by frame (frames never decrease along descs) and their byte ranges do not overlap (each string's counts are kept in the
+ * workspace at its own offset).  Every byte of labels is written by the call; pixels under no mask are 0; where masks of one frame
+ * overlap, the string listed later wins (label[mask] = value in listing order).
+ * Reading a string: 5 bits per character, little end first, continuation bit 0x20, sign extension from bit 0x10 of a count's last
+ * character, counts[m-2] added once m > 2; the counts must be >= 0 and add up to H * W.
+ * status (device, int32 [nstrings]) is written for every string, 0 = painted.  A string with a non-zero status paints nothing and is
+ * never read or written out of range:
+ *   ST_CHAR       a byte outside 48..111
+ *   ST_TRUNCATED  the string ends inside a count (its last character has the continuation bit)
+ *   ST_LONG       a count of more than 6 characters
+ *   ST_NEGATIVE   a count below 0
+ *   ST_SUM        the counts do not add up to H * W
+ *   ST_DESC       frame outside 0..frames-1 or below the frame of the string before, value outside 1..255, or a range outside bits
+ * CHAR, TRUNCATED and LONG end the reading of a string; NEGATIVE and SUM are looked for only in strings without them.
+ * workspace: rmem_rle_decode_workspace_bytes bytes, 16-byte aligned: one int32 per byte of bits, 16 + 4 W bytes per string (the run
+ * at the top of every column), 8 per frame.
+ * Refused (non-zero, nothing launched): null pointers, total_bytes outside 0..2^31-1, nstrings outside 1..65535*255, frames outside
+ * 1..65535, non-positive H / W, H * W above 2^26, a misaligned workspace.
+ * Replaces pycocotools' decode per mask on the host and the upload of H * W bytes per frame. */
+typedef struct RmemRleDesc {
+  int frame;            /* 0..frames-1 */
+  int value;            /* 1..255: the label the mask paints */
+  long long offset;     /* of the string in bits */
+  int length;           /* of the string in bytes */
+} RmemRleDesc;
+#define RMEM_RLE_ST_CHAR 1
+#define RMEM_RLE_ST_TRUNCATED 2
+#define RMEM_RLE_ST_LONG 4
+#define RMEM_RLE_ST_NEGATIVE 8
+#define RMEM_RLE_ST_SUM 16
+#define RMEM_RLE_ST_DESC 32
+size_t rmem_rle_decode_workspace_bytes(long long nstrings, long long total_bytes, int frames, int W);   /* host only, 0 on bad arguments */
+int rmem_rle_decode_labels(const unsigned char* bits, long long total_bytes, const RmemRleDesc* descs /* device */, int nstrings, int frames,
+                           int H, int W, void* workspace, unsigned char* labels /* device [frames][H][W] */,
+                           int* status /* device [nstrings] */, void* stream);
+
 /* Baseline-JPEG files written on the device: uint8 RGB frames rgb[frames][H][W][3] (contiguous, device) in, complete .jpg files
  * packed back to back out, in one call on `stream`, no host sync, no state kept between calls.  File f is
  * out[offsets[f] : offsets[f+1]) (offsets: device, int64 [frames + 1], starts at 0); out holds frames * rmem_jpeg_encode_bound(H, W)

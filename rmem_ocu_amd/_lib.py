@@ -77,6 +77,10 @@ class PngDesc(C.Structure):
     _fields_ = [('offset', C.c_longlong), ('bytes', C.c_longlong), ('bit_depth', C.c_int), ('colour_type', C.c_int)]
 
 
+class RleDesc(C.Structure):
+    _fields_ = [('frame', C.c_int), ('value', C.c_int), ('offset', C.c_longlong), ('length', C.c_int)]
+
+
 class LabelRoute(C.Structure):
     _fields_ = [('dst', C.c_void_p), ('overlay', C.c_void_p), ('feed', C.c_void_p), ('twin', C.c_int), ('mode', C.c_int)]
 
@@ -173,6 +177,10 @@ SIGNATURES = {
     'rmem_png_encode_labels': (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
     'rmem_png_decode_workspace_bytes': (C.c_size_t, [_i, _i, _i]),
     'rmem_png_decode_labels': (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
+    'rmem_rle_workspace_bytes': (C.c_size_t, [_i, _i, _i, _i]),
+    'rmem_rle_encode_labels': (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _ll, _vp, _vp, _vp]),
+    'rmem_rle_decode_workspace_bytes': (C.c_size_t, [_ll, _ll, _i, _i]),
+    'rmem_rle_decode_labels': (_i, [_vp, _ll, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
     'rmem_split_label': (_i, [_vp, _i, _i, _vp, _ll, _vp]),
     'rmem_soft_logit_aggregate': (_i, [C.POINTER(_vp), _i, _i, _i, _i, _i, _vp, _vp]),
     'rmem_copy_async': (_i, [_vp, _vp, C.c_size_t, _vp]),

@@ -21,7 +21,10 @@ Mirrors what networks/managers/evaluator.py:330-568 does for one sequence, witho
     db_eval_boundary and its per-sequence mean, recall and decay) -- rmem_clip_score_counts, score_clip;
   * what the dataset class derives from a sequence's annotations (dataloaders/eval_datasets.py, VOSTest: the object list, the
     squeeze of sparse ids, the first label, objects that appear mid-clip) comes from a census of the decoded stack on the device
-    -- rmem_label_census / rmem_label_remap, protocol.py, run_annotated_clips, score_annotated_clip, object_boxes.
+    -- rmem_label_census / rmem_label_remap, protocol.py, run_annotated_clips, score_annotated_clip, object_boxes;
+  * the other format of the field, COCO run-length masks (BURST / TAO-VOS, YouTube-VIS, SA-V, pycocotools), is written and read
+    on the device as well: one string per frame and object out, label stacks in -- rmem_rle_encode_labels /
+    rmem_rle_decode_labels, rle.py, rle_results, labels_from_rles.
 """
 from __future__ import annotations
 
@@ -329,6 +332,31 @@ def labels_from_pngs(paths_or_bytes: Sequence, device, lut=None) -> torch.Tensor
     score_clip takes, and with gt[0].float()[None, None] the first-frame mask of a run."""
     from . import png
     return png.decode_label_stack(paths_or_bytes, device, lut)
+
+
+def labels_from_rles(frames: Sequence[Dict], size: Tuple[int, int], device, ids: Optional[Sequence] = None):
+    """A clip's run-length annotations (BURST / TAO-VOS, YouTube-VIS, SA-V: frames[f] = {track id: {'size': [H, W], 'counts':
+    bytes, str or the uncompressed list}}) -> (uint8 [n, H, W] label maps on the device, ids): track ids[i] is label value i + 1,
+    ids defaults to the sorted union of the keys; tracks not in ids are left out.  Decoded on the device (rle.decode_label_stack):
+    only the strings cross to it.  The stack feeds protocol.clip_protocol, run_annotated_clips, score_clip and
+    score_annotated_clip exactly as labels_from_pngs' does.  More than 255 tracks raise RmemError."""
+    from . import rle
+    ids = sorted({k for fr in frames for k in fr}) if ids is None else list(ids)
+    if len(ids) > 255:
+        raise _lib.RmemError(f'labels_from_rles: {len(ids)} tracks (at most 255 fit one uint8 label stack)')
+    value = {k: i + 1 for i, k in enumerate(ids)}
+    listed = [[(value[k], r) for k, r in fr.items() if k in value] for fr in frames]
+    return rle.decode_label_stack(listed, size, device), ids
+
+
+def rle_results(labels_u8: torch.Tensor, num_objs: int, squeeze_idx: Optional[Sequence[int]] = None, boxes: bool = False,
+                ascii: bool = True) -> List[Dict[int, dict]]:
+    """save_masks' twin for run-length submissions: per frame of a stack of device label maps ([n, H, W] or [H, W] uint8 --
+    FinishedClip.labels, slot.labels[c, 1:n], run_annotated_clips' output) {object id: {'size': [H, W], 'counts': str}} for the
+    objects 1..num_objs, the strings built on the device (rle.encode_label_stack).  squeeze_idx un-squeezes the keys; boxes adds
+    'area' and 'bbox' = [x, y, w, h]; ascii=False keeps the counts as bytes (pycocotools' own type)."""
+    from . import rle
+    return rle.encode_label_stack(labels_u8, num_objs, squeeze_idx, boxes=boxes, ascii=ascii)
 
 
 class SequenceEvaluator:
