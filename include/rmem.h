@@ -627,6 +627,22 @@ int rmem_label_census(const unsigned char* labels, int n, int H, int W, int* out
 int rmem_label_remap(const unsigned char* src, unsigned char* dst, int n, long long pixels, const unsigned char* luts,
                      int lut_per_frame, void* stream);
 
+/* Pair census of two uint8 label stacks: per frame the joint histogram of (value in a, value in b) -- the table behind the IoU of
+ * every predicted with every annotated object (pairs.py: pair_iou, track_iou, assign; evaluator.relabel_to_match,
+ * identity_report), where rmem_mask_iou_counts / rmem_clip_score_counts compare id i with id i only.
+ * a, b [n][H][W], contiguous; each may start at any byte, independently of the other.  out int32 [n][num_a + 2][num_b + 2]:
+ * out[f][i][j] = number of pixels of frame f with min(a, num_a + 1) == i and min(b, num_b + 1) == j.  The last row and the last
+ * column are "other": every value above num_a / num_b falls there (a void label of 255 when num_b < 255); no pixel is dropped, so
+ * every frame's table sums to H * W.  Every entry of out is written by the call (zeroed on the stream first): prior contents do not
+ * matter.  No state between calls, no workspace, no host sync.  Tables of up to rmem_label_pair_census_lds_bins() bins are kept in
+ * LDS per workgroup and flushed with global integer adds, larger ones are added to in global memory directly.  Integer atomics
+ * only: the result does not depend on the order of arrival and is bit-reproducible.  Refused (non-zero, nothing launched): null a /
+ * b / out, n outside 1..65535, non-positive H / W, H * W above 2^26 (which keeps every count inside int32), num_a or num_b
+ * outside 1..255. */
+int rmem_label_pair_census(const unsigned char* a, const unsigned char* b, int n, int H, int W, int num_a, int num_b, int* out,
+                           void* stream);
+int rmem_label_pair_census_lds_bins(void);   /* host only */
+
 /* Region-similarity (Jaccard) counts per object id for one mask pair: counts[2*id] += |pred==id & gt==id|,
  * counts[2*id+1] += |pred==id | gt==id| over the n pixels whose ground truth is not `void_label`; the caller zeroes
  * counts (uint64 [2 * num_ids]).  Replaces evaluation/source/metrics.py:6-37 (db_eval_iou) per object. */

@@ -17,20 +17,10 @@
 //   k_remap    The frame's 256-byte table is staged in LDS; 16-byte stores where dst allows them, 16-byte loads where src allows
 //              them at the same offsets (always, in place), single bytes at head and tail.
 #include <limits.h>
-#include "common.h"
+#include "label_wave.h"
 #include "../../include/rmem.h"
 
 namespace {
-constexpr int kThreads = 256;
-constexpr int kWaves = kThreads / 64;
-constexpr long kMaxPixels = 1L << 26;
-constexpr int kMaxBlocks = 2048;      // workgroups of one launch, about: enough to fill the chip, few enough to keep the flushes rare
-
-__device__ __forceinline__ int wave_isum(int v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
 __device__ __forceinline__ int wave_imin(int v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v = min(v, __shfl_xor(v, o, 64));
@@ -42,20 +32,6 @@ __device__ __forceinline__ int wave_imax(int v) {
   return v;
 }
 
-// bit j = byte j of w equals the byte replicated in v4
-__device__ __forceinline__ unsigned eq4(uint32_t w, uint32_t v4) {
-  const uint32_t t = w ^ v4;
-  const uint32_t z = ~(((t & 0x7f7f7f7fu) + 0x7f7f7f7fu) | t | 0x7f7f7f7fu);   // 0x80 in every zero byte of t, exactly
-  return (((z >> 7) * 0x00204081u) >> 21) & 0xfu;
-}
-__device__ __forceinline__ bool all_equal(uint4 w) {
-  return w.x == w.y && w.x == w.z && w.x == w.w && w.x == ((w.x >> 8) | (w.x << 24));
-}
-// byte j (0..15) of w, without indexing registers dynamically
-__device__ __forceinline__ int byte_at(uint4 w, int j) {
-  const uint32_t word = j < 8 ? (j < 4 ? w.x : w.y) : (j < 12 ? w.z : w.w);
-  return (int)((word >> (8 * (j & 3))) & 0xffu);
-}
 __device__ __forceinline__ int top_bit(unsigned m) { return 31 - __builtin_clz(m); }
 
 // Box of the bytes in m (non-zero, 16 bits): byte j is the pixel j steps after (y, x) in a row-major image W wide.
@@ -240,15 +216,6 @@ __global__ __launch_bounds__(kThreads) void k_remap(const unsigned char* src, un
     if (t < head) d[t] = lut[s[t]];
     else if (t >= 16 && t - 16 < tail) d[tail_begin + t - 16] = lut[s[tail_begin + t - 16]];
   }
-}
-
-// workgroups per frame: one 16-byte piece per thread at the finest, about kMaxBlocks in the whole launch at the coarsest
-int blocks_per_frame(long pixels, int n) {
-  const long chunks = pixels / 16 + 1;
-  long b = (chunks + kThreads - 1) / kThreads;
-  const long cap = kMaxBlocks / n > 1 ? kMaxBlocks / n : 1;
-  if (b > cap) b = cap;
-  return (int)b;
 }
 }  // namespace
 

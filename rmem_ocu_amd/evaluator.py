@@ -24,7 +24,10 @@ Mirrors what networks/managers/evaluator.py:330-568 does for one sequence, witho
     -- rmem_label_census / rmem_label_remap, protocol.py, run_annotated_clips, score_annotated_clip, object_boxes;
   * the other format of the field, COCO run-length masks (BURST / TAO-VOS, YouTube-VIS, SA-V, pycocotools), is written and read
     on the device as well: one string per frame and object out, label stacks in -- rmem_rle_encode_labels /
-    rmem_rle_decode_labels, rle.py, rle_results, labels_from_rles.
+    rmem_rle_decode_labels, rle.py, rle_results, labels_from_rles;
+  * the overlap of EVERY predicted with every annotated object, where the scorer compares id i with id i only, comes from one
+    joint histogram per frame built on the device: matching predictions whose ids are not the annotation's, and telling an
+    identity swap from a lost object -- rmem_label_pair_census, pairs.py, relabel_to_match, identity_report.
 """
 from __future__ import annotations
 
@@ -296,6 +299,80 @@ def object_boxes(labels_u8: torch.Tensor, num_objs: int) -> Tuple[torch.Tensor, 
         raise _lib.RmemError(f'object_boxes: num_objs must be in 1..255 (got {num_objs})')
     area, box = label_census(labels_u8)
     return area[:, 1:int(num_objs) + 1], box[:, 1:int(num_objs) + 1]
+
+
+def relabel_to_match(pred_u8: torch.Tensor, gt_u8: torch.Tensor, num_pred: int, num_gt: int):
+    """Predictions whose ids are not the annotation's (another run, another squeeze order, an identity-free protocol) in the
+    annotation's ids: (pred relabelled uint8 like pred_u8, mapping {pred id: gt id}, track IoU float64 [num_pred, num_gt]).
+    pairs.pair_census of the two stacks ([n, H, W] or [H, W] uint8, device; pred ids 1..num_pred, gt ids 1..num_gt, gt may carry
+    void), one readback, pairs.track_iou, pairs.assign on it (one-to-one, largest total track IoU, pairs that never overlap left
+    out), one protocol.remap_labels launch.  Predicted ids without a partner get num_gt + 1, num_gt + 2, ... in ascending order
+    (RmemError if those pass 255); predicted values above num_pred become background.  The returned stack goes into score_clip /
+    score_annotated_clip unchanged.  The assignment is on track IoU alone: DAVIS's unsupervised matching, on the mean of J and F
+    of every pair, is another rule."""
+    from . import pairs
+    from .protocol import remap_labels
+    census = pairs.pair_census(pred_u8, gt_u8, num_pred, num_gt)
+    iou = pairs.track_iou(census.cpu().numpy())
+    mapping = {i + 1: j + 1 for i, j in pairs.assign(iou)}
+    spare = int(num_gt)
+    for i in range(1, int(num_pred) + 1):
+        if i not in mapping:
+            spare += 1
+            mapping[i] = spare
+    if spare > 255:
+        raise _lib.RmemError(f'relabel_to_match: {spare - int(num_gt)} predicted ids without a partner do not fit above '
+                             f'{num_gt} annotated ids (ids end at 255)')
+    lut = np.zeros(256, dtype=np.uint8)
+    for i, j in mapping.items():
+        lut[i] = j
+    return remap_labels(pred_u8, lut), dict(sorted(mapping.items())), iou
+
+
+@dataclass
+class ObjectIdentity:
+    """identity_report's entry for one object i.  J_own: per-frame J of predicted i against annotated i [n] (empty against empty
+    is 1, as db_eval_iou has it); rival: the annotated id j != i with the largest track IoU with predicted i (the smallest such j
+    on a tie), None when predicted i overlaps no other object; rival_iou: that track IoU (0.0 without a rival); switch_frames: the
+    frames on which predicted i is not empty and overlaps some annotated j != i with a higher IoU than annotated i."""
+    J_own: np.ndarray
+    rival: Optional[int]
+    rival_iou: float
+    switch_frames: List[int]
+
+
+def identity_report(pred_u8: torch.Tensor, gt_u8: torch.Tensor, num_objs: int, void_label: Optional[int] = 255) -> Dict[int, ObjectIdentity]:
+    """Where did the mask go?  For a run whose ids are aligned with the annotation's ([n, H, W] or [H, W] uint8 device stacks,
+    objects 1..num_objs, up to 255 of them where score_clip stops at 31): {i: ObjectIdentity}.  J per object going to zero does
+    not tell an identity swap from a lost object; the overlap of predicted i with annotated j != i does.  One pairs.pair_census
+    launch and one readback.  void_label (default 255) must lie above num_objs: annotated pixels of values above num_objs, void
+    among them, count nowhere; None counts every pixel."""
+    from . import pairs
+    if void_label is not None and isinstance(num_objs, (int, np.integer)) and int(void_label) <= int(num_objs):
+        raise _lib.RmemError(f'identity_report: void_label {void_label} must lie above num_objs {num_objs} (or be None)')
+    census = pairs.pair_census(pred_u8, gt_u8, num_objs, num_objs).cpu().numpy()
+    drop = void_label is not None
+    iou, inter, union = pairs.pair_iou(census, drop_other_b=drop)
+    track = pairs.track_iou(census, drop_other_b=drop)
+    n, K = iou.shape[0], int(num_objs)
+    c = census[:, :, :-1] if drop else census
+    pred_area = c.sum(axis=2)[:, 1:K + 1]                          # [n, K]: predicted i on pixels that count
+    diag = np.arange(K)
+    own_u = union[:, diag, diag]
+    J_own = np.where(own_u == 0, 1.0, inter[:, diag, diag] / np.maximum(own_u, 1))
+    own = np.where(own_u == 0, 0.0, J_own)
+    others = np.where(np.isnan(iou), 0.0, iou)
+    others[:, diag, diag] = -1.0
+    rivals = track.copy()
+    rivals[diag, diag] = 0.0
+    report = {}
+    for k in range(K):
+        j = int(np.argmax(rivals[k]))
+        has = rivals[k, j] > 0.0
+        switched = (pred_area[:, k] > 0) & (others[:, k].max(axis=1) > own[:, k]) if K > 1 else np.zeros(n, dtype=bool)
+        report[k + 1] = ObjectIdentity(J_own=J_own[:, k], rival=j + 1 if has else None, rival_iou=float(rivals[k, j]) if has else 0.0,
+                                       switch_frames=np.nonzero(switched)[0].tolist())
+    return report
 
 
 def frames_from_jpegs(paths_or_bytes: Sequence, device, scale: float = 1.0) -> torch.Tensor:
