@@ -668,6 +668,35 @@ int rmem_boundary_radius(int H, int W, double bound_th);
 int rmem_clip_score_counts(const unsigned char* pred, const unsigned char* gt, int frames, int H, int W, int num_ids,
                            int void_label, int radius, void* workspace, unsigned long long* counts, void* stream);
 
+/* Pair boundary census: the boundary match counts of EVERY object of a with every object of b, per frame, in one call, no host
+ * sync -- what the boundary accuracy F of every (predicted, annotated) pair is made of (pairs.py: pair_boundary_counts, pair_f,
+ * pair_jf; evaluator.score_clip_objects, score_unsupervised_clip), where rmem_clip_score_counts compares id i with id i only and
+ * stops at 31 objects.  a, b: uint8 label stacks [frames][H][W], contiguous, each may start at any byte; objects are 1..num_a and
+ * 1..num_b (1 <= num <= 255), every other value is "no object".  With void = (b == void_label), A_i = (a == i) & ~void,
+ * B_j = (b == j) & ~void, d = seg2bmap at the mask's own size (rmem_clip_score_counts' boundary map) and (+) r = dilation by the
+ * disk dx^2 + dy^2 <= radius^2 with zero padding:
+ *   bnd_a[f][i] = |dA_i|                        int32 [frames][num_a + 1]
+ *   bnd_b[f][j] = |dB_j|                        int32 [frames][num_b + 1]
+ *   match[f][i][j][0] = |dA_i & (dB_j (+) r)|   int32 [frames][num_a + 1][num_b + 1][2]
+ *   match[f][i][j][1] = |dB_j & (dA_i (+) r)|
+ * Index 0 (background) is a zero row and column, so ids index directly.  For num <= 31 the diagonal equals columns 0..3 of
+ * rmem_clip_score_counts.  A void_label outside 0..255 means no void; one inside must lie above num_b.  All three outputs are
+ * zeroed on the stream by the call: prior contents do not matter.
+ * workspace: 8-byte aligned device memory of workspace_bytes bytes for the bit planes, per frame (num_a + num_b + 2) planes of
+ * H * ceil(W / 64) 64-bit words (the ids of both sides and, per side, the OR of its boundaries);
+ * rmem_pair_boundary_workspace_bytes(frames, ...) is what `frames` frames need (0 on bad arguments), 132 MB per 1080p frame at
+ * 255 + 255 ids.  The call works in passes of min(frames, workspace_bytes / one frame's bytes) frames on the stream, clears a
+ * pass's planes itself (a dirty workspace never shows) and keeps no state between calls.  Integer atomics only: the result does not
+ * depend on the order of arrival and is bit-reproducible.
+ * Refused (non-zero, nothing launched): a null pointer, num_a or num_b outside 1..255, radius outside 1..63 (the word-triple
+ * dilation reaches one word to each side), frames outside 1..65535, non-positive H / W, H * W above 2^26 (which keeps every count
+ * inside int32), H * ceil(W / 64) of 2^30 or more, a void_label in 0..num_b, a workspace smaller than one frame's planes or not
+ * 8-byte aligned. */
+size_t rmem_pair_boundary_workspace_bytes(int frames, int H, int W, int num_a, int num_b);   /* host only */
+int rmem_pair_boundary_counts(const unsigned char* a, const unsigned char* b, int frames, int H, int W, int num_a, int num_b,
+                              int void_label, int radius, void* workspace, size_t workspace_bytes, int* bnd_a, int* bnd_b,
+                              int* match, void* stream);
+
 /* Palette-PNG payloads: one zlib stream per uint8 label map [frames][H][W] (contiguous, device), in one call on `stream`, no host
  * sync.  lut: 256 device bytes applied to every label as it is read (save_mask's un-squeeze of object ids), or NULL.  The streams
  * are packed back to back: stream f is out[offsets[f] : offsets[f+1]), offsets (device, int64 [frames + 1]) starts at 0; out holds

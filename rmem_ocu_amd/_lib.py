@@ -174,6 +174,8 @@ SIGNATURES = {
     'rmem_clip_score_workspace_bytes': (C.c_size_t, [_i, _i, _i, _i]),
     'rmem_boundary_radius': (_i, [_i, _i, C.c_double]),
     'rmem_clip_score_counts': (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
+    'rmem_pair_boundary_workspace_bytes': (C.c_size_t, [_i, _i, _i, _i, _i]),
+    'rmem_pair_boundary_counts': (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, C.c_size_t, _vp, _vp, _vp, _vp]),
     'rmem_png_zlib_bound': (C.c_size_t, [_i, _i]),
     'rmem_png_workspace_bytes': (C.c_size_t, [_i, _i, _i]),
     'rmem_png_encode_labels': (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),

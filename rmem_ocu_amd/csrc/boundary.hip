@@ -22,14 +22,12 @@
 #include <math.h>
 #include <algorithm>
 #include "common.h"
+#include "bitplane_dilate.h"
 #include "../../include/rmem.h"
 
 namespace {
 
 constexpr int kNone = 256;            // a label no id equals: void, outside the image, or a neighbour the edge rule leaves out
-constexpr int kRows = 16;             // k_bmatch tile: rows
-constexpr int kWords = 16;            // k_bmatch tile: words per row (1024 pixels)
-constexpr int kLdsWords = kWords + 2; // with one halo word on each side
 
 __device__ __forceinline__ int label_at(const uint8_t* pred, const uint8_t* gt, long i, bool ok, int void_label, int& g) {
   g = kNone;
@@ -102,29 +100,10 @@ __global__ __launch_bounds__(256) void k_bplanes(const uint8_t* __restrict__ pre
   }
 }
 
-// one-pixel horizontal dilation of the 192-bit row segment (l, c, r); bit 0 of a word is its leftmost pixel
-__device__ __forceinline__ void widen1(uint64_t& l, uint64_t& c, uint64_t& r) {
-  const uint64_t nl = l | (l << 1) | (l >> 1) | (c << 63);
-  const uint64_t nc = c | (c << 1) | (l >> 63) | (c >> 1) | (r << 63);
-  const uint64_t nr = r | (r << 1) | (c >> 63) | (r >> 1);
-  l = nl; c = nc; r = nr;
-}
-
 // popcount(own & dilate(other side, disk r)) for the word at tile position (ty, tx); rows = the other side's staged rows
+// (the tile and the recurrence: bitplane_dilate.h)
 __device__ __forceinline__ unsigned match_word(uint64_t own, const uint64_t* rows, int ty, int tx, int radius) {
-  const uint64_t* p = rows + (ty + radius) * kLdsWords + tx;
-  uint64_t l = p[0], c = p[1], r = p[2];
-  const int r2 = radius * radius;
-  int h = radius;
-  for (int d = 1; d <= radius; ++d) {
-    while (h * h + d * d > r2) { widen1(l, c, r); --h; }
-    const uint64_t* a = p - d * kLdsWords;
-    const uint64_t* b = p + d * kLdsWords;
-    l |= a[0] | b[0];
-    c |= a[1] | b[1];
-    r |= a[2] | b[2];
-  }
-  return (unsigned)__popcll(own & c);
+  return (unsigned)__popcll(own & dilated_word(rows, ty, tx, radius));
 }
 
 __global__ __launch_bounds__(256) void k_bmatch(const uint64_t* __restrict__ planes, int H, int Wq, int num_ids, int radius, int xtiles,

@@ -27,7 +27,10 @@ Mirrors what networks/managers/evaluator.py:330-568 does for one sequence, witho
     rmem_rle_decode_labels, rle.py, rle_results, labels_from_rles;
   * the overlap of EVERY predicted with every annotated object, where the scorer compares id i with id i only, comes from one
     joint histogram per frame built on the device: matching predictions whose ids are not the annotation's, and telling an
-    identity swap from a lost object -- rmem_label_pair_census, pairs.py, relabel_to_match, identity_report.
+    identity swap from a lost object -- rmem_label_pair_census, pairs.py, relabel_to_match, identity_report;
+  * the boundary counts of every such pair come from the device as well, and with them the DAVIS unsupervised protocol (proposals
+    matched to annotated objects on the mean of J and F) and clip scoring for up to 255 objects -- rmem_pair_boundary_counts,
+    pairs.pair_jf, score_unsupervised_clip, score_clip_objects.
 """
 from __future__ import annotations
 
@@ -244,6 +247,94 @@ def score_clip(pred_u8: torch.Tensor, gt_u8: torch.Tensor, num_objs: Optional[in
     return summarize_scores(J[:, 1:], F[:, 1:], frames, tail)
 
 
+def _max_object(gt: torch.Tensor, void_label) -> int:
+    return int((gt if void_label is None else torch.where(gt == void_label, torch.zeros_like(gt), gt)).max().item())
+
+
+def _pair_tables(pred, gt, num_a, num_b, void_label, bound_th):
+    """pairs.pair_census and pairs.pair_boundary_counts of one pair of stacks, read back: (census, match, bnd_a, bnd_b)"""
+    from . import pairs
+    census = pairs.pair_census(pred, gt, num_a, num_b)
+    tables = pairs.pair_boundary_counts(pred, gt, num_a, num_b, void_label, bound_th)
+    return (census.cpu().numpy(),) + tuple(t.cpu().numpy() for t in tables)
+
+
+def score_clip_objects(pred_u8: torch.Tensor, gt_u8: torch.Tensor, num_objs: Optional[int] = None, frames=slice(1, -1),
+                       tail: float = 0.25, void_label: Optional[int] = 255, bound_th: float = 0.008) -> ClipScore:
+    """score_clip for 1..255 objects: the diagonal of the pair tables (pairs.pair_census, pairs.pair_boundary_counts) pushed
+    through scores_from_counts and summarize_scores.  Up to 31 objects every field equals score_clip's bit for bit -- the same
+    integers, the same float code -- as long as the annotation holds nothing but 0..num_objs and void_label: an annotated value
+    above num_objs that is not void counts nowhere here (pairs.pair_iou's drop_other_b) and as "not the object" there.
+    void_label must lie above num_objs; None means no void and is the only choice for 255 objects.  num_objs defaults to the
+    largest non-void id of the annotation (one more scalar read)."""
+    from . import pairs
+    pred, gt = _label_stacks(pred_u8, gt_u8, 'score_clip_objects')
+    if num_objs is None:
+        num_objs = _max_object(gt, void_label)
+    if isinstance(num_objs, bool) or not isinstance(num_objs, (int, np.integer)) or not 1 <= num_objs <= 255:
+        raise _lib.RmemError(f'score_clip_objects: num_objs must be in 1..255 (got {num_objs!r})')
+    K = int(num_objs)
+    census, match, bnd_a, bnd_b = _pair_tables(pred, gt, K, K, void_label, bound_th)
+    _, inter, union = pairs.pair_iou(census, drop_other_b=void_label is not None)
+    d = np.arange(K)
+    counts = np.zeros((pred.shape[0], K + 1, 6), dtype=np.int64)
+    counts[:, 1:, 0], counts[:, 1:, 1] = bnd_a[:, 1:], bnd_b[:, 1:]
+    counts[:, 1:, 2], counts[:, 1:, 3] = match[:, d + 1, d + 1, 0], match[:, d + 1, d + 1, 1]
+    counts[:, 1:, 4], counts[:, 1:, 5] = inter[:, d, d], union[:, d, d]
+    J, F = scores_from_counts(counts)
+    return summarize_scores(J[:, 1:], F[:, 1:], frames, tail)
+
+
+def summarize_unsupervised(J: np.ndarray, F: np.ndarray, gt_area: np.ndarray, gt_bnd: np.ndarray, frames=slice(None),
+                           tail: float = 0.25) -> Tuple[ClipScore, Dict[int, Optional[int]]]:
+    """Host half of score_unsupervised_clip.  J, F: float64 [n, num_pred, num_gt], every proposal against every annotated object
+    on every frame (pairs.pair_jf); gt_area, gt_bnd [n, num_gt]: the pixels and the boundary pixels of every annotated object.
+    M[i, j] = (mean J + mean F) / 2 over `frames`; pairs.assign picks the one-to-one assignment with the largest total M (every
+    proposal or every object gets a partner, whichever are fewer; among equal totals the lexicographically smallest); annotated
+    object j is scored by its partner's series, and without one against an empty prediction: J = 1 on the frames where its mask
+    is empty, else 0, F = 1 where it has no boundary, else 0 (f_measure with no predicted boundary: P = 1, R = 0) -- the
+    toolkit's zero padding.  -> (ClipScore with one column per annotated object, {annotated id: proposal id or None})."""
+    from . import pairs
+    J, F = np.asarray(J, dtype=np.float64), np.asarray(F, dtype=np.float64)
+    area, bnd = np.asarray(gt_area), np.asarray(gt_bnd)
+    if J.ndim != 3 or J.shape != F.shape or 0 in J.shape or area.shape != (J.shape[0], J.shape[2]) or bnd.shape != area.shape:
+        raise _lib.RmemError(f'score_unsupervised_clip: J and F must be [n, num_pred, num_gt], gt_area and gt_bnd [n, num_gt] '
+                             f'(got {J.shape}, {F.shape}, {area.shape}, {bnd.shape})')
+    sel = np.arange(J.shape[0])[frames]
+    if sel.size == 0:
+        raise _lib.RmemError(f'score_unsupervised_clip: no frame to score ({J.shape[0]} frames)')
+    M = 0.5 * (J[sel].mean(axis=0) + F[sel].mean(axis=0))
+    partner = {j: i for i, j in pairs.assign(M, minimum=-1.0)}        # M >= 0: no chosen pair is left out
+    Jo, Fo = np.where(area == 0, 1.0, 0.0), np.where(bnd == 0, 1.0, 0.0)
+    for j, i in partner.items():
+        Jo[:, j], Fo[:, j] = J[:, i, j], F[:, i, j]
+    mapping = {j + 1: (partner[j] + 1 if j in partner else None) for j in range(J.shape[2])}
+    return summarize_scores(Jo, Fo, frames, tail), mapping
+
+
+def score_unsupervised_clip(pred_u8: torch.Tensor, gt_u8: torch.Tensor, num_pred: int, num_gt: Optional[int] = None,
+                            frames=slice(None), tail: float = 0.25, void_label: Optional[int] = 255, bound_th: float = 0.008,
+                            max_proposals: int = 20) -> Tuple[ClipScore, Dict[int, Optional[int]]]:
+    """The DAVIS unsupervised protocol for one clip: pred_u8 holds proposals 1..num_pred whose ids mean nothing, gt_u8 annotated
+    objects 1..num_gt ([n, H, W] uint8 device stacks; num_gt defaults to the annotation's largest non-void id).  J and F of every
+    (proposal, object) pair on every frame (pairs.pair_census, pairs.pair_boundary_counts, pairs.jf_from_tables: two device calls,
+    then the readback of the four tables), then summarize_unsupervised: proposals are matched to objects on the mean of J and F, every
+    object is scored by its partner, an object without one against an empty prediction.  More than max_proposals proposals raise
+    RmemError (the benchmark allows 20).  -> (ClipScore, {annotated id: proposal id or None}); every frame is scored by default,
+    as the unsupervised protocol does."""
+    from . import pairs
+    what = 'score_unsupervised_clip'
+    if isinstance(num_pred, (int, np.integer)) and num_pred > max_proposals:
+        raise _lib.RmemError(f'{what}: {num_pred} proposals, the protocol allows max_proposals = {max_proposals}')
+    pred, gt = _label_stacks(pred_u8, gt_u8, what)
+    if num_gt is None:
+        num_gt = _max_object(gt, void_label)
+    census, match, bnd_a, bnd_b = _pair_tables(pred, gt, num_pred, num_gt, void_label, bound_th)
+    J, F = pairs.jf_from_tables(census, match, bnd_a, bnd_b, drop_other_b=void_label is not None)
+    gt_area = census.sum(axis=1)[:, 1:int(num_gt) + 1]               # void pixels sit in the "other" column, not here
+    return summarize_unsupervised(J, F, gt_area, bnd_b[:, 1:], frames, tail)
+
+
 def summarize_scores_per_object(J: np.ndarray, F: np.ndarray, first_frames: Sequence[int], tail: float = 0.25) -> ClipScore:
     """Host half of score_annotated_clip: summarize_scores with a frame range per object.  Object k (column k - 1) is scored over
     frames first_frames[k - 1] + 1 .. n - 2: from the frame after the one that shows it to the engine to the last but one, as the
@@ -309,7 +400,7 @@ def relabel_to_match(pred_u8: torch.Tensor, gt_u8: torch.Tensor, num_pred: int, 
     out), one protocol.remap_labels launch.  Predicted ids without a partner get num_gt + 1, num_gt + 2, ... in ascending order
     (RmemError if those pass 255); predicted values above num_pred become background.  The returned stack goes into score_clip /
     score_annotated_clip unchanged.  The assignment is on track IoU alone: DAVIS's unsupervised matching, on the mean of J and F
-    of every pair, is another rule."""
+    of every pair, is another rule (score_unsupervised_clip)."""
     from . import pairs
     from .protocol import remap_labels
     census = pairs.pair_census(pred_u8, gt_u8, num_pred, num_gt)

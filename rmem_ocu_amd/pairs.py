@@ -5,6 +5,10 @@ identity went, the spatio-temporal IoU of every predicted with every annotated t
 matrices association metrics start from (BURST / TAO-VOS) and the matching of predictions whose ids are not the annotation's are
 all functions of the joint histogram of (predicted value, annotated value).  pair_census builds that table on the device
 (rmem_label_pair_census, one call for the whole stack); pair_iou, track_iou and assign read it on the host after one readback.
+
+The boundary half: pair_boundary_counts gives the boundary match counts of every pair (rmem_pair_boundary_counts), pair_f turns
+them into the boundary accuracy F of every pair, pair_jf returns J and F of every pair -- what DAVIS's unsupervised matching and
+clip scoring beyond 31 objects are built on (evaluator.score_unsupervised_clip, score_clip_objects).
 """
 from __future__ import annotations
 
@@ -14,7 +18,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._codec import uint8_stack
+from ._codec import uint8_stack, workspace
 from ._lib import RmemError
 
 
@@ -31,11 +35,7 @@ def pair_census(a_u8: torch.Tensor, b_u8: torch.Tensor, num_a: int, num_b: int) 
     device stacks [n, H, W] or [H, W] of one shape on one device.  One call on the current stream, no host sync."""
     what = 'pairs.pair_census'
     num_a, num_b = _num(what, 'num_a', num_a), _num(what, 'num_b', num_b)
-    a, b = uint8_stack(a_u8, what, 'a'), uint8_stack(b_u8, what, 'b')
-    if a_u8.shape != b_u8.shape or a.device != b.device:
-        raise RmemError(f'{what}: a and b must have one shape, [n, H, W] or [H, W], on one device '
-                        f'(got {tuple(a_u8.shape)} on {a.device} and {tuple(b_u8.shape)} on {b.device})')
-    a, b = a.contiguous(), b.contiguous()
+    a, b = _stack_pair(a_u8, b_u8, what)
     n, H, W = a.shape
     out = torch.empty(n, num_a + 2, num_b + 2, dtype=torch.int32, device=a.device)
     stream = torch.cuda.current_stream(a.device)
@@ -44,6 +44,114 @@ def pair_census(a_u8: torch.Tensor, b_u8: torch.Tensor, num_a: int, num_b: int) 
     for t in (a, b):
         t.record_stream(stream)
     return out
+
+
+def _stack_pair(a_u8, b_u8, what: str) -> Tuple[torch.Tensor, torch.Tensor]:
+    a, b = uint8_stack(a_u8, what, 'a'), uint8_stack(b_u8, what, 'b')
+    if a_u8.shape != b_u8.shape or a.device != b.device:
+        raise RmemError(f'{what}: a and b must have one shape, [n, H, W] or [H, W], on one device '
+                        f'(got {tuple(a_u8.shape)} on {a.device} and {tuple(b_u8.shape)} on {b.device})')
+    return a.contiguous(), b.contiguous()
+
+
+def _void(what: str, void_label, num_b: int) -> int:
+    """the C entry points' void_label: -1 for None (no void), else an integer in num_b + 1 .. 255"""
+    if void_label is None:
+        return -1
+    if isinstance(void_label, bool) or not isinstance(void_label, (int, np.integer)) or not num_b < int(void_label) <= 255:
+        raise RmemError(f'{what}: void_label must be None or an integer above num_b = {num_b}, at most 255 (got {void_label!r})')
+    return int(void_label)
+
+
+PAIR_BOUNDARY_WORKSPACE_CAP = 256 << 20      # bytes of bit planes one call keeps, unless one frame needs more
+
+
+def pair_boundary_counts(a_u8: torch.Tensor, b_u8: torch.Tensor, num_a: int, num_b: int, void_label: Optional[int] = 255,
+                         bound_th: float = 0.008, workspace_bytes: Optional[int] = None):
+    """(match int32 [n, num_a + 1, num_b + 1, 2], bnd_a int32 [n, num_a + 1], bnd_b int32 [n, num_b + 1]) on the device: the
+    boundary pixels of every object of a and of b, and for every pair (i, j) the boundary pixels of a's object i inside b's
+    object j's boundary dilated by f_measure's disk ([..., 0]) and the other way round ([..., 1]) -- include/rmem.h,
+    rmem_pair_boundary_counts.  Row and column 0 (background) are zero.  a_u8, b_u8: uint8 device stacks [n, H, W] or [H, W] of
+    one shape on one device; pixels where b is void_label count on neither side; void_label None means no void (needed for
+    num_b = 255).  bound_th: as evaluator.boundary_radius takes it.  One call on the current stream, no host sync.
+    The bit planes live in a workspace per (device, stream) that holds as many frames as fit workspace_bytes (default: 256 MiB,
+    or one frame's planes where those are larger); the call passes over the stack that many frames at a time."""
+    what = 'pairs.pair_boundary_counts'
+    num_a, num_b = _num(what, 'num_a', num_a), _num(what, 'num_b', num_b)
+    void = _void(what, void_label, num_b)
+    a, b = _stack_pair(a_u8, b_u8, what)
+    n, H, W = a.shape
+    L = _lib.lib()
+    radius = L.rmem_boundary_radius(H, W, float(bound_th))
+    if not 1 <= radius <= 63:
+        raise RmemError(f'{what}: the dilation radius must be in 1..63 (bound_th={bound_th} gives {radius} at {H} x {W})')
+    per_frame = L.rmem_pair_boundary_workspace_bytes(1, H, W, num_a, num_b)
+    if per_frame == 0:
+        raise RmemError(f'{what}: frames of {H} x {W} are too large (H * W at most 2^26), or more than 65535 of them')
+    if workspace_bytes is None:
+        workspace_bytes = max(per_frame, min(n * per_frame, PAIR_BOUNDARY_WORKSPACE_CAP))
+    elif isinstance(workspace_bytes, bool) or not isinstance(workspace_bytes, (int, np.integer)) or workspace_bytes < per_frame:
+        raise RmemError(f'{what}: workspace_bytes must be an integer of at least one frame\'s planes, {per_frame} bytes '
+                        f'(got {workspace_bytes!r})')
+    nbytes = int(min(workspace_bytes, n * per_frame))
+    stream = torch.cuda.current_stream(a.device)
+    ws = workspace('pair_boundary', a.device, stream, nbytes)
+    match = torch.empty(n, num_a + 1, num_b + 1, 2, dtype=torch.int32, device=a.device)
+    bnd_a = torch.empty(n, num_a + 1, dtype=torch.int32, device=a.device)
+    bnd_b = torch.empty(n, num_b + 1, dtype=torch.int32, device=a.device)
+    _lib.check(L.rmem_pair_boundary_counts(a.data_ptr(), b.data_ptr(), n, H, W, num_a, num_b, void, radius, ws.data_ptr(), nbytes,
+                                           bnd_a.data_ptr(), bnd_b.data_ptr(), match.data_ptr(), stream.cuda_stream),
+               'rmem_pair_boundary_counts')
+    for t in (a, b):
+        t.record_stream(stream)
+    return match, bnd_a, bnd_b
+
+
+def _host_ints(t, ndim: int, what: str, name: str) -> np.ndarray:
+    c = t.cpu().numpy() if isinstance(t, torch.Tensor) else np.asarray(t)
+    if c.ndim != ndim or not np.issubdtype(c.dtype, np.integer):
+        raise RmemError(f'{what}: {name} must be an integer array of {ndim} dimensions (got {c.dtype} {c.shape})')
+    return c
+
+
+def pair_f(match, bnd_a, bnd_b) -> np.ndarray:
+    """The boundary accuracy F of every pair, float64 [n, num_a, num_b], from pair_boundary_counts' three tables (device tensors:
+    one readback each; or host arrays).  Entry [f, i - 1, j - 1] is object i of a against object j of b.  f_measure's edge cases,
+    by the very operations of evaluator.scores_from_counts: no boundary in a -> P = 1, R = 0; none in b -> P = 0, R = 1; neither
+    -> P = R = 1; F = 0 when P + R = 0."""
+    what = 'pairs.pair_f'
+    m, ba, bb = _host_ints(match, 4, what, 'match'), _host_ints(bnd_a, 2, what, 'bnd_a'), _host_ints(bnd_b, 2, what, 'bnd_b')
+    if m.shape != (ba.shape[0], ba.shape[1], bb.shape[1], 2) or ba.shape[0] != bb.shape[0] or ba.shape[1] < 2 or bb.shape[1] < 2:
+        raise RmemError(f'{what}: match [n, num_a + 1, num_b + 1, 2], bnd_a [n, num_a + 1] and bnd_b [n, num_b + 1] do not fit '
+                        f'(got {m.shape}, {ba.shape}, {bb.shape})')
+    fg_m, gt_m = m[:, 1:, 1:, 0].astype(np.float64), m[:, 1:, 1:, 1].astype(np.float64)
+    n_fg = np.broadcast_to(ba[:, 1:, None], fg_m.shape).astype(np.float64)
+    n_gt = np.broadcast_to(bb[:, None, 1:], fg_m.shape).astype(np.float64)
+    P = np.where(n_fg > 0, np.where(n_gt > 0, fg_m / np.maximum(n_fg, 1.0), 0.0), 1.0)
+    R = np.where(n_gt > 0, np.where(n_fg > 0, gt_m / np.maximum(n_gt, 1.0), 0.0), 1.0)
+    return np.where(P + R == 0, 0.0, 2.0 * P * R / np.where(P + R == 0, 1.0, P + R))
+
+
+def jf_from_tables(census, match, bnd_a, bnd_b, drop_other_b: bool = True) -> Tuple[np.ndarray, np.ndarray]:
+    """Host half of pair_jf: (J, F) float64 [n, num_a, num_b] from a pair census and pair_boundary_counts' tables (device tensors
+    or host arrays).  J = pair_iou with db_eval_iou's "empty union is 1" on EVERY pair, as the benchmark toolkit scores a pair of
+    empty masks; F = pair_f."""
+    iou, _, union = pair_iou(census, drop_other_b=drop_other_b)
+    F = pair_f(match, bnd_a, bnd_b)
+    if iou.shape != F.shape:
+        raise RmemError(f'pairs.jf_from_tables: the census is for {iou.shape[1:]} objects, the boundary tables for {F.shape[1:]}')
+    return np.where(union == 0, 1.0, iou), F
+
+
+def pair_jf(a_u8: torch.Tensor, b_u8: torch.Tensor, num_a: int, num_b: int, void_label: Optional[int] = 255,
+            bound_th: float = 0.008) -> Tuple[np.ndarray, np.ndarray]:
+    """(J, F) float64 [n, num_a, num_b]: the region similarity and the boundary accuracy of every object of a against every object
+    of b on every frame (jf_from_tables).  With a void_label, annotated pixels of any value above num_b count nowhere in J
+    (pair_iou's drop_other_b) and void pixels nowhere in F; without one every pixel counts.  Two device calls on the current
+    stream (pair_census, pair_boundary_counts), then the readbacks."""
+    census = pair_census(a_u8, b_u8, num_a, num_b)
+    match, bnd_a, bnd_b = pair_boundary_counts(a_u8, b_u8, num_a, num_b, void_label, bound_th)
+    return jf_from_tables(census, match, bnd_a, bnd_b, drop_other_b=void_label is not None)
 
 
 def _table(census, what: str) -> np.ndarray:
