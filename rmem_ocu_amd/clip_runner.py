@@ -15,17 +15,13 @@ from typing import List, NamedTuple, Optional, Sequence
 import torch
 
 from . import _lib, ops
+from .frame_feed import FrameFeed
 from .jpeg import JpegClip
 
 
-def _load_frames(dst: torch.Tensor, frames, i: int, m: int, stream: int):
-    """Frames i .. i+m-1 of a clip into the uint8 staging rows dst[0:m] on ``stream``: an H2D copy of pinned uint8 frames, or
-    for a JpegClip the copy of their compressed bytes and the GPU decode straight into those rows."""
-    if isinstance(frames, JpegClip):
-        frames.decode_into(list(dst[:m]), i, m, stream)
-    else:
-        hs, ws = int(frames.shape[1]), int(frames.shape[2])
-        ops.copy_async(dst, frames[i:i + m], m * hs * ws * 3)(stream)
+def clip_gap(n: int) -> int:
+    """The long_term_mem_gap of a clip of n frames (managers/evaluator.py:330-335)."""
+    return max(int(round(n / 30)), 5)
 
 
 def shard_clips(num_clips: int, rank: int, world: int, lengths: Optional[Sequence[int]] = None) -> List[int]:
@@ -174,6 +170,7 @@ class ClipSlot:
         self.cur_label = torch.zeros(out_hw[0], out_hw[1], dtype=torch.uint8, device=device)   # fixed address (graph-captured)
         self.out_hw = out_hw
         self.device = device
+        self.feed = FrameFeed(device, lookahead=lookahead)
         self.frames = None
         self.cursor = 0
         self.done = True
@@ -193,23 +190,16 @@ class ClipSlot:
             self.labels = torch.zeros(n, self.out_hw[0], self.out_hw[1], dtype=torch.uint8, device=self.device)
         eng = self.engine
         eng.restart_engine()
-        eng.long_term_mem_gap = max(int(round(n / 30)), 5)      # evaluator.py:330-335
+        eng.long_term_mem_gap = clip_gap(n)
         if self.host_u8:
-            if not frames.is_pinned():
-                raise ValueError('uint8 host frames must be in pinned memory')
-            H, W = int(first_mask.shape[-2]), int(first_mask.shape[-1])
-            hs, ws = int(frames.shape[1]), int(frames.shape[2])
-            if getattr(self, '_stage', None) is None or self._stage.shape[1:3] != (hs, ws):
-                self._stage = torch.empty(max(self.lookahead, 1), hs, ws, 3, dtype=torch.uint8, device=self.device)
-                self._first = torch.empty(1, 3, H, W, dtype=torch.float32, device=self.device)
-            self._net_hw = (H, W)
+            self.feed.check_pinned(frames)
+            self._first = self.feed.rows('first', (1, 3, int(first_mask.shape[-2]), int(first_mask.shape[-1])))
             cur = torch.cuda.current_stream(self.device)
-            # the engine's own stream may still be running the previous clip's last frames, which read _stage / _first:
+            # the engine's own stream may still be running the previous clip's last frames, which read the staging rows / _first:
             # order this clip's first-frame copy + ingest behind them (a device-side wait, no host stall)
             for e in eng.aot_engines + getattr(eng, '_pool', []):
                 cur.wait_stream(e.stream)
-            _load_frames(self._stage, frames, 0, 1, cur.cuda_stream)
-            ops.run(ops.ingest_rgb8(self._stage[0], Hs=hs, Ws=ws, Hd=H, Wd=W, out_chw=self._first[0]), cur.cuda_stream)
+            self._ingest_group(0, 1, self._first, cur.cuda_stream)
             cur.synchronize()        # once per clip: the engine works on its own stream
             eng.add_reference_frame(self._first, first_mask, obj_nums=[num_objs], frame_step=0)
         else:
@@ -226,42 +216,36 @@ class ClipSlot:
             torch.cuda.current_stream(self.device).synchronize()
             self.frames.check(self.device)
 
-    def _ingest_group(self, i: int):
-        """Host -> device copy of the next look-ahead group of uint8 frames and their resize + normalise into the encoder's
-        input buffer, all on the clip's stream."""
-        eng = self.engine
-        s = eng.aot_engines[0].stream.cuda_stream
-        la = max(self.lookahead, 1)
-        m = min(la, self.frames.shape[0] - i)
-        hs, ws = int(self.frames.shape[1]), int(self.frames.shape[2])
-        H, W = self._net_hw
-        _load_frames(self._stage, self.frames, i, m, s)
-        dst = eng.encode_inputs(la) if la > 1 else self._first
-        ops.run([ops.ingest_rgb8(self._stage[b], Hs=hs, Ws=ws, Hd=H, Wd=W, out_chw=dst[b]) for b in range(m)], s)
+    def _ingest_group(self, i: int, m: int, dst: torch.Tensor, stream: int):
+        """Host -> device copy (or decode) of uint8 frames i .. i+m-1 and their resize + normalise into dst[0:m] on ``stream``."""
+        stage = self.feed.stage(max(self.lookahead, 1), int(self.frames.shape[1]), int(self.frames.shape[2]))
+        self.feed.ingest([(self.frames, i, m, stage, dst)], stream)
 
     def step(self):
         """Propagate one frame and update the memory with the predicted labels (all asynchronous)."""
         i = self.cursor
+        s = self.engine.aot_engines[0].stream.cuda_stream          # the clip's stream
         if self.lookahead > 1:
             e = (i - 1) % self.lookahead
             if e == 0:
-                self.frames_encoded += min(self.lookahead, self.frames.shape[0] - i)
+                m = min(self.lookahead, self.frames.shape[0] - i)
+                self.frames_encoded += m
                 if self.host_u8:
-                    self._ingest_group(i)
+                    self._ingest_group(i, m, self.engine.encode_inputs(self.lookahead), s)
                     self.engine.encode_ahead(None, self.lookahead)
                 else:
                     self.engine.encode_ahead(self.frames[i:i + self.lookahead], self.lookahead)
             self.engine.propagate_to_label(None, self.cur_label, enc_slot=e)
         elif self.host_u8:
             self.frames_encoded += 1
-            self._ingest_group(i)
+            self._ingest_group(i, 1, self._first, s)
             self.engine.propagate_to_label(self._first, self.cur_label)
         else:
             self.frames_encoded += 1
             self.engine.propagate_to_label(self.frames[i:i + 1], self.cur_label)
         self.engine.update_memory_from_label_u8(self.cur_label)
         # the clip's delivered masks stay on the device
-        ops.copy_async(self.labels[i], self.cur_label, self.cur_label.numel())(self.engine.aot_engines[0].stream.cuda_stream)
+        ops.copy_async(self.labels[i], self.cur_label, self.cur_label.numel())(s)
         self.cursor += 1
         self.done = self.cursor >= self.frames.shape[0]
 
@@ -291,9 +275,11 @@ class GroupSlot:
         self.clips = self.B // 2 if self.flip else self.B        # clips the caller hands in (rows beyond them are mirrored twins)
         self.out_hw = out_hw
         self.device = device
+        self.feed = FrameFeed(device, self.B, self.clips, engine.lookahead, self.flip)
         self.cur_label = torch.zeros(self.B, out_hw[0], out_hw[1], dtype=torch.uint8, device=device)   # fixed address (graph-captured)
         self.labels: Optional[torch.Tensor] = None
         self.frames = None
+        self._frames_by_pointer = False
         self.cursor = 0
         self.done = True
         self.frames_encoded = 0             # frames that went through the encoder (reference frames + look-ahead batches)
@@ -309,7 +295,7 @@ class GroupSlot:
         assert len(frames) == self.clips and len({int(f.shape[0]) for f in frames}) == 1
         n = int(frames[0].shape[0])
         self.check_frames()                       # JPEG clips: waits for their decodes, so they can be let go of
-        if getattr(self, '_frames_by_pointer', False):
+        if self._frames_by_pointer:
             self.engine.enc_stream.synchronize()  # queued encoder launches read the previous clips' frames in place: let go of them after
         self.frames = list(frames)
         self.host_u8 = frames[0].dtype == torch.uint8
@@ -321,28 +307,21 @@ class GroupSlot:
         eng = self.engine
         self._frames_by_pointer = not self.host_u8 and eng.lookahead > 1
         eng.restart_engine()
-        eng.long_term_mem_gap = max(int(round(n / 30)), 5)      # evaluator.py:330-335
+        eng.long_term_mem_gap = clip_gap(n)
         H, W = int(first_masks[0].shape[-2]), int(first_masks[0].shape[-1])
         with torch.cuda.stream(eng.stream):
             s = eng.stream.cuda_stream
             if self.host_u8:
-                hs, ws = int(frames[0].shape[1]), int(frames[0].shape[2])
-                la = max(eng.lookahead, 1)
-                if getattr(self, '_stage', None) is None or tuple(self._stage.shape[1:3]) != (hs, ws):
-                    self._stage = torch.empty(la * self.B, hs, ws, 3, dtype=torch.uint8, device=self.device)
-                    self._first = torch.empty(self.B, 3, H, W, dtype=torch.float32, device=self.device)
-                for c in range(self.clips):
-                    if not frames[c].is_pinned():
-                        raise ValueError('uint8 host frames must be in pinned memory')
-                    _load_frames(self._stage[c:c + 1], frames[c], 0, 1, s)
-                ops.run([ops.ingest_rgb8(self._stage[c], Hs=hs, Ws=ws, Hd=H, Wd=W, out_chw=self._first[c]) for c in range(self.clips)], s)
-                imgs = self._first
+                for f in frames:
+                    self.feed.check_pinned(f)
+                self._first = self.feed.rows('first', (self.B, 3, H, W))
+                imgs = self._ingest_frame(0)
             else:
                 imgs = torch.cat([f[0:1] for f in frames] * (2 if self.flip else 1), 0)
             masks = torch.cat([m.reshape(1, 1, m.shape[-2], m.shape[-1]).float() for m in first_masks] * (2 if self.flip else 1), 0)
             if self.flip:                                       # the twins' reference frames and first masks
-                self._mirror_twins(imgs, s)
-                self._mirror_twins(masks, s)
+                self.feed.mirror(imgs[:self.clips], imgs[self.clips:], s)
+                self.feed.mirror(masks[:self.clips], masks[self.clips:], s)
         eng.add_reference_frames(imgs, masks, num_objs)
         self.frames_encoded += self.B
         self.cursor = 1
@@ -360,66 +339,15 @@ class GroupSlot:
             for c in clips:
                 c.check(self.device)
 
-    def _mirror_twins(self, rows: torch.Tensor, stream: int):
-        """rows fp32 [B, planes, H, W]: rows P..2P-1 := rows 0..P-1 mirrored along W (rmem_resize_nearest_flip_f32 at equal size)."""
-        ops.run(ops.resize_nearest_flip(rows[:self.clips], rows[self.clips:], flip=True), stream)
-
     def _kick_encoder(self, buf: int, i: int):
         """Encode frames i .. i + lookahead - 1 of every clip into look-ahead buffer ``buf`` on the engine's side stream."""
-        eng = self.engine
-        m = min(eng.lookahead, self.frames[0].shape[0] - i)
-        self.frames_encoded += self.B * m
-        stage = None
-        if self.host_u8:
-            if getattr(self, '_stage_la', None) is None or tuple(self._stage_la.shape[1:3]) != tuple(self.frames[0].shape[1:3]):
-                hs, ws = int(self.frames[0].shape[1]), int(self.frames[0].shape[2])
-                self._stage_la = torch.empty(eng.lookahead * self.B, hs, ws, 3, dtype=torch.uint8, device=self.device)
-            stage = self._stage_la
-        enc = eng.rt.enc_bufs[buf]
-        if self.host_u8:
-            enc.point_at_img_in(eng.enc_stream.cuda_stream)
-            self._fill_encoder_inputs(eng.encode_inputs(buf), i, m, stream=eng.enc_stream, stage=stage)
-        else:
-            # the encoder reads the frames where the clips are (device table of pointers, row k * B + c = frame i + k of clip c): no
-            # staging copy; rows beyond the clip's end name its last frame again (encoded, never used)
-            last = self.frames[0].shape[0] - 1
-            la, es = eng.lookahead, eng.enc_stream.cuda_stream
-            rows = [[self.frames[c][min(i + k, last)] for c in range(self.clips)] for k in range(la)]
-            if self.flip:
-                # the twins' frames of this batch: mirrored here, on the encoder stream, into this look-ahead buffer's staging rows
-                # (clip-major, one launch per clip).  The rows are read by the encoder launch that follows and rewritten on this
-                # stream only after it, and that launch is what _enc_done / _enc_free order against the propagation.
-                H, W = int(self.frames[0].shape[-2]), int(self.frames[0].shape[-1])
-                if getattr(self, '_twin_stage', None) is None or tuple(self._twin_stage.shape[-2:]) != (H, W):
-                    self._twin_stage = torch.empty(2, self.clips, la, 3, H, W, dtype=torch.float32, device=self.device)
-                st = self._twin_stage[buf]
-                ops.run([ops.resize_nearest_flip(self.frames[c][i:i + m], st[c, :m], flip=True) for c in range(self.clips)], es)
-                for k in range(la):
-                    rows[k] += [st[c, min(k, m - 1)] for c in range(self.clips)]
-            enc.set_frames([f for r in rows for f in r], es)
-        eng.encode_ahead(buf)
+        self.frames_encoded += self.B * self.feed.kick(self.engine, buf, {c: (f, i, None) for c, f in enumerate(self.frames)})
 
-    def _fill_encoder_inputs(self, dst: torch.Tensor, i: int, m: int, stream=None, stage=None):
-        """frames i .. i + m - 1 of every clip into rows k * B + c of dst ([., 3, H, W] fp32) on ``stream`` (default: the engine's
-        main stream), uint8 host frames through the staging buffer ``stage``."""
-        eng, B = self.engine, self.B
-        s = (stream or eng.stream).cuda_stream
-        stage = getattr(self, '_stage', None) if stage is None else stage
-        if self.host_u8:
-            hs, ws = int(self.frames[0].shape[1]), int(self.frames[0].shape[2])
-            H, W = int(dst.shape[-2]), int(dst.shape[-1])
-            for c in range(self.clips):
-                _load_frames(stage[c * m:(c + 1) * m], self.frames[c], i, m, s)
-            ops.run([ops.ingest_rgb8(stage[c * m + k], Hs=hs, Ws=ws, Hd=H, Wd=W, out_chw=dst[k * B + c]) for c in range(self.clips)
-                     for k in range(m)], s)
-        else:
-            fb = dst[0].numel() * 4
-            for c in range(self.clips):
-                for k in range(m):
-                    ops.copy_async(dst[k * B + c], self.frames[c][i + k], fb)(s)
-        if self.flip:                     # the twins' rows: the mirror of what was just ingested / copied, frame by frame
-            for k in range(m):
-                self._mirror_twins(dst[k * B:(k + 1) * B], s)
+    def _ingest_frame(self, i: int) -> torch.Tensor:
+        """uint8 sources: frame i of every clip into rows 0..P-1 of _first on the engine's main stream -> _first"""
+        stage = self.feed.stage(self.clips, int(self.frames[0].shape[1]), int(self.frames[0].shape[2]))
+        self.feed.ingest([(f, i, 1, stage[c:], self._first[c:]) for c, f in enumerate(self.frames)], self.engine.stream.cuda_stream)
+        return self._first
 
     def step(self, feed: Optional[torch.Tensor] = None):
         """Propagate frame ``cursor`` of every clip, deliver its labels and update the memories.  feed: uint8 [clips, Ho, Wo] device
@@ -450,13 +378,12 @@ class GroupSlot:
         else:
             self.frames_encoded += B
             if self.host_u8:
-                self._fill_encoder_inputs(self._first, i, 1)
-                imgs = self._first
+                imgs = self._ingest_frame(i)
             else:
                 with torch.cuda.stream(eng.stream):
                     imgs = torch.cat([f[i:i + 1] for f in self.frames] * (B // P), 0)
-                    if self.flip:
-                        self._mirror_twins(imgs, s)
+            if self.flip:
+                self.feed.mirror(imgs[:P], imgs[P:], s)
             if to_logits:
                 return eng.propagate_to_logits(imgs=imgs)
             eng.propagate_to_labels(self.cur_label, imgs=imgs)
@@ -473,10 +400,9 @@ class GroupSlot:
         eng, i, P = self.engine, self.cursor, self.clips
         s = eng.stream.cuda_stream
         inject = [c for c, (fi, _) in self.new_objects.items() if fi == i]
-        nb = self.cur_label[0].numel()
         if feed is not None:                          # deliver the prediction, then continue from the given labels
             self._deliver()
-            ops.copy_async(self.cur_label, feed.contiguous(), P * nb)(s)
+            ops.copy_async(self.cur_label, feed.contiguous(), P * self.cur_label[0].numel())(s)
             if self.flip:
                 with torch.cuda.stream(eng.stream):
                     self.cur_label[P:].copy_(self.cur_label[:P].flip(-1))
@@ -498,10 +424,9 @@ class GroupSlot:
         for c in inject:
             eng.add_reference_frame_for(c, self.frames[c][i], self.cur_label[c])
             if self.flip:                             # the twin is re-initialised from the mirrored frame and the mirrored label
-                if getattr(self, '_twin_ref', None) is None or self._twin_ref.shape != self.frames[c][i:i + 1].shape:
-                    self._twin_ref = torch.empty_like(self.frames[c][i:i + 1])
-                ops.run(ops.resize_nearest_flip(self.frames[c][i:i + 1], self._twin_ref, flip=True), s)
-                eng.add_reference_frame_for(P + c, self._twin_ref[0], self.cur_label[P + c])
+                twin = self.feed.rows('twin_ref', self.frames[c][i].shape)
+                self.feed.mirror(self.frames[c][i], twin, s)
+                eng.add_reference_frame_for(P + c, twin, self.cur_label[P + c])
 
     def _advance(self):
         self.cursor += 1
@@ -681,8 +606,8 @@ class RaggedGroupSlot:
     refilled before the next step.  Per step the labels of all rows are routed by ONE launch (ops.LabelRoutes, rmem_route_labels):
     delivery into each clip's stack, a new object's overlay, fed labels, the mirror into a flip twin.
 
-    Frame sources: fp32 device frames at the network size, or uint8 frames in pinned host memory (staged and ingested as in
-    GroupSlot).  All clips of a slot share the network size and the output size.  With GroupEngine(flip_tta=True) the slot takes
+    Frame sources: fp32 device frames at the network size, or uint8 frames in pinned host memory (staged and ingested by the
+    slot's FrameFeed, as GroupSlot's).  All clips of a slot share the network size and the output size.  With GroupEngine(flip_tta=True) the slot takes
     B / 2 rows of clips and makes their mirrored twins itself (frames and masks resized, THEN mirrored).
 
     Counters: row_steps_live / row_steps_idle (rows that propagated a frame of a clip / did not, per step), refills (clips that moved
@@ -695,6 +620,7 @@ class RaggedGroupSlot:
         self.clips = self.B // 2 if self.flip else self.B
         self.out_hw = (int(out_hw[0]), int(out_hw[1]))
         self.device = device
+        self.feed = FrameFeed(device, self.B, self.clips, engine.lookahead, self.flip)
         self._queue: List[_RaggedClip] = []
         self._trivial: List[_RaggedClip] = []          # single-frame clips: nothing to propagate
         self._rows = [_Row() for _ in range(self.clips)]
@@ -705,7 +631,6 @@ class RaggedGroupSlot:
         self._plan = None                              # {row: (clip, first frame, is new)} of the batch kicked ahead
         self._retired = []                             # (events, clip): frames queued launches may still read in place
         self.cur_label = None
-        self._inputs_zeroed = False                    # uint8 sources: the look-ahead encoders' inputs have been zeroed once
         self.row_steps_live = self.row_steps_idle = self.refills = self.frames_encoded = 0
 
     # ------------------------------------------------------------------ queue
@@ -734,8 +659,7 @@ class RaggedGroupSlot:
             if self._src_hw is not None and src != self._src_hw:
                 raise ValueError(f'RaggedGroupSlot: clip {clip_id!r} has uint8 frames of {src}, the slot stages {self._src_hw}: all '
                                  'clips of a slot share one frame size')
-            if self.device.type == 'cuda' and not frames.is_pinned():
-                raise ValueError('uint8 host frames must be in pinned memory')
+            self.feed.check_pinned(frames)
             if new_objects:
                 raise ValueError('new_objects: frames must be fp32 device tensors at the network size')
             self._src_hw = src
@@ -744,7 +668,7 @@ class RaggedGroupSlot:
             new_objects = {new_objects[0]: new_objects[1]}
         c.new_objects = {int(k): v for k, v in (new_objects or {}).items()}
         c.mask = first_mask
-        c.gap = max(int(round(c.n / 30)), 5) if gap is None else int(gap)
+        c.gap = clip_gap(c.n) if gap is None else int(gap)
         c.labels = torch.zeros(c.n, self.out_hw[0], self.out_hw[1], dtype=torch.uint8, device=self.device)
         c.ready = None
         if self.device.type == 'cuda':             # the stack is zeroed on the caller's stream and written on the engine's
@@ -775,29 +699,17 @@ class RaggedGroupSlot:
     def _buffers(self):
         if self.cur_label is not None:
             return
-        B, P, dev, (H, W) = self.B, self.clips, self.device, self._net_hw
-        self.cur_label = torch.zeros(B, self.out_hw[0], self.out_hw[1], dtype=torch.uint8, device=dev)   # fixed address (graph-captured)
+        dev, (H, W) = self.device, self._net_hw
+        self.cur_label = torch.zeros(self.B, self.out_hw[0], self.out_hw[1], dtype=torch.uint8, device=dev)   # fixed address (graph-captured)
         self.routes = ops.LabelRoutes(self.cur_label, dev)
-        self._first = torch.zeros(B, 3, H, W, dtype=torch.float32, device=dev)      # row-start frames (uint8 sources), look-ahead 1 input
-        if self.flip:
-            self._twin_img = torch.zeros(P, 3, H, W, dtype=torch.float32, device=dev)
-            self._twin_mask = torch.zeros(P, 1, H, W, dtype=torch.float32, device=dev)
-        if self._src_hw is not None:
-            la = max(self.engine.lookahead, 1)
-            self._stage = torch.zeros(P, *self._src_hw, 3, dtype=torch.uint8, device=dev)
-            self._stage_la = torch.zeros(la * P, *self._src_hw, 3, dtype=torch.uint8, device=dev)
-        if self._src_hw is None:
-            # what the encoder rows of idle rows name (fp32 sources are read in place): a frame the slot owns, so that no finished
-            # clip's frames are named after its end
-            self._idle_frame = torch.zeros(3, H, W, dtype=torch.float32, device=dev)
-        if self.flip and self.engine.lookahead > 1 and self._src_hw is None:
-            self._twin_stage = torch.zeros(2, P, self.engine.lookahead, 3, H, W, dtype=torch.float32, device=dev)
-        # the buffers were zeroed on the current stream; the engine's streams use them from here on
+        # it was zeroed on the current stream; the engine's streams use it from here on
         for st in (self.engine.stream, self.engine.enc_stream):
             st.wait_stream(torch.cuda.current_stream(dev))
-
-    def _mirror(self, src: torch.Tensor, dst: torch.Tensor, stream: int):
-        ops.run(ops.resize_nearest_flip(src, dst, flip=True), stream)
+        with torch.cuda.stream(self.engine.stream):    # zeroed on the stream that uses them: rows no clip has started in are encoded too
+            self._first = self.feed.rows('first', (self.B, 3, H, W), zero=True)     # row-start frames (uint8 sources), look-ahead 1 input
+        if self.flip:                                  # the twins' reference frames and first masks
+            self._twin_img = self.feed.rows('twin_img', (self.clips, 3, H, W))
+            self._twin_mask = self.feed.rows('twin_mask', (self.clips, 1, H, W))
 
     def _release(self):
         """Let go of finished clips whose frames no queued launch reads any more (no host wait: the events are only queried)."""
@@ -824,9 +736,7 @@ class RaggedGroupSlot:
                 if c.ready is not None:
                     eng.stream.wait_event(c.ready)
                 if c.host_u8:
-                    hs, ws = self._src_hw
-                    _load_frames(self._stage[p:p + 1], c.frames, 0, 1, s)
-                    ops.run(ops.ingest_rgb8(self._stage[p], Hs=hs, Ws=ws, Hd=H, Wd=W, out_chw=self._first[p]), s)
+                    self._ingest_frame(p, c.frames, 0)
                     img = self._first[p]
                 else:
                     img = c.frames[0]
@@ -834,8 +744,8 @@ class RaggedGroupSlot:
                 mine = [p] + (spare if j == 0 else [])
                 rows.append(mine); imgs.append(img); masks.append(mask); gaps.append(c.gap)
                 if self.flip:                                   # the twin: frame and first mask at the network size, THEN mirrored
-                    self._mirror(img, self._twin_img[p], s)
-                    self._mirror(mask, self._twin_mask[p], s)
+                    self.feed.mirror(img, self._twin_img[p], s)
+                    self.feed.mirror(mask, self._twin_mask[p], s)
                     rows.append([P + q for q in mine]); imgs.append(self._twin_img[p]); masks.append(self._twin_mask[p]); gaps.append(c.gap)
                 row = self._rows[p]
                 row.clip, row.i, row.live = c, 1, True
@@ -855,56 +765,16 @@ class RaggedGroupSlot:
 
     # ------------------------------------------------------------------ look-ahead encoder
     def _kick(self, buf: int, plan):
-        """Encode look-ahead batch ``plan`` ({row: (clip, first frame, new)}) into buffer ``buf`` on the engine's side stream: frames
-        first .. first + lookahead - 1 of each planned row (beyond the clip's end its last frame again: encoded, never used); rows
-        without a plan name the slot's own idle frame (uint8 sources: keep what their input rows hold).  frames_encoded counts as
-        GroupSlot does: every row of the group for each frame index of the batch that some row needs."""
-        eng, B, P = self.engine, self.B, self.clips
-        la, es = eng.lookahead, eng.enc_stream.cuda_stream
-        enc = eng.rt.enc_bufs[buf]
-        H, W = self._net_hw
-        for c, _, is_new in plan.values():
-            if is_new and c.ready is not None:                  # the first time this stream touches the clip
-                eng.enc_stream.wait_event(c.ready)
-        self.frames_encoded += B * max(min(la, c.n - i) for c, i, _ in plan.values())
-        if self._src_hw is not None:
-            enc.point_at_img_in(es)
-            dst = eng.encode_inputs(buf)
-            if not self._inputs_zeroed:                         # rows that are never ingested into must still hold numbers
-                with torch.cuda.stream(eng.enc_stream):       # (on the encoder stream, ahead of the ingests that follow)
-                    for b in eng.rt.enc_bufs:
-                        b.img_in.zero_()
-                self._inputs_zeroed = True
-            hs, ws = self._src_hw
-            for p, (c, i, _) in plan.items():
-                m = min(la, c.n - i)
-                _load_frames(self._stage_la[p * la:p * la + m], c.frames, i, m, es)
-                ops.run([ops.ingest_rgb8(self._stage_la[p * la + k], Hs=hs, Ws=ws, Hd=H, Wd=W, out_chw=dst[k * B + p]) for k in range(m)], es)
-            if self.flip:
-                for k in range(la):
-                    self._mirror(dst[k * B:k * B + P], dst[k * B + P:(k + 1) * B], es)
-        else:
-            rows = [[None] * B for _ in range(la)]
-            for p in range(P):
-                if p not in plan:
-                    for k in range(la):
-                        rows[k][p] = self._idle_frame
-                        if self.flip:
-                            rows[k][P + p] = self._idle_frame
-                    continue
-                c, i, _ = plan[p]
-                m = min(la, c.n - i)
-                for k in range(la):
-                    rows[k][p] = c.frames[min(i + k, c.n - 1)]
-                if self.flip:
-                    # the twin's frames of this batch, mirrored on the encoder stream into this buffer's staging rows; they are read by
-                    # the encoder launch that follows and rewritten on this stream only after it
-                    st = self._twin_stage[buf]
-                    self._mirror(c.frames[i:i + m], st[p, :m], es)
-                    for k in range(la):
-                        rows[k][P + p] = st[p, min(k, m - 1)]
-            enc.set_frames([f for r in rows for f in r], es)
-        eng.encode_ahead(buf)
+        """Encode look-ahead batch ``plan`` ({row: (clip, first frame, new)}) into buffer ``buf`` on the engine's side stream
+        (FrameFeed.kick; a new clip's ready event is waited for there).  frames_encoded counts as GroupSlot does: every row of the
+        group for each frame index of the batch that some row needs."""
+        feed_plan = {p: (c.frames, i, c.ready if is_new else None) for p, (c, i, is_new) in plan.items()}
+        self.frames_encoded += self.B * self.feed.kick(self.engine, buf, feed_plan)
+
+    def _ingest_frame(self, p: int, frames: torch.Tensor, i: int):
+        """uint8 sources: frame i of row p's clip into _first[p] on the engine's main stream"""
+        stage = self.feed.stage(self.clips, *self._src_hw)
+        self.feed.ingest([(frames, i, 1, stage[p:], self._first[p:])], self.engine.stream.cuda_stream)
 
     def _boundary(self):
         """Look-ahead batch boundary: the clips planned for this batch start in their rows (cold: the rows are filled from the queue
@@ -978,13 +848,11 @@ class RaggedGroupSlot:
             for p in live:
                 r = self._rows[p]
                 if r.clip.host_u8:
-                    hs, ws = self._src_hw
-                    _load_frames(self._stage[p:p + 1], r.clip.frames, r.i, 1, s)
-                    ops.run(ops.ingest_rgb8(self._stage[p], Hs=hs, Ws=ws, Hd=H, Wd=W, out_chw=self._first[p]), s)
+                    self._ingest_frame(p, r.clip.frames, r.i)
                 else:
                     ops.copy_async(self._first[p], r.clip.frames[r.i], nb)(s)
             if self.flip:
-                self._mirror(self._first[:P], self._first[P:], s)
+                self.feed.mirror(self._first[:P], self._first[P:], s)
             self.frames_encoded += B
             eng.propagate_to_labels(self.cur_label, imgs=self._first)
         self.row_steps_live += len(live)
@@ -1010,7 +878,7 @@ class RaggedGroupSlot:
             r = self._rows[p]
             eng.add_reference_frame_for(p, r.clip.frames[r.i], self.cur_label[p])
             if self.flip:
-                self._mirror(r.clip.frames[r.i], self._twin_img[p], s)
+                self.feed.mirror(r.clip.frames[r.i], self._twin_img[p], s)
                 eng.add_reference_frame_for(P + p, self._twin_img[p], self.cur_label[P + p])
         ended = []
         for p in live:

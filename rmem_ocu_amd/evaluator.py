@@ -44,6 +44,7 @@ import torch
 
 from . import _lib, ops
 from ._codec import davis_palette as _davis_palette, uint8_stack, workspace
+from .clip_runner import clip_gap
 from .networks.engines import build_engine
 
 
@@ -470,6 +471,7 @@ def frames_from_jpegs(paths_or_bytes: Sequence, device, scale: float = 1.0) -> t
     """A clip's JPEG files (paths or bytes, one size) -> fp32 [n, 3, H, W] normalised frames at the network size
     synth.network_size(h, w, scale=scale): GPU decode (rmem_jpeg_decode_batch, jpeg.CHUNK frames per call) then bicubic resize + normalise
     (rmem_ingest_rgb8), the input SequenceEvaluator.run takes."""
+    from .frame_feed import FrameFeed
     from .jpeg import CHUNK, JpegClip
     from .synth import network_size
     device = torch.device(device)
@@ -486,10 +488,9 @@ def frames_from_jpegs(paths_or_bytes: Sequence, device, scale: float = 1.0) -> t
     out = torch.empty(n, 3, H, W, dtype=torch.float32, device=device)
     rgb = torch.empty(min(n, CHUNK), hs, ws, 3, dtype=torch.uint8, device=device)     # one chunk of decoded frames at a time
     stream = torch.cuda.current_stream(device).cuda_stream
+    feed = FrameFeed(device)
     for k in range(0, n, CHUNK):
-        m = min(CHUNK, n - k)
-        clip.decode_into(list(rgb[:m]), k, m, stream)
-        ops.run([ops.ingest_rgb8(rgb[b], Hs=hs, Ws=ws, Hd=H, Wd=W, out_chw=out[k + b]) for b in range(m)], stream)
+        feed.ingest([(clip, k, min(CHUNK, n - k), rgb, out[k:])], stream)
     clip.check(device, stream=stream)
     return out
 
@@ -551,7 +552,7 @@ class SequenceEvaluator:
         Returns the uint8 label map of every frame after the first, at the original size."""
         per_scale = list(frames) if isinstance(frames, (list, tuple)) else [frames]
         n = per_scale[0].shape[0]
-        gap = max(int(round(n / 30)), 5)
+        gap = clip_gap(n)
         flips = [False, True] if self.flip else [False]
         augs = [(si, fl) for si in range(len(per_scale)) for fl in flips]      # evaluator.py:342-355 order: scale outer, flip inner
         if len(augs) > 8:

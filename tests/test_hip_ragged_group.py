@@ -334,6 +334,47 @@ def test_ragged_group_from_pinned_uint8_frames(dev):
             assert a[j].labels[1:].any()
 
 
+def test_ragged_flip_group_from_pinned_uint8_frames(dev):
+    """A flip group of four rows (two clips and their twins) fed from pinned uint8 frames, clips of (9, 12, 3) frames, with and
+    without look-ahead: exactly the labels of the same run fed with the ingested fp32 frames (the bar of
+    test_ragged_group_from_pinned_uint8_frames), and after every step the twin rows of cur_label are the mirror of the clips'."""
+    from rmem_ocu_amd import ops
+    from rmem_ocu_amd.clip_runner import RaggedGroupSlot
+    from rmem_ocu_amd.networks.engines.group_engine import GroupEngine
+    lengths = (9, 12, 3)
+    u8s, ings, masks = [], [], []
+    for n in lengths:
+        f, m = _clip(n)
+        vid = F.interpolate(f, size=OUT, mode='bilinear', align_corners=False)
+        u8 = (vid * 40.0 + 128.0).clamp(0, 255).to(torch.uint8).permute(0, 2, 3, 1).contiguous().pin_memory()
+        u8d = u8.to(dev)
+        ing = torch.empty(n, 3, *NET, dtype=torch.float32, device=dev)
+        ops.run([ops.ingest_rgb8(u8d[i], Hs=OUT[0], Ws=OUT[1], Hd=NET[0], Wd=NET[1], out_chw=ing[i]) for i in range(n)])
+        u8s.append(u8); ings.append(ing); masks.append(m.to(dev))
+    torch.cuda.synchronize()
+
+    def run(la, frames):
+        ge = GroupEngine(_model(), 4, 0, lookahead=la, flip_tta=True)
+        slot = RaggedGroupSlot(ge, OUT, dev)
+        for j in range(len(lengths)):
+            slot.submit(j, frames[j], masks[j], gap=2)
+        fins, P = {}, slot.clips
+        while not slot.done:
+            for fin in slot.step():
+                fins[fin.clip_id] = fin
+            ge.synchronize()
+            live = [p for p, r in enumerate(slot._rows) if r.live]
+            assert all(torch.equal(slot.cur_label[P + p], slot.cur_label[p].flip(-1)) for p in live), 'twin rows are not the mirror'
+        assert sorted(fins) == list(range(len(lengths)))
+        return fins
+
+    for la in (2, 1):
+        a, b = run(la, ings), run(la, u8s)
+        for j in range(len(lengths)):
+            assert torch.equal(a[j].labels[1:], b[j].labels[1:]), (la, j)
+            assert a[j].labels[1:].any()
+
+
 def test_ragged_group_table_uploads_never_race_the_gpu(dev):
     """Key table, append table, encoder frame table and the label-route table are re-sent through pinned rings every step while
     earlier steps are still queued.  A run that never synchronises delivers exactly the labels of a run that synchronises after
