@@ -643,6 +643,42 @@ int rmem_label_pair_census(const unsigned char* a, const unsigned char* b, int n
                            void* stream);
 int rmem_label_pair_census_lds_bins(void);   /* host only */
 
+/* Connected components of uint8 label stacks, their statistics and the clean-up rule built on them (components.py: fill small
+ * holes, drop small specks, keep the largest piece of every object) -- the census above knows label VALUES, this knows their PIECES.
+ * labels: uint8 [n][H][W], contiguous, device, may start at any byte.  Every value 0..255 is treated alike (0 too: its components
+ * are the holes and the background; a void label of 255 is an ordinary value); frames are independent.  Two pixels of a frame are
+ * in one component when they hold one value and a path of pixels of that value links them under `connectivity`: 4 = edge
+ * neighbours, 8 = corner neighbours too.
+ *   roots  int32 [n][H][W]: the flat index y * W + x of the component's FIRST PIXEL IN RASTER ORDER -- independent of scheduling,
+ *          comparable bit for bit.  rmem_label_components writes every entry (prior contents do not matter).
+ *   status int32 [1]: OR-ed into, never cleared (the caller zeroes it).  Every loop over parents is bounded (find: H * W steps,
+ *          union: H * W + 64 rounds); bit 0 = a union, bit 1 = a find ran into its bound.  A set bit is a bug, not a condition.
+ *   stats  int32 [n][H * W][4]: at a root's flat index (area, nb_min, nb_max, border), anywhere else (0, 256, -1, 0).  nb_min /
+ *          nb_max: the smallest / largest value among the in-frame pixels adjacent (same connectivity) to a pixel of the
+ *          component that hold another value; (256, -1) when the component is the whole frame.  border: 1 if a pixel of the
+ *          component lies in row 0, row H - 1, column 0 or column W - 1.
+ *   table  int32 [n][256][3]: per value (number of components, area of the largest, root of the largest -- the smallest root on
+ *          equal areas); (0, 0, -1) for an absent value.
+ * rmem_label_component_stats writes every entry of stats and table from labels and the roots of rmem_label_components with the
+ * same connectivity.  rmem_label_clean is one pass, every decision taken from the components of src: a pixel of value v whose
+ * component has (area, nb_min, nb_max, border) becomes
+ *   v == 0, area <= max_hole_area, border == 0 and nb_min == nb_max: nb_min (a hole wholly inside one object);
+ *   v != 0 and (area <= max_sprinkle_area, or keep_largest and the component's root is not table[f][v][2]): nb_min where
+ *          nb_min == nb_max (a speck wholly inside one object, or on the background), else 0;
+ *   and stays v otherwise.  Areas of 0 and keep_largest = 0 are the identity.  dst == src (in place) is allowed; partial overlap
+ * is not looked for; src and dst may start at any byte.
+ * The tile kernel works on tiles of th x tw pixels (rmem_label_components_tile); rmem_label_components_workspace_bytes is the bytes
+ * of roots, stats and table for n frames (0 for refused geometry).  No state between calls, no host sync, integer atomics only:
+ * bit-reproducible.  Refused (non-zero, nothing launched): a null pointer, n outside 1..65535, non-positive H / W, H * W above
+ * 2^26, a connectivity other than 4 or 8, a negative area. */
+int rmem_label_components_tile(int* th, int* tw);   /* host only */
+long long rmem_label_components_workspace_bytes(int n, int H, int W);   /* host only */
+int rmem_label_components(const unsigned char* labels, int n, int H, int W, int connectivity, int* roots, int* status, void* stream);
+int rmem_label_component_stats(const unsigned char* labels, const int* roots, int n, int H, int W, int connectivity, int* stats,
+                               int* table, void* stream);
+int rmem_label_clean(const unsigned char* src, unsigned char* dst, const int* roots, const int* stats, const int* table, int n, int H,
+                     int W, int max_hole_area, int max_sprinkle_area, int keep_largest, void* stream);
+
 /* Region-similarity (Jaccard) counts per object id for one mask pair: counts[2*id] += |pred==id & gt==id|,
  * counts[2*id+1] += |pred==id | gt==id| over the n pixels whose ground truth is not `void_label`; the caller zeroes
  * counts (uint64 [2 * num_ids]).  Replaces evaluation/source/metrics.py:6-37 (db_eval_iou) per object. */

@@ -170,6 +170,11 @@ SIGNATURES = {
     'rmem_label_remap': (_i, [_vp, _vp, _i, _ll, _vp, _i, _vp]),
     'rmem_label_pair_census': (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp]),
     'rmem_label_pair_census_lds_bins': (_i, []),
+    'rmem_label_components_tile': (_i, [C.POINTER(_i), C.POINTER(_i)]),
+    'rmem_label_components_workspace_bytes': (_ll, [_i, _i, _i]),
+    'rmem_label_components': (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp]),
+    'rmem_label_component_stats': (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp]),
+    'rmem_label_clean': (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
     'rmem_mask_iou_counts': (_i, [_vp, _vp, _ll, _i, _i, _vp, _vp]),
     'rmem_clip_score_workspace_bytes': (C.c_size_t, [_i, _i, _i, _i]),
     'rmem_boundary_radius': (_i, [_i, _i, C.c_double]),

@@ -21,17 +21,6 @@
 #include "../../include/rmem.h"
 
 namespace {
-__device__ __forceinline__ int wave_imin(int v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = min(v, __shfl_xor(v, o, 64));
-  return v;
-}
-__device__ __forceinline__ int wave_imax(int v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = max(v, __shfl_xor(v, o, 64));
-  return v;
-}
-
 __device__ __forceinline__ int top_bit(unsigned m) { return 31 - __builtin_clz(m); }
 
 // Box of the bytes in m (non-zero, 16 bits): byte j is the pixel j steps after (y, x) in a row-major image W wide.
@@ -179,9 +168,6 @@ __global__ __launch_bounds__(kThreads) void k_census(const unsigned char* __rest
 __device__ __forceinline__ uint32_t map4(uint32_t w, const unsigned char* lut) {
   return (uint32_t)lut[w & 0xffu] | ((uint32_t)lut[(w >> 8) & 0xffu] << 8) | ((uint32_t)lut[(w >> 16) & 0xffu] << 16) |
          ((uint32_t)lut[w >> 24] << 24);
-}
-__device__ __forceinline__ uint32_t load4(const unsigned char* p) {
-  return (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24);
 }
 
 // src and dst may be the same frame: every byte is read and written by the same thread, and read first.

@@ -1,5 +1,5 @@
-// What the kernels that walk uint8 label stacks 16 bytes per lane share (label_census.hip, label_pairs.hip): the byte compares of
-// a lane's piece, the wave's integer sum and the bound on the grid.
+// What the kernels that walk uint8 label stacks 16 bytes per lane share (label_census.hip, label_pairs.hip, label_components.hip):
+// the byte compares of a lane's piece, the wave's integer sum, minimum and maximum, the unaligned word and the bound on the grid.
 #pragma once
 #include "common.h"
 
@@ -13,6 +13,22 @@ __device__ __forceinline__ int wave_isum(int v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
   return v;
+}
+
+__device__ __forceinline__ int wave_imin(int v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v = min(v, __shfl_xor(v, o, 64));
+  return v;
+}
+__device__ __forceinline__ int wave_imax(int v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v = max(v, __shfl_xor(v, o, 64));
+  return v;
+}
+
+// four bytes that may start anywhere, as one little-endian word
+__device__ __forceinline__ uint32_t load4(const unsigned char* p) {
+  return (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24);
 }
 
 // bit j = byte j of w equals the byte replicated in v4

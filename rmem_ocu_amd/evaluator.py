@@ -393,6 +393,27 @@ def object_boxes(labels_u8: torch.Tensor, num_objs: int) -> Tuple[torch.Tensor, 
     return area[:, 1:int(num_objs) + 1], box[:, 1:int(num_objs) + 1]
 
 
+def clean_masks(labels_u8: torch.Tensor, fill_holes: int = 0, remove_specks: int = 0, keep_largest: bool = False,
+                connectivity: int = 8) -> torch.Tensor:
+    """The usual clean-up of delivered labels before they are written or scored, on the device: a new uint8 stack like labels_u8
+    ([n, H, W] or [H, W], device) in which holes of up to fill_holes pixels wholly inside one object are filled with it, pieces of
+    up to remove_specks pixels are dropped and, with keep_largest, only the largest piece of every object stays (a dropped piece
+    becomes the one value around it, or background) -- components.clean_labels, whose docstring has the rule; every decision is
+    taken from the input's connected components, frame by frame.  Something the caller applies to the labels a run delivered:
+    nothing here feeds it back into a memory bank.  The current stream; one 4-byte readback at the end."""
+    from .components import clean_labels
+    return clean_labels(labels_u8, max_hole_area=fill_holes, max_sprinkle_area=remove_specks, keep_largest=keep_largest,
+                        connectivity=connectivity)
+
+
+def object_fragments(labels_u8: torch.Tensor, num_objs: int, connectivity: int = 8) -> torch.Tensor:
+    """int32 [n, num_objs + 1] on the device: into how many connected pieces every value 0..num_objs of a predicted stack
+    [n, H, W] (uint8, device) falls on every frame -- 1 for a mask in one piece, 0 for an absent object
+    (components.object_fragments).  The current stream, no host sync."""
+    from .components import object_fragments as fragments
+    return fragments(labels_u8, num_objs, connectivity)
+
+
 def relabel_to_match(pred_u8: torch.Tensor, gt_u8: torch.Tensor, num_pred: int, num_gt: int):
     """Predictions whose ids are not the annotation's (another run, another squeeze order, an identity-free protocol) in the
     annotation's ids: (pred relabelled uint8 like pred_u8, mapping {pred id: gt id}, track IoU float64 [num_pred, num_gt]).
