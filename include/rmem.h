@@ -679,6 +679,49 @@ int rmem_label_component_stats(const unsigned char* labels, const int* roots, in
 int rmem_label_clean(const unsigned char* src, unsigned char* dst, const int* roots, const int* stats, const int* table, int n, int H,
                      int W, int max_hole_area, int max_sprinkle_area, int keep_largest, void* stream);
 
+/* Label stacks traced into polygon rings: the outer contours and the holes of every object of every frame, the last way a run's
+ * labels leave the device (polygons.py: trace, trace_label_stack; evaluator.polygon_results) -- what CVAT / Labelme tracks and
+ * COCO `segmentation` lists are made of, and what labels.cpu() plus a sequential border follower per frame and object computes.
+ * labels: uint8 [n][H][W], contiguous, device, may start at any byte.  Objects are the values 1..num_objs; 0 and every value above
+ * num_objs are "not an object".  Frames are independent.  connectivity (4 or 8) is that of the objects.
+ * Edges.  Vertices are pixel corners (x, y), 0 <= x <= W, 0 <= y <= H, y pointing down.  A pixel (y, x) of object v owns a
+ * directed unit edge on each side whose neighbour does not hold v (a side on the frame's edge is such a side); the object lies on
+ * the right of the direction of travel:
+ *   side 0 top    (x, y)         -> (x + 1, y)      east        side 1 right  (x + 1, y)     -> (x + 1, y + 1)  south
+ *   side 2 bottom (x + 1, y + 1) -> (x, y + 1)      west        side 3 left   (x, y + 1)     -> (x, y)          north
+ * The edge id is (y * W + x) * 4 + side.
+ * Successor.  For an edge of pixel (y, x), side s, A is the pixel ahead on the right and B the pixel ahead on the left of its end
+ * vertex: s = 0: A (y, x + 1), B (y - 1, x + 1); s = 1: A (y + 1, x), B (y + 1, x + 1); s = 2: A (y, x - 1), B (y + 1, x - 1);
+ * s = 3: A (y - 1, x), B (y - 1, x - 1).  a / b: A / B holds v (false outside the frame).  8: left turn if b, else straight if a,
+ * else right turn.  4: right turn if not a, else straight if not b, else left turn.  Right turn: side (s + 1) % 4 of the same
+ * pixel; straight: side s of A; left turn: side (s + 3) % 4 of B.  This is a permutation of a frame's edges; its cycles are the
+ * rings.
+ * Rings.  A ring's start edge is its smallest edge id.  Its vertices are the start corners of those of its edges whose heading
+ * differs from their predecessor's, in walk order beginning at the start edge (which need not be a corner itself; for a hole it
+ * usually is not).  area2 is the shoelace sum of (x_i * y_{i+1} - x_{i+1} * y_i): positive for an outer ring, negative for a
+ * hole.  Collinear vertices never occur; a vertex can occur twice in one ring (the saddle between two diagonal pixels under 8).
+ * Output, all device, in the order (frame, start edge):
+ *   rings  int32 [max_edges / 4 + 1][8]: (frame, value, first vertex, vertex count, area2, start edge id, edge count, 0); a ring's
+ *          vertices are contiguous, and ring r + 1 starts where ring r ends.
+ *   verts  int32 [max_edges][2]: (x, y).
+ *   counts int32 [4]: (edges E, rings R, vertices V, status).
+ * Prior contents of the outputs do not matter; entries beyond R and V are not written.  E above max_edges: status =
+ * RMEM_POLY_ST_CAPACITY, counts[0] is still the exact E (2^31 - 1 where it is larger), R = V = 0, nothing is written to rings or
+ * verts.  Every loop is bounded; RMEM_POLY_ST_LINK (a successor was not found among its pixel's edges) and RMEM_POLY_ST_ORDER (a
+ * ring position out of range) say that one ran out or an index went astray: a bug, never a condition.
+ * workspace: rmem_label_polygons_workspace_bytes(n, H, W, max_edges) bytes of device memory, 16-byte aligned (0 for refused
+ * arguments): 40 bytes per edge of capacity plus 4 per walk unit.  A walk unit is rmem_label_polygons_unit() pixels of one row.
+ * No state between calls, no host sync, 15 + ceil(log2(min(max_edges, 4 H W))) launches on `stream`, integer arithmetic only:
+ * bit-reproducible.  Refused (non-zero, nothing launched): a null pointer, n outside 1..65535, non-positive H / W, H * W above
+ * 2^26, num_objs outside 1..255, a connectivity other than 4 or 8, max_edges below 4, a workspace smaller than the query says. */
+#define RMEM_POLY_ST_CAPACITY 1
+#define RMEM_POLY_ST_LINK 2
+#define RMEM_POLY_ST_ORDER 4
+int rmem_label_polygons_unit(void);   /* host only */
+size_t rmem_label_polygons_workspace_bytes(int n, int H, int W, int max_edges);   /* host only */
+int rmem_label_polygons(const unsigned char* labels, int n, int H, int W, int num_objs, int connectivity, int max_edges,
+                        void* workspace, size_t workspace_bytes, int* rings, int* verts, int* counts, void* stream);
+
 /* Region-similarity (Jaccard) counts per object id for one mask pair: counts[2*id] += |pred==id & gt==id|,
  * counts[2*id+1] += |pred==id | gt==id| over the n pixels whose ground truth is not `void_label`; the caller zeroes
  * counts (uint64 [2 * num_ids]).  Replaces evaluation/source/metrics.py:6-37 (db_eval_iou) per object. */
