@@ -1,5 +1,6 @@
 """Host plumbing the image codecs (png, jpeg) and the clip scorer (evaluator.clip_counts) share: the palette, streams, the
-grow-only device workspaces, the pinned readback of packed files, the check of a label stack, a packed clip's copy on a device."""
+grow-only device workspaces, the pinned readback of packed files, the check of a label stack, a packed clip's copy on a device.
+Device plumbing lives here; the argument checks of the modules on label stacks (pairs, components, polygons, rle) are _labels'."""
 from __future__ import annotations
 
 from typing import Dict, List, Optional, Tuple

@@ -12,14 +12,12 @@ from __future__ import annotations
 import ctypes as C
 from typing import Optional, Tuple
 
-import numpy as np
 import torch
 
 from . import _lib
-from ._codec import uint8_stack, workspace
+from ._codec import workspace
+from ._labels import connectivity as _connectivity, frames_per_pass, int_in, is_int, stack as _frames
 from ._lib import RmemError
-
-COMPONENTS_WORKSPACE_CAP = 256 << 20         # bytes of roots, statistics and tables one pass of clean_labels keeps, unless one frame needs more
 
 
 def tile() -> Tuple[int, int]:
@@ -29,24 +27,10 @@ def tile() -> Tuple[int, int]:
     return th.value, tw.value
 
 
-def _connectivity(what: str, connectivity) -> int:
-    if isinstance(connectivity, bool) or not isinstance(connectivity, (int, np.integer)) or int(connectivity) not in (4, 8):
-        raise RmemError(f'{what}: connectivity must be 4 or 8 (got {connectivity!r})')
-    return int(connectivity)
-
-
 def _area(what: str, name: str, v) -> int:
-    if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or int(v) < 0:
+    if not is_int(v) or int(v) < 0:
         raise RmemError(f'{what}: {name} must be a non-negative integer (got {v!r})')
     return int(min(int(v), 2 ** 31 - 1))
-
-
-def _frames(what: str, labels_u8) -> torch.Tensor:
-    a = uint8_stack(labels_u8, what).contiguous()
-    n, H, W = a.shape
-    if _lib.lib().rmem_label_components_workspace_bytes(1, H, W) == 0 or n > 65535:
-        raise RmemError(f'{what}: labels of {n} x {H} x {W} are too large (H * W at most 2^26, at most 65535 frames)')
-    return a
 
 
 def _status(what: str, status, device) -> torch.Tensor:
@@ -144,12 +128,7 @@ def clean_labels(labels_u8: torch.Tensor, max_hole_area: int = 0, max_sprinkle_a
         dst = out.view(a.shape)
     L = _lib.lib()
     per_frame = int(L.rmem_label_components_workspace_bytes(1, H, W))
-    if workspace_bytes is None:
-        workspace_bytes = max(per_frame, min(n * per_frame, COMPONENTS_WORKSPACE_CAP))
-    elif isinstance(workspace_bytes, bool) or not isinstance(workspace_bytes, (int, np.integer)) or workspace_bytes < per_frame:
-        raise RmemError(f'{what}: workspace_bytes must be an integer of at least one frame\'s need, {per_frame} bytes '
-                        f'(got {workspace_bytes!r})')
-    k = int(min(n, workspace_bytes // per_frame))                  # frames per pass
+    k = frames_per_pass(what, n, per_frame, workspace_bytes, 'one frame\'s need')[1]
     stream = torch.cuda.current_stream(a.device)
     own_status = status is None
     st = torch.zeros(1, dtype=torch.int32, device=a.device) if own_status else _status(what, status, a.device)
@@ -179,9 +158,7 @@ def object_fragments(labels_u8: torch.Tensor, num_objs: int, connectivity: int =
     """int32 [n, num_objs + 1] on the device: the number of pieces of every value 0..num_objs on every frame (column 0 of
     component_stats' table; column 0 here is the background's pieces).  1 everywhere for a clean prediction; a 3 says that the
     object's mask fell into three parts on that frame.  No host sync."""
-    what = 'components.object_fragments'
-    if isinstance(num_objs, bool) or not isinstance(num_objs, (int, np.integer)) or not 1 <= int(num_objs) <= 255:
-        raise RmemError(f'{what}: num_objs must be an integer in 1..255 (got {num_objs!r})')
+    K = int_in('components.object_fragments', 'num_objs', num_objs, 1, 255)
     roots, _ = label_components(labels_u8, connectivity)
     _, table = component_stats(labels_u8, roots, connectivity)
-    return table[:, :int(num_objs) + 1, 0].contiguous()
+    return table[:, :K + 1, 0].contiguous()

@@ -207,8 +207,8 @@ __global__ __launch_bounds__(kThreads) void k_remap(const unsigned char* src, un
 
 extern "C" int rmem_label_census(const unsigned char* labels, int n, int H, int W, int* out, void* stream) {
   RMEM_REQUIRE(labels && out, "rmem_label_census: null pointer (labels and out are required)");
-  RMEM_REQUIRE(n >= 1 && n <= 65535, "rmem_label_census: n must be in 1..65535");
-  RMEM_REQUIRE(H >= 1 && W >= 1 && (long)H * W <= kMaxPixels, "rmem_label_census: H and W must be positive, H * W at most 2^26");
+  RMEM_REQUIRE(n >= 1 && n <= kMaxFrames, "rmem_label_census: n must be in 1..65535");
+  RMEM_REQUIRE(stack_geometry_ok(n, H, W), "rmem_label_census: H and W must be positive, H * W at most 2^26");
   const int HW = H * W, entries = n * 256;
   hipLaunchKernelGGL(k_census_init, dim3((entries + kThreads - 1) / kThreads), dim3(kThreads), 0, (hipStream_t)stream, out, entries, H, W);
   hipLaunchKernelGGL(k_census, dim3(blocks_per_frame(HW, n), n), dim3(kThreads), 0, (hipStream_t)stream, labels, HW, W, out);
@@ -218,7 +218,7 @@ extern "C" int rmem_label_census(const unsigned char* labels, int n, int H, int 
 extern "C" int rmem_label_remap(const unsigned char* src, unsigned char* dst, int n, long long pixels, const unsigned char* luts,
                                 int lut_per_frame, void* stream) {
   RMEM_REQUIRE(src && dst && luts, "rmem_label_remap: null pointer (src, dst and luts are required)");
-  RMEM_REQUIRE(n >= 1 && n <= 65535, "rmem_label_remap: n must be in 1..65535");
+  RMEM_REQUIRE(n >= 1 && n <= kMaxFrames, "rmem_label_remap: n must be in 1..65535");
   RMEM_REQUIRE(pixels >= 1 && pixels <= kMaxPixels, "rmem_label_remap: pixels must be in 1..2^26");
   hipLaunchKernelGGL(k_remap, dim3(blocks_per_frame((long)pixels, n), n), dim3(kThreads), 0, (hipStream_t)stream, src, dst, (int)pixels,
                      luts, lut_per_frame);

@@ -411,7 +411,6 @@ __global__ __launch_bounds__(kThreads) void k_cc_clean(const unsigned char* src,
   }
 }
 
-inline bool geometry_ok(int H, int W) { return H >= 1 && W >= 1 && (long)H * W <= kMaxPixels; }
 }  // namespace
 
 extern "C" int rmem_label_components_tile(int* th, int* tw) {
@@ -422,15 +421,15 @@ extern "C" int rmem_label_components_tile(int* th, int* tw) {
 }
 
 extern "C" long long rmem_label_components_workspace_bytes(int n, int H, int W) {
-  if (n < 1 || n > 65535 || !geometry_ok(H, W)) return 0;
+  if (!stack_geometry_ok(n, H, W)) return 0;
   return (long long)n * ((long long)H * W * 20 + 256 * 3 * 4);     // roots, stats (4 ints per pixel), table
 }
 
 extern "C" int rmem_label_components(const unsigned char* labels, int n, int H, int W, int connectivity, int* roots, int* status,
                                      void* stream) {
   RMEM_REQUIRE(labels && roots && status, "rmem_label_components: null pointer (labels, roots and status are required)");
-  RMEM_REQUIRE(n >= 1 && n <= 65535, "rmem_label_components: n must be in 1..65535");
-  RMEM_REQUIRE(geometry_ok(H, W), "rmem_label_components: H and W must be positive, H * W at most 2^26");
+  RMEM_REQUIRE(n >= 1 && n <= kMaxFrames, "rmem_label_components: n must be in 1..65535");
+  RMEM_REQUIRE(stack_geometry_ok(n, H, W), "rmem_label_components: H and W must be positive, H * W at most 2^26");
   RMEM_REQUIRE(connectivity == 4 || connectivity == 8, "rmem_label_components: connectivity must be 4 or 8");
   const int HW = H * W, conn8 = connectivity == 8;
   const int tiles_x = (W + kTW - 1) / kTW, tiles_y = (H + kTH - 1) / kTH;
@@ -444,8 +443,8 @@ extern "C" int rmem_label_components(const unsigned char* labels, int n, int H, 
 extern "C" int rmem_label_component_stats(const unsigned char* labels, const int* roots, int n, int H, int W, int connectivity, int* stats,
                                           int* table, void* stream) {
   RMEM_REQUIRE(labels && roots && stats && table, "rmem_label_component_stats: null pointer (labels, roots, stats and table are required)");
-  RMEM_REQUIRE(n >= 1 && n <= 65535, "rmem_label_component_stats: n must be in 1..65535");
-  RMEM_REQUIRE(geometry_ok(H, W), "rmem_label_component_stats: H and W must be positive, H * W at most 2^26");
+  RMEM_REQUIRE(n >= 1 && n <= kMaxFrames, "rmem_label_component_stats: n must be in 1..65535");
+  RMEM_REQUIRE(stack_geometry_ok(n, H, W), "rmem_label_component_stats: H and W must be positive, H * W at most 2^26");
   RMEM_REQUIRE(connectivity == 4 || connectivity == 8, "rmem_label_component_stats: connectivity must be 4 or 8");
   const int HW = H * W, conn8 = connectivity == 8;
   const int init_threads = HW * 4 > 768 ? HW * 4 : 768;
@@ -461,8 +460,8 @@ extern "C" int rmem_label_component_stats(const unsigned char* labels, const int
 extern "C" int rmem_label_clean(const unsigned char* src, unsigned char* dst, const int* roots, const int* stats, const int* table, int n,
                                 int H, int W, int max_hole_area, int max_sprinkle_area, int keep_largest, void* stream) {
   RMEM_REQUIRE(src && dst && roots && stats && table, "rmem_label_clean: null pointer (src, dst, roots, stats and table are required)");
-  RMEM_REQUIRE(n >= 1 && n <= 65535, "rmem_label_clean: n must be in 1..65535");
-  RMEM_REQUIRE(geometry_ok(H, W), "rmem_label_clean: H and W must be positive, H * W at most 2^26");
+  RMEM_REQUIRE(n >= 1 && n <= kMaxFrames, "rmem_label_clean: n must be in 1..65535");
+  RMEM_REQUIRE(stack_geometry_ok(n, H, W), "rmem_label_clean: H and W must be positive, H * W at most 2^26");
   RMEM_REQUIRE(max_hole_area >= 0 && max_sprinkle_area >= 0, "rmem_label_clean: max_hole_area and max_sprinkle_area must not be negative");
   const int HW = H * W;
   const CleanRule rule = {max_hole_area, max_sprinkle_area, keep_largest != 0};

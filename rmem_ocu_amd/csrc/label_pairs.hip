@@ -132,8 +132,8 @@ extern "C" int rmem_label_pair_census_lds_bins(void) { return kLdsBins; }
 extern "C" int rmem_label_pair_census(const unsigned char* a, const unsigned char* b, int n, int H, int W, int num_a, int num_b, int* out,
                                       void* stream) {
   RMEM_REQUIRE(a && b && out, "rmem_label_pair_census: null pointer (a, b and out are required)");
-  RMEM_REQUIRE(n >= 1 && n <= 65535, "rmem_label_pair_census: n must be in 1..65535");
-  RMEM_REQUIRE(H >= 1 && W >= 1 && (long)H * W <= kMaxPixels, "rmem_label_pair_census: H and W must be positive, H * W at most 2^26");
+  RMEM_REQUIRE(n >= 1 && n <= kMaxFrames, "rmem_label_pair_census: n must be in 1..65535");
+  RMEM_REQUIRE(stack_geometry_ok(n, H, W), "rmem_label_pair_census: H and W must be positive, H * W at most 2^26");
   RMEM_REQUIRE(num_a >= 1 && num_a <= 255 && num_b >= 1 && num_b <= 255, "rmem_label_pair_census: num_a and num_b must be in 1..255");
   const int HW = H * W, nbins = (num_a + 2) * (num_b + 2);
   if (hipMemsetAsync(out, 0, (size_t)n * nbins * sizeof(int), (hipStream_t)stream) != hipSuccess) {

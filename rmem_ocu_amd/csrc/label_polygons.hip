@@ -10,7 +10,8 @@
 //
 //   k_poly_walk<false>   one thread per unit = kRun pixels of a row (lanes = adjacent runs: a wave reads consecutive bytes of the
 //                        rows y - 1, y, y + 1): the number of edges of its pixels, stored to the unit's own counter.
-//   k_poly_scan_units    one workgroup per frame: exclusive scan of its units' counts in place (unit order = edge id order), total.
+//   k_label_scan_units   one workgroup per frame: exclusive scan of its units' counts in place (unit order = edge id order), total
+//                        (label_scan.h, which also holds the workgroup scan of the kernels below).
 //   k_poly_base          one workgroup: scan over the frames' totals in 64 bits -> every frame's base; counts = (E, 0, 0, status).
 //                        With E > max_edges the status says so and every later kernel returns at once.
 //   k_poly_walk<true>    the same walk; edge ids go to base + running offset -- the compact array comes out sorted by (frame, edge
@@ -31,45 +32,14 @@
 //                        (unsigned arithmetic: the prefixes may wrap, the difference of at most 2^27 does not).
 //   k_poly_emit          per position: a corner's vertex; from the ring's first position the ring's row; from position 0, R and V.
 #include <limits.h>
-#include "label_wave.h"
+#include "label_scan.h"
 #include "../../include/rmem.h"
 
 namespace {
 constexpr int kRun = 8;                           // pixels of one row a thread walks: the walk unit
 constexpr int kScanItems = 8;                     // entries per thread of the device-wide scans
 constexpr int kScanTile = kThreads * kScanItems;
-constexpr int kMaxFrames = 65535;
 
-// the workgroup scan of rle.hip (each translation unit keeps its helpers in its own anonymous namespace)
-template <typename T>
-__device__ __forceinline__ T wave_incl_scan(T v, int lane) {
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const T u = __shfl_up(v, o, 64);
-    if (lane >= o) v += u;
-  }
-  return v;
-}
-// inclusive scan over the workgroup's kThreads values (thread order) and their total; sh: kWaves entries; whole workgroups only
-template <typename T>
-__device__ __forceinline__ T block_incl_scan(T v, T* sh, T& total) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const T w = wave_incl_scan(v, lane);
-  __syncthreads();                    // the previous call's readers are done with sh
-  if (lane == 63) sh[wave] = w;
-  __syncthreads();
-  T add = 0, tot = 0;
-#pragma unroll
-  for (int k = 0; k < kWaves; ++k) {
-    const T s = sh[k];
-    if (k < wave) add += s;
-    tot += s;
-  }
-  total = tot;
-  return w + add;
-}
-
-inline size_t align16(size_t b) { return (b + 15) & ~(size_t)15; }
 inline int units_x(int W) { return (W + kRun - 1) / kRun; }
 
 struct Layout {
@@ -169,21 +139,6 @@ __global__ __launch_bounds__(kThreads) void k_poly_walk(const unsigned char* __r
     }
   }
   if (!WRITE) *mine = count;                                        // one owner: a plain store
-}
-
-__global__ __launch_bounds__(kThreads) void k_poly_scan_units(int* __restrict__ cnt, int U, int* __restrict__ totals) {
-  __shared__ int sh[kWaves];
-  int* c = cnt + (size_t)blockIdx.x * U;
-  int carry = 0;
-  for (int b = 0; b < U; b += kThreads) {
-    const int i = b + threadIdx.x;
-    const int v = i < U ? c[i] : 0;
-    int tot;
-    const int inc = block_incl_scan(v, sh, tot);
-    if (i < U) c[i] = carry + inc - v;
-    carry += tot;
-  }
-  if (threadIdx.x == 0) totals[blockIdx.x] = carry;
 }
 
 __global__ __launch_bounds__(kThreads) void k_poly_base(const int* __restrict__ totals, int n, int M, int* __restrict__ fb, int* __restrict__ counts) {
@@ -420,13 +375,12 @@ __global__ __launch_bounds__(kThreads) void k_poly_emit(const unsigned char* __r
   o[7] = 0;
 }
 
-inline bool geometry_ok(int n, int H, int W) { return n >= 1 && n <= kMaxFrames && H >= 1 && W >= 1 && (long)H * W <= kMaxPixels; }
 }  // namespace
 
 extern "C" int rmem_label_polygons_unit(void) { return kRun; }
 
 extern "C" size_t rmem_label_polygons_workspace_bytes(int n, int H, int W, int max_edges) {
-  if (!geometry_ok(n, H, W) || max_edges < 4) return 0;
+  if (!stack_geometry_ok(n, H, W) || max_edges < 4) return 0;
   return layout(n, H, W, max_edges).bytes;
 }
 
@@ -435,7 +389,7 @@ extern "C" int rmem_label_polygons(const unsigned char* labels, int n, int H, in
   RMEM_REQUIRE(labels && workspace && rings && verts && counts,
                "rmem_label_polygons: null pointer (labels, workspace, rings, verts and counts are required)");
   RMEM_REQUIRE(n >= 1 && n <= kMaxFrames, "rmem_label_polygons: n must be in 1..65535");
-  RMEM_REQUIRE(H >= 1 && W >= 1 && (long)H * W <= kMaxPixels, "rmem_label_polygons: H and W must be positive, H * W at most 2^26");
+  RMEM_REQUIRE(stack_geometry_ok(n, H, W), "rmem_label_polygons: H and W must be positive, H * W at most 2^26");
   RMEM_REQUIRE(num_objs >= 1 && num_objs <= 255, "rmem_label_polygons: num_objs must be in 1..255");
   RMEM_REQUIRE(connectivity == 4 || connectivity == 8, "rmem_label_polygons: connectivity must be 4 or 8");
   RMEM_REQUIRE(max_edges >= 4, "rmem_label_polygons: max_edges must be at least 4");
@@ -458,7 +412,7 @@ extern "C" int rmem_label_polygons(const unsigned char* labels, int n, int H, in
   const dim3 tiles((unsigned)l.nb);
   hipLaunchKernelGGL(k_poly_walk<false>, walk, th, 0, st, labels, H, W, num_objs, conn8, nxu, U, M, cnt, (const int*)nullptr, (const int*)nullptr,
                      (int*)nullptr, (int*)nullptr);
-  hipLaunchKernelGGL(k_poly_scan_units, dim3((unsigned)n), th, 0, st, cnt, U, totals);
+  hipLaunchKernelGGL(k_label_scan_units, dim3((unsigned)n), th, 0, st, cnt, U, totals);
   hipLaunchKernelGGL(k_poly_base, dim3(1), th, 0, st, (const int*)totals, n, M, fb, counts);
   hipLaunchKernelGGL(k_poly_walk<true>, walk, th, 0, st, labels, H, W, num_objs, conn8, nxu, U, M, cnt, (const int*)fb, (const int*)counts, eid, nxt);
   hipLaunchKernelGGL(k_poly_link, edges, th, 0, st, (const int*)fb, n, counts, (const int*)cnt, U, nxu, W, HW, (const int*)eid, (const int*)nxt, pp[0]);

@@ -1,13 +1,18 @@
-// What the kernels that walk uint8 label stacks 16 bytes per lane share (label_census.hip, label_pairs.hip, label_components.hip):
-// the byte compares of a lane's piece, the wave's integer sum, minimum and maximum, the unaligned word and the bound on the grid.
+// What the kernels on uint8 label stacks share (label_census.hip, label_pairs.hip, label_components.hip, and through
+// label_scan.h label_polygons.hip and rle.hip): the workgroup, the limits of a stack, and for those that walk it 16 bytes per
+// lane the byte compares of a lane's piece, the wave's integer sum, minimum and maximum, the unaligned word and the bound on the grid.
 #pragma once
 #include "common.h"
 
 namespace {
 constexpr int kThreads = 256;
 constexpr int kWaves = kThreads / 64;
+constexpr int kMaxFrames = 65535;
 constexpr long kMaxPixels = 1L << 26;
 constexpr int kMaxBlocks = 2048;      // workgroups of one launch, about: enough to fill the chip, few enough to keep the flushes rare
+
+// host: a stack of n frames of H x W that the entry points take
+inline bool stack_geometry_ok(int n, int H, int W) { return n >= 1 && n <= kMaxFrames && H >= 1 && W >= 1 && (long)H * W <= kMaxPixels; }
 
 __device__ __forceinline__ int wave_isum(int v) {
 #pragma unroll

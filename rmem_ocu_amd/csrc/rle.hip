@@ -11,7 +11,8 @@
 //                      columns, so a wave's loads are 64 consecutive bytes), compared with the pixel before in column-major order.
 //                      Every boundary adds 1 to cnt[frame][id][x * NC + chunk]; that counter has exactly one owner thread, so the
 //                      no-return integer atomic is only a cheap read-modify-write: its order cannot show.
-//   k_rle_scan_units   one workgroup per (frame, id): exclusive scan of its units in place (unit order = position order), its total.
+//   k_label_scan_units one workgroup per (frame, id): exclusive scan of its units in place (unit order = position order), its total
+//                      (label_scan.h, which also holds the workgroup scan every kernel below uses).
 //   k_rle_base         one workgroup per frame: where each id's positions start in the frame's position array (<= 2 H W entries).
 //   k_rle_walk<true>   the same walk; a boundary is stored at base + the unit's running offset: positions come out sorted.
 //   k_rle_sizes        one workgroup per (frame, id): counts from positions, the delta (count i minus count i - 2 for i > 2), the
@@ -32,48 +33,15 @@
 //   k_rle_paint        one thread per four consecutive pixels of a column, lanes = adjacent columns (a store instruction writes 64
 //                      consecutive bytes of a row): the frame's strings from the last listed to the first; in each whose set
 //                      range covers these positions, a binary search among the column's runs; the first hit wins.
-#include "common.h"
+#include "label_scan.h"
 #include "../../include/rmem.h"
 
 namespace {
-constexpr int kThreads = 256;
-constexpr int kWaves = kThreads / 64;
-constexpr long kMaxPixels = 1L << 26;
 constexpr int kChunkRows = 128;       // rows of one column a thread walks
 constexpr int kLoadRows = 16;         // loads in flight per thread
-constexpr int kMaxFrames = 65535;
-constexpr long long kMaxStrings = 65535LL * 255;
-
-template <typename T>
-__device__ __forceinline__ T wave_incl_scan(T v, int lane) {
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const T u = __shfl_up(v, o, 64);
-    if (lane >= o) v += u;
-  }
-  return v;
-}
-// inclusive scan over the workgroup's kThreads values (thread order) and their total; sh: kWaves entries; whole workgroups only
-template <typename T>
-__device__ __forceinline__ T block_incl_scan(T v, T* sh, T& total) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const T w = wave_incl_scan(v, lane);
-  __syncthreads();                    // the previous call's readers are done with sh
-  if (lane == 63) sh[wave] = w;
-  __syncthreads();
-  T add = 0, tot = 0;
-#pragma unroll
-  for (int k = 0; k < kWaves; ++k) {
-    const T s = sh[k];
-    if (k < wave) add += s;
-    tot += s;
-  }
-  total = tot;
-  return w + add;
-}
+constexpr long long kMaxStrings = (long long)kMaxFrames * 255;
 
 inline int chunks_of(int H) { return (H + kChunkRows - 1) / kChunkRows; }
-inline size_t align16(size_t b) { return (b + 15) & ~(size_t)15; }
 
 // ---------------------------------------------------------------------------------------------------------------- writing
 struct EncodeLayout {
@@ -136,21 +104,6 @@ __global__ __launch_bounds__(kThreads) void k_rle_walk(const unsigned char* __re
       }
     }
   }
-}
-
-__global__ __launch_bounds__(kThreads) void k_rle_scan_units(int* __restrict__ cnt, int U, int* __restrict__ totals) {
-  __shared__ int sh[kWaves];
-  int* c = cnt + (size_t)blockIdx.x * U;
-  int carry = 0;
-  for (int b = 0; b < U; b += kThreads) {
-    const int i = b + threadIdx.x;
-    const int v = i < U ? c[i] : 0;
-    int tot;
-    const int inc = block_incl_scan(v, sh, tot);
-    if (i < U) c[i] = carry + inc - v;
-    carry += tot;
-  }
-  if (threadIdx.x == 0) totals[blockIdx.x] = carry;
 }
 
 __global__ __launch_bounds__(kThreads) void k_rle_base(const int* __restrict__ totals, int K, int* __restrict__ base) {
@@ -418,11 +371,10 @@ __global__ __launch_bounds__(kThreads) void k_rle_paint(const RmemRleDesc* __res
   for (int i = 0; i < npx; ++i) o[(size_t)i * W] = (unsigned char)(out >> (8 * i));
 }
 
-bool geometry_ok(int frames, int H, int W) { return frames >= 1 && frames <= kMaxFrames && H >= 1 && W >= 1 && (long)H * W <= kMaxPixels; }
 }  // namespace
 
 extern "C" size_t rmem_rle_workspace_bytes(int frames, int H, int W, int num_ids) {
-  if (!geometry_ok(frames, H, W) || num_ids < 1 || num_ids > 255) return 0;
+  if (!stack_geometry_ok(frames, H, W) || num_ids < 1 || num_ids > 255) return 0;
   return encode_layout(frames, H, W, num_ids).bytes;
 }
 
@@ -431,7 +383,7 @@ extern "C" int rmem_rle_encode_labels(const unsigned char* labels, int frames, i
   RMEM_REQUIRE(labels && workspace && out && offsets && status,
                "rmem_rle_encode_labels: null pointer (labels, workspace, out, offsets and status are required)");
   RMEM_REQUIRE(frames >= 1 && frames <= kMaxFrames, "rmem_rle_encode_labels: frames must be in 1..65535");
-  RMEM_REQUIRE(H >= 1 && W >= 1 && (long)H * W <= kMaxPixels, "rmem_rle_encode_labels: H and W must be positive, H * W at most 2^26");
+  RMEM_REQUIRE(stack_geometry_ok(frames, H, W), "rmem_rle_encode_labels: H and W must be positive, H * W at most 2^26");
   RMEM_REQUIRE(num_ids >= 1 && num_ids <= 255, "rmem_rle_encode_labels: num_ids must be in 1..255");
   RMEM_REQUIRE(capacity >= 0, "rmem_rle_encode_labels: capacity must not be negative");
   RMEM_REQUIRE(((uintptr_t)workspace & 15u) == 0, "rmem_rle_encode_labels: the workspace must be 16-byte aligned");
@@ -452,7 +404,7 @@ extern "C" int rmem_rle_encode_labels(const unsigned char* labels, int frames, i
   const int nxb = (W + kThreads - 1) / kThreads;
   const dim3 walk((unsigned)(nxb * NC), (unsigned)frames);
   hipLaunchKernelGGL(k_rle_walk<false>, walk, dim3(kThreads), 0, st, labels, H, W, K, NC, nxb, cnt, (const int*)nullptr, (int*)nullptr);
-  hipLaunchKernelGGL(k_rle_scan_units, dim3((unsigned)S), dim3(kThreads), 0, st, cnt, (int)U, totals);
+  hipLaunchKernelGGL(k_label_scan_units, dim3((unsigned)S), dim3(kThreads), 0, st, cnt, (int)U, totals);
   hipLaunchKernelGGL(k_rle_base, dim3((unsigned)frames), dim3(kThreads), 0, st, totals, K, base);
   hipLaunchKernelGGL(k_rle_walk<true>, walk, dim3(kThreads), 0, st, labels, H, W, K, NC, nxb, cnt, (const int*)base, pos);
   hipLaunchKernelGGL(k_rle_sizes, dim3((unsigned)S), dim3(kThreads), 0, st, pos, totals, base, K, HW, sizes);
@@ -475,7 +427,7 @@ extern "C" int rmem_rle_decode_labels(const unsigned char* bits, long long total
   RMEM_REQUIRE(total_bytes >= 0 && total_bytes <= INT32_MAX, "rmem_rle_decode_labels: total_bytes must be in 0..2^31-1");
   RMEM_REQUIRE(nstrings >= 1 && nstrings <= kMaxStrings, "rmem_rle_decode_labels: nstrings must be in 1..65535*255");
   RMEM_REQUIRE(frames >= 1 && frames <= kMaxFrames, "rmem_rle_decode_labels: frames must be in 1..65535");
-  RMEM_REQUIRE(H >= 1 && W >= 1 && (long)H * W <= kMaxPixels, "rmem_rle_decode_labels: H and W must be positive, H * W at most 2^26");
+  RMEM_REQUIRE(stack_geometry_ok(frames, H, W), "rmem_rle_decode_labels: H and W must be positive, H * W at most 2^26");
   RMEM_REQUIRE(((uintptr_t)workspace & 15u) == 0, "rmem_rle_decode_labels: the workspace must be 16-byte aligned");
   const DecodeLayout l = decode_layout(nstrings, total_bytes, frames, W);
   char* ws = (char*)workspace;

@@ -42,8 +42,8 @@ from typing import Dict, List, Optional, Sequence, Tuple
 import numpy as np
 import torch
 
-from . import _lib, ops
-from ._codec import davis_palette as _davis_palette, uint8_stack, workspace
+from . import _labels, _lib, ops
+from ._codec import davis_palette as _davis_palette, workspace
 from .clip_runner import clip_gap
 from .networks.engines import build_engine
 
@@ -118,11 +118,7 @@ def region_similarity(pred_u8: torch.Tensor, gt_u8: torch.Tensor, num_ids: int =
 
 
 def _label_stacks(pred_u8, gt_u8, what):
-    pred, gt = uint8_stack(pred_u8, what, 'pred'), uint8_stack(gt_u8, what, 'gt')
-    if pred_u8.shape != gt_u8.shape or pred.device != gt.device:
-        raise _lib.RmemError(f'{what}: pred and gt must have one shape, [n, H, W] or [H, W], on one device '
-                             f'(got {tuple(pred_u8.shape)} and {tuple(gt_u8.shape)})')
-    return pred.contiguous(), gt.contiguous()
+    return _labels.stack_pair(what, pred_u8, gt_u8, ('pred', 'gt'), devices=False)
 
 
 def boundary_radius(H: int, W: int, bound_th: float = 0.008) -> int:
@@ -162,10 +158,7 @@ def scores_from_counts(counts) -> Tuple[np.ndarray, np.ndarray]:
     c = np.asarray(counts).astype(np.float64)
     n_fg, n_gt, fg_m, gt_m, inter, union = (c[..., i] for i in range(6))
     J = np.where(union == 0, 1.0, inter / np.maximum(union, 1.0))
-    P = np.where(n_fg > 0, np.where(n_gt > 0, fg_m / np.maximum(n_fg, 1.0), 0.0), 1.0)
-    R = np.where(n_gt > 0, np.where(n_fg > 0, gt_m / np.maximum(n_gt, 1.0), 0.0), 1.0)
-    F = np.where(P + R == 0, 0.0, 2.0 * P * R / np.where(P + R == 0, 1.0, P + R))
-    return J, F
+    return J, _labels.boundary_prf(n_fg, n_gt, fg_m, gt_m)[2]
 
 
 def boundary_accuracy(pred_u8: torch.Tensor, gt_u8: torch.Tensor, num_ids: int = 11, void_label: int = 255,
@@ -272,9 +265,7 @@ def score_clip_objects(pred_u8: torch.Tensor, gt_u8: torch.Tensor, num_objs: Opt
     pred, gt = _label_stacks(pred_u8, gt_u8, 'score_clip_objects')
     if num_objs is None:
         num_objs = _max_object(gt, void_label)
-    if isinstance(num_objs, bool) or not isinstance(num_objs, (int, np.integer)) or not 1 <= num_objs <= 255:
-        raise _lib.RmemError(f'score_clip_objects: num_objs must be in 1..255 (got {num_objs!r})')
-    K = int(num_objs)
+    K = _labels.int_in('score_clip_objects', 'num_objs', num_objs, 1, 255, must_be='in')
     census, match, bnd_a, bnd_b = _pair_tables(pred, gt, K, K, void_label, bound_th)
     _, inter, union = pairs.pair_iou(census, drop_other_b=void_label is not None)
     d = np.arange(K)

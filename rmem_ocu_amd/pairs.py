@@ -18,14 +18,9 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._codec import uint8_stack, workspace
+from ._codec import workspace
+from ._labels import WORKSPACE_CAP as PAIR_BOUNDARY_WORKSPACE_CAP, boundary_prf, frames_per_pass, int_in, is_int, stack_pair
 from ._lib import RmemError
-
-
-def _num(what: str, name: str, v) -> int:
-    if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 1 <= int(v) <= 255:
-        raise RmemError(f'{what}: {name} must be an integer in 1..255 (got {v!r})')
-    return int(v)
 
 
 def pair_census(a_u8: torch.Tensor, b_u8: torch.Tensor, num_a: int, num_b: int) -> torch.Tensor:
@@ -34,8 +29,8 @@ def pair_census(a_u8: torch.Tensor, b_u8: torch.Tensor, num_a: int, num_b: int) 
     above num_a / num_b, a void label of 255 included when num_b < 255.  Every frame's table sums to H * W.  a_u8, b_u8: uint8
     device stacks [n, H, W] or [H, W] of one shape on one device.  One call on the current stream, no host sync."""
     what = 'pairs.pair_census'
-    num_a, num_b = _num(what, 'num_a', num_a), _num(what, 'num_b', num_b)
-    a, b = _stack_pair(a_u8, b_u8, what)
+    num_a, num_b = int_in(what, 'num_a', num_a, 1, 255), int_in(what, 'num_b', num_b, 1, 255)
+    a, b = stack_pair(what, a_u8, b_u8)
     n, H, W = a.shape
     out = torch.empty(n, num_a + 2, num_b + 2, dtype=torch.int32, device=a.device)
     stream = torch.cuda.current_stream(a.device)
@@ -46,24 +41,13 @@ def pair_census(a_u8: torch.Tensor, b_u8: torch.Tensor, num_a: int, num_b: int) 
     return out
 
 
-def _stack_pair(a_u8, b_u8, what: str) -> Tuple[torch.Tensor, torch.Tensor]:
-    a, b = uint8_stack(a_u8, what, 'a'), uint8_stack(b_u8, what, 'b')
-    if a_u8.shape != b_u8.shape or a.device != b.device:
-        raise RmemError(f'{what}: a and b must have one shape, [n, H, W] or [H, W], on one device '
-                        f'(got {tuple(a_u8.shape)} on {a.device} and {tuple(b_u8.shape)} on {b.device})')
-    return a.contiguous(), b.contiguous()
-
-
 def _void(what: str, void_label, num_b: int) -> int:
     """the C entry points' void_label: -1 for None (no void), else an integer in num_b + 1 .. 255"""
     if void_label is None:
         return -1
-    if isinstance(void_label, bool) or not isinstance(void_label, (int, np.integer)) or not num_b < int(void_label) <= 255:
+    if not is_int(void_label) or not num_b < int(void_label) <= 255:
         raise RmemError(f'{what}: void_label must be None or an integer above num_b = {num_b}, at most 255 (got {void_label!r})')
     return int(void_label)
-
-
-PAIR_BOUNDARY_WORKSPACE_CAP = 256 << 20      # bytes of bit planes one call keeps, unless one frame needs more
 
 
 def pair_boundary_counts(a_u8: torch.Tensor, b_u8: torch.Tensor, num_a: int, num_b: int, void_label: Optional[int] = 255,
@@ -77,9 +61,9 @@ def pair_boundary_counts(a_u8: torch.Tensor, b_u8: torch.Tensor, num_a: int, num
     The bit planes live in a workspace per (device, stream) that holds as many frames as fit workspace_bytes (default: 256 MiB,
     or one frame's planes where those are larger); the call passes over the stack that many frames at a time."""
     what = 'pairs.pair_boundary_counts'
-    num_a, num_b = _num(what, 'num_a', num_a), _num(what, 'num_b', num_b)
+    num_a, num_b = int_in(what, 'num_a', num_a, 1, 255), int_in(what, 'num_b', num_b, 1, 255)
     void = _void(what, void_label, num_b)
-    a, b = _stack_pair(a_u8, b_u8, what)
+    a, b = stack_pair(what, a_u8, b_u8)
     n, H, W = a.shape
     L = _lib.lib()
     radius = L.rmem_boundary_radius(H, W, float(bound_th))
@@ -88,12 +72,7 @@ def pair_boundary_counts(a_u8: torch.Tensor, b_u8: torch.Tensor, num_a: int, num
     per_frame = L.rmem_pair_boundary_workspace_bytes(1, H, W, num_a, num_b)
     if per_frame == 0:
         raise RmemError(f'{what}: frames of {H} x {W} are too large (H * W at most 2^26), or more than 65535 of them')
-    if workspace_bytes is None:
-        workspace_bytes = max(per_frame, min(n * per_frame, PAIR_BOUNDARY_WORKSPACE_CAP))
-    elif isinstance(workspace_bytes, bool) or not isinstance(workspace_bytes, (int, np.integer)) or workspace_bytes < per_frame:
-        raise RmemError(f'{what}: workspace_bytes must be an integer of at least one frame\'s planes, {per_frame} bytes '
-                        f'(got {workspace_bytes!r})')
-    nbytes = int(min(workspace_bytes, n * per_frame))
+    nbytes = min(frames_per_pass(what, n, per_frame, workspace_bytes, 'one frame\'s planes')[0], n * per_frame)
     stream = torch.cuda.current_stream(a.device)
     ws = workspace('pair_boundary', a.device, stream, nbytes)
     match = torch.empty(n, num_a + 1, num_b + 1, 2, dtype=torch.int32, device=a.device)
@@ -116,9 +95,8 @@ def _host_ints(t, ndim: int, what: str, name: str) -> np.ndarray:
 
 def pair_f(match, bnd_a, bnd_b) -> np.ndarray:
     """The boundary accuracy F of every pair, float64 [n, num_a, num_b], from pair_boundary_counts' three tables (device tensors:
-    one readback each; or host arrays).  Entry [f, i - 1, j - 1] is object i of a against object j of b.  f_measure's edge cases,
-    by the very operations of evaluator.scores_from_counts: no boundary in a -> P = 1, R = 0; none in b -> P = 0, R = 1; neither
-    -> P = R = 1; F = 0 when P + R = 0."""
+    one readback each; or host arrays).  Entry [f, i - 1, j - 1] is object i of a against object j of b.  f_measure's edge cases
+    are _labels.boundary_prf's, which evaluator.scores_from_counts calls as well."""
     what = 'pairs.pair_f'
     m, ba, bb = _host_ints(match, 4, what, 'match'), _host_ints(bnd_a, 2, what, 'bnd_a'), _host_ints(bnd_b, 2, what, 'bnd_b')
     if m.shape != (ba.shape[0], ba.shape[1], bb.shape[1], 2) or ba.shape[0] != bb.shape[0] or ba.shape[1] < 2 or bb.shape[1] < 2:
@@ -127,9 +105,7 @@ def pair_f(match, bnd_a, bnd_b) -> np.ndarray:
     fg_m, gt_m = m[:, 1:, 1:, 0].astype(np.float64), m[:, 1:, 1:, 1].astype(np.float64)
     n_fg = np.broadcast_to(ba[:, 1:, None], fg_m.shape).astype(np.float64)
     n_gt = np.broadcast_to(bb[:, None, 1:], fg_m.shape).astype(np.float64)
-    P = np.where(n_fg > 0, np.where(n_gt > 0, fg_m / np.maximum(n_fg, 1.0), 0.0), 1.0)
-    R = np.where(n_gt > 0, np.where(n_fg > 0, gt_m / np.maximum(n_gt, 1.0), 0.0), 1.0)
-    return np.where(P + R == 0, 0.0, 2.0 * P * R / np.where(P + R == 0, 1.0, P + R))
+    return boundary_prf(n_fg, n_gt, fg_m, gt_m)[2]
 
 
 def jf_from_tables(census, match, bnd_a, bnd_b, drop_other_b: bool = True) -> Tuple[np.ndarray, np.ndarray]:

@@ -19,10 +19,10 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._codec import uint8_stack, workspace
+from ._codec import workspace
+from ._labels import connectivity as _connectivity, frames_per_pass, int_in, is_int, object_keys, stack as _frames
 from ._lib import RmemError
 
-POLYGONS_WORKSPACE_CAP = 256 << 20           # bytes of workspace and outputs one pass of trace_label_stack keeps, unless one frame needs more
 ST_CAPACITY, ST_LINK, ST_ORDER = 1, 2, 4     # include/rmem.h
 MAX_EDGES = 2 ** 31 - 1
 
@@ -40,32 +40,12 @@ def default_max_edges(n: int, H: int, W: int) -> int:
     return int(max(4, min(n * (H * W // 4 + 4 * (H + W) + 64), 4 * n * H * W, MAX_EDGES)))
 
 
-def _num_objs(what: str, num_objs) -> int:
-    if isinstance(num_objs, bool) or not isinstance(num_objs, (int, np.integer)) or not 1 <= int(num_objs) <= 255:
-        raise RmemError(f'{what}: num_objs must be an integer in 1..255 (got {num_objs!r})')
-    return int(num_objs)
-
-
-def _connectivity(what: str, connectivity) -> int:
-    if isinstance(connectivity, bool) or not isinstance(connectivity, (int, np.integer)) or int(connectivity) not in (4, 8):
-        raise RmemError(f'{what}: connectivity must be 4 or 8 (got {connectivity!r})')
-    return int(connectivity)
-
-
 def _max_edges(what: str, max_edges, n: int, H: int, W: int) -> int:
     if max_edges is None:
         return default_max_edges(n, H, W)
-    if isinstance(max_edges, bool) or not isinstance(max_edges, (int, np.integer)) or not 4 <= int(max_edges) <= MAX_EDGES:
+    if not is_int(max_edges) or not 4 <= int(max_edges) <= MAX_EDGES:
         raise RmemError(f'{what}: max_edges must be an integer in 4..2^31-1 (got {max_edges!r})')
     return int(max_edges)
-
-
-def _frames(what: str, labels_u8) -> torch.Tensor:
-    a = uint8_stack(labels_u8, what).contiguous()
-    n, H, W = a.shape
-    if H * W > (1 << 26) or n > 65535:
-        raise RmemError(f'{what}: labels of {n} x {H} x {W} are too large (H * W at most 2^26, at most 65535 frames)')
-    return a
 
 
 def trace(labels_u8: torch.Tensor, num_objs: int, connectivity: int = 8,
@@ -78,7 +58,7 @@ def trace(labels_u8: torch.Tensor, num_objs: int, connectivity: int = 8,
     more edges: counts is (E, 0, 0, ST_CAPACITY) then, E exact.  Any other status bit is a bug.  One call of rmem_label_polygons
     on the current stream, no host sync; the workspace is one buffer per (device, stream) that only grows."""
     what = 'polygons.trace'
-    K, conn = _num_objs(what, num_objs), _connectivity(what, connectivity)
+    K, conn = int_in(what, 'num_objs', num_objs, 1, 255), _connectivity(what, connectivity)
     a = _frames(what, labels_u8)
     n, H, W = a.shape
     M = _max_edges(what, max_edges, n, H, W)
@@ -104,13 +84,11 @@ def group_rings(rings: np.ndarray, verts: np.ndarray, n: int, num_objs: int, squ
     `trace` orders them -> one dict per frame, {key of object id: [{'exterior', 'area2', 'holes'}, ...]} with an empty list for an
     object the frame does not hold.  roots_at_start [R]: label_components' root at every ring's start pixel; a hole (area2 < 0)
     goes to the outer ring of its frame whose start pixel is that root.  None: holes are not attached, see trace_label_stack."""
-    K = int(num_objs)
-    ids = range(1, K + 1) if squeeze_idx is None else range(1, min(K + 1, len(squeeze_idx)))
-    key = {i: (i if squeeze_idx is None else int(squeeze_idx[i])) for i in ids}
-    frames: List[Dict] = [{key[i]: [] for i in ids} for _ in range(n)]
+    key = object_keys(int(num_objs), squeeze_idx)
+    frames: List[Dict] = [{k: [] for k in key.values()} for _ in range(n)]
     if roots_at_start is None:
         for fr in frames:
-            fr[None] = {'holes': {key[i]: [] for i in ids}}
+            fr[None] = {'holes': {k: [] for k in key.values()}}
     outer = {}
     rows = [(int(r[0]), int(r[1]), verts[int(r[2]):int(r[2]) + int(r[3])].astype(np.int32, copy=True), int(r[4]), int(r[5]) >> 2)
             for r in rings]
@@ -168,18 +146,13 @@ def trace_label_stack(labels_u8: torch.Tensor, num_objs: int, connectivity: int 
     rows.  max_edges (per pass; default: default_max_edges): when the status says ST_CAPACITY the pass is traced once more with
     max_edges = counts[0]."""
     what = 'polygons.trace_label_stack'
-    K, conn = _num_objs(what, num_objs), _connectivity(what, connectivity)
+    K, conn = int_in(what, 'num_objs', num_objs, 1, 255), _connectivity(what, connectivity)
     a = _frames(what, labels_u8)
     n, H, W = a.shape
     per_frame = frame_bytes(H, W, parents)
-    if workspace_bytes is None:
-        workspace_bytes = max(per_frame, min(n * per_frame, POLYGONS_WORKSPACE_CAP))
-    elif isinstance(workspace_bytes, bool) or not isinstance(workspace_bytes, (int, np.integer)) or workspace_bytes < per_frame:
-        raise RmemError(f'{what}: workspace_bytes must be an integer of at least one frame\'s need, {per_frame} bytes '
-                        f'(got {workspace_bytes!r})')
+    k = frames_per_pass(what, n, per_frame, workspace_bytes, 'one frame\'s need')[1]     # at least 1: the budget holds a frame
     if max_edges is not None:
         _max_edges(what, max_edges, n, H, W)
-    k = int(max(1, min(n, workspace_bytes // per_frame)))           # frames per pass
     out: List[Dict] = []
     for f0 in range(0, n, k):
         part = a[f0:f0 + k]

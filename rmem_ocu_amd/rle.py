@@ -27,6 +27,7 @@ import torch
 
 from . import _lib
 from ._codec import Packed, fetch_files, stream_of, uint8_stack, workspace
+from ._labels import object_keys
 
 # encode_label_stack gives one encode call as many frames as keep rmem_rle_workspace_bytes at or below this (one frame at least,
 # MAX_FRAMES at most): per frame 8 H W bytes of boundary positions plus 4 * num_ids * W * ceil(H / 128) bytes of counters.
@@ -111,18 +112,18 @@ def encode_label_stack(labels_u8: torch.Tensor, num_ids: int, squeeze_idx: Optio
     if boxes:
         from .evaluator import object_boxes
         area, box = (t.cpu().numpy() for t in object_boxes(labels, K))
-    keys = range(1, K + 1) if squeeze_idx is None else range(1, min(K + 1, len(squeeze_idx)))
+    keys = object_keys(K, squeeze_idx)
     frames = []
     for f in range(n):
         entry = {}
-        for i in keys:
+        for i, key in keys.items():
             s = strings[f * K + i - 1]
             e = {'size': [H, W], 'counts': s.decode('ascii') if ascii else s}
             if boxes:
                 a = int(area[f, i - 1])
                 x0, y0, x1, y1 = (int(v) for v in box[f, i - 1])
                 e['area'], e['bbox'] = a, ([x0, y0, x1 - x0 + 1, y1 - y0 + 1] if a else [0, 0, 0, 0])
-            entry[i if squeeze_idx is None else int(squeeze_idx[i])] = e
+            entry[key] = e
         frames.append(entry)
     return frames
 
