@@ -722,6 +722,77 @@ size_t rmem_label_polygons_workspace_bytes(int n, int H, int W, int max_edges); 
 int rmem_label_polygons(const unsigned char* labels, int n, int H, int W, int num_objs, int connectivity, int max_edges,
                         void* workspace, size_t workspace_bytes, int* rings, int* verts, int* counts, void* stream);
 
+/* The inverse: annotation polygons filled into uint8 label maps labels[frames][H][W] (contiguous, device, may start at any byte),
+ * the way polygon tracks (CVAT, Labelme, COCO `segmentation` lists) enter a run (polygons.py: PackedPolygons, fill_labels_into,
+ * fill_label_stack; evaluator.labels_from_polygons).  One call on `stream`, no host sync, no state kept between calls; only the
+ * vertices' edges cross to the device.
+ * The rule.  A shape is a set of rings (an exterior, holes, several pieces, in any order and orientation; rings may self-intersect,
+ * repeat vertices, have zero area or leave the frame), filled under the even-odd rule sampled at pixel centres, in exact integer
+ * arithmetic on 1/256-pixel fixed point.  A vertex (x, y) -- x right, y down, pixel corners at integers, as rmem_label_polygons
+ * emits them -- is X = rint(256 x), Y = rint(256 y) (ties to even), |x|, |y| <= 2^20.  The centre of pixel (y, x) is
+ * (256 x + 128, 256 y + 128).  An edge (X0, Y0) -> (X1, Y1), oriented so that Y0 < Y1, crosses the sample row of y iff
+ * Y0 <= 256 y + 128 < Y1; horizontal edges cross nothing.  A crossing toggles every pixel of that row from column c on, c the
+ * smallest integer with (256 c + 128) * dY >= X0 * dY + (256 y + 128 - Y0) * dX, clamped to 0..W (dX = X1 - X0, dY = Y1 - Y0;
+ * every term stays below 2^59).  A pixel belongs to the shape iff it was toggled an odd number of times.  So left and top edges
+ * are inclusive, right and bottom ones exclusive, and shapes that share an edge neither overlap nor leave a gap; the rings of
+ * rmem_label_polygons fill back to exactly the pixels they were traced from.  (Not pycocotools' frPoly, which upsamples the
+ * outline five times and rounds in its own way: masks can differ from it in boundary pixels.)
+ * A stack.  Frame f lists its shapes in painting order, each with a label value 1..255: label[shape] = value in listing order (the
+ * later shape wins), 0 under no shape.  Every byte of the frames of the pass is written by the call.
+ * Input, all device, built by the host:
+ *   edge_xy     int32 [nedges][4], 16-byte aligned: (X0, Y0, X1, Y1) of every edge that crosses a sample row of the frame, in any
+ *               orientation, listed shape by shape.
+ *   edge_shape  int32 [nedges]: the edge's shape (index into shapes).
+ *   edge_first  int32 [nedges + 1]: the exclusive prefix of the edges' crossing counts (an edge's count: the rows y in 0..H-1 it
+ *               crosses); edge_first[nedges] is the total, at most 2^31 - 1.
+ *   shapes      RmemPolyShape [nshapes]: frame (non-decreasing along the table), value, the box of the pixels whose centres the
+ *               shape can cover, clipped to the frame (columns x0..x1-1, rows y0..y1-1; empty: the shape paints nothing and has no
+ *               plane), and the word offset of its bit plane -- (y1 - y0) rows of ceil((x1 - x0) / 32) 32-bit words, bit i of a
+ *               row = column x0 + i -- among the planes of the whole table.
+ *   frame_shape int32 [frames + 1]: the first shape of every frame; frame_shape[frames] = nshapes.
+ * pass (host): the frames the call fills and what belongs to them -- the shapes listed for those frames, their edges, the crossings
+ * of those edges (cross0 = edge_first[edge0]), and the planes (plane0 = the first plane's offset, plane_words = their sum).  One
+ * table can so be filled in several passes when the planes of all frames exceed the workspace the caller wants to spend.
+ * workspace: rmem_polygon_fill_workspace_bytes(plane_words) bytes, 16-byte aligned (0 for refused arguments); the call clears the
+ * pass's planes itself, a dirty workspace never shows.
+ * status (device, int32 [nshapes]) is written for every shape of the pass, 0 = painted.  Every index read from device memory is
+ * range-checked before it is used; a failed check sets a bit instead of making the access, and a shape with a non-zero status paints
+ * nothing:
+ *   ST_DESC    frame outside the pass or below the frame of the shape before, the shape outside its frame's range in frame_shape,
+ *              value outside 1..255, a box outside the frame, a plane outside the pass's planes; also set when an edge names a
+ *              shape outside the pass (on the pass's first or last shape, whichever is nearer to the name)
+ *   ST_PREFIX  the crossing prefix disagrees with an edge (more crossings than the edge has rows, a decreasing prefix)
+ *   ST_EDGE    an edge coordinate beyond 2^28, or a crossing in a row outside the shape's box
+ * Edges without a crossing in the pass are never looked at.  5 launches per pass (a memset, the check, one thread per crossing,
+ * one per plane row, one per 16 output bytes); the only atomics are integer XOR and OR: the bytes do not depend on the order of
+ * arrival.  Every loop is bounded.
+ * Refused (non-zero, nothing launched): null pointers, frames outside 1..65535, non-positive H / W, H * W above 2^26, nshapes
+ * outside 1..65535*255, nedges outside 0..2^30, a pass whose frames, shapes or edges are no range of the tables', whose crossings
+ * leave 0..2^31-1 or exist without edges, whose plane words leave 0..2^34; a misaligned workspace or edge_xy, a workspace smaller
+ * than the query says.
+ * Replaces a host rasteriser per frame and object (Pillow, pycocotools) and the upload of H * W bytes per frame. */
+typedef struct RmemPolyShape {
+  int frame;            /* 0..frames-1 */
+  int value;            /* 1..255: the label the shape paints */
+  int x0, y0, x1, y1;   /* the box, clipped to the frame */
+  long long plane;      /* word offset of the shape's bit plane */
+} RmemPolyShape;
+typedef struct RmemPolyPass {
+  int frame0, frames;
+  int shape0, shapes;
+  int edge0, edges;
+  long long cross0, crossings;
+  long long plane0, plane_words;
+} RmemPolyPass;
+#define RMEM_POLYFILL_ST_DESC 1
+#define RMEM_POLYFILL_ST_PREFIX 2
+#define RMEM_POLYFILL_ST_EDGE 4
+size_t rmem_polygon_fill_workspace_bytes(long long plane_words);   /* host only, 0 for refused arguments */
+int rmem_polygon_fill_labels(const int* edge_xy, const int* edge_shape, const int* edge_first, int nedges,
+                             const RmemPolyShape* shapes /* device */, int nshapes, const int* frame_shape, int frames, int H, int W,
+                             const RmemPolyPass* pass /* host */, void* workspace, size_t workspace_bytes,
+                             unsigned char* labels /* device [frames][H][W] */, int* status /* device [nshapes] */, void* stream);
+
 /* Region-similarity (Jaccard) counts per object id for one mask pair: counts[2*id] += |pred==id & gt==id|,
  * counts[2*id+1] += |pred==id | gt==id| over the n pixels whose ground truth is not `void_label`; the caller zeroes
  * counts (uint64 [2 * num_ids]).  Replaces evaluation/source/metrics.py:6-37 (db_eval_iou) per object. */

@@ -81,6 +81,15 @@ class RleDesc(C.Structure):
     _fields_ = [('frame', C.c_int), ('value', C.c_int), ('offset', C.c_longlong), ('length', C.c_int)]
 
 
+class PolyShape(C.Structure):
+    _fields_ = [(n, C.c_int) for n in ('frame', 'value', 'x0', 'y0', 'x1', 'y1')] + [('plane', C.c_longlong)]
+
+
+class PolyPass(C.Structure):
+    _fields_ = ([(n, C.c_int) for n in ('frame0', 'frames', 'shape0', 'shapes', 'edge0', 'edges')]
+                + [(n, C.c_longlong) for n in ('cross0', 'crossings', 'plane0', 'plane_words')])
+
+
 class LabelRoute(C.Structure):
     _fields_ = [('dst', C.c_void_p), ('overlay', C.c_void_p), ('feed', C.c_void_p), ('twin', C.c_int), ('mode', C.c_int)]
 
@@ -178,6 +187,8 @@ SIGNATURES = {
     'rmem_label_polygons_unit': (_i, []),
     'rmem_label_polygons_workspace_bytes': (C.c_size_t, [_i, _i, _i, _i]),
     'rmem_label_polygons': (_i, [_vp, _i, _i, _i, _i, _i, _i, _vp, C.c_size_t, _vp, _vp, _vp, _vp]),
+    'rmem_polygon_fill_workspace_bytes': (C.c_size_t, [_ll]),
+    'rmem_polygon_fill_labels': (_i, [_vp, _vp, _vp, _i, _vp, _i, _vp, _i, _i, _i, C.POINTER(PolyPass), _vp, C.c_size_t, _vp, _vp, _vp]),
     'rmem_mask_iou_counts': (_i, [_vp, _vp, _ll, _i, _i, _vp, _vp]),
     'rmem_clip_score_workspace_bytes': (C.c_size_t, [_i, _i, _i, _i]),
     'rmem_boundary_radius': (_i, [_i, _i, C.c_double]),

@@ -530,6 +530,22 @@ def labels_from_rles(frames: Sequence[Dict], size: Tuple[int, int], device, ids:
     return rle.decode_label_stack(listed, size, device), ids
 
 
+def labels_from_polygons(frames: Sequence[Dict], size: Tuple[int, int], device, ids: Optional[Sequence] = None):
+    """labels_from_rles' twin for polygon tracks (CVAT, Labelme, COCO `segmentation` lists: frames[f] = {track id: shape}, a shape
+    in any form polygons.PackedPolygons takes) -> (uint8 [n, H, W] label maps on the device, ids): track ids[i] is label value
+    i + 1, ids defaults to the sorted union of the keys; tracks not in ids are left out.  Filled on the device
+    (polygons.fill_label_stack: the even-odd rule at pixel centres, not pycocotools' frPoly): only the edges cross to it.  The stack
+    feeds protocol.clip_protocol, run_annotated_clips, score_clip and score_annotated_clip exactly as labels_from_pngs' does.
+    More than 255 tracks raise RmemError."""
+    from . import polygons
+    ids = sorted({k for fr in frames for k in fr}) if ids is None else list(ids)
+    if len(ids) > 255:
+        raise _lib.RmemError(f'labels_from_polygons: {len(ids)} tracks (at most 255 fit one uint8 label stack)')
+    value = {k: i + 1 for i, k in enumerate(ids)}
+    listed = [[(value[k], s) for k, s in fr.items() if k in value] for fr in frames]
+    return polygons.fill_label_stack(listed, size, device), ids
+
+
 def rle_results(labels_u8: torch.Tensor, num_objs: int, squeeze_idx: Optional[Sequence[int]] = None, boxes: bool = False,
                 ascii: bool = True) -> List[Dict[int, dict]]:
     """save_masks' twin for run-length submissions: per frame of a stack of device label maps ([n, H, W] or [H, W] uint8 --

@@ -10,6 +10,16 @@ Replaces labels.cpu() and a sequential border follower per frame and object: onl
     rings, verts, counts = polygons.trace(labels, num_objs)                     # device tensors, no host sync
     per_frame = polygons.trace_label_stack(labels, num_objs, squeeze_idx=idx)   # [{object id: [{'exterior', 'area2', 'holes'}]}]
     per_frame = evaluator.polygon_results(labels, num_objs, idx, holes='drop')  # [{object id: {'size', 'segmentation', 'area'}}]
+
+The other direction: annotation polygons filled into a uint8 label stack on the device (include/rmem.h,
+rmem_polygon_fill_labels, has the contract: the even-odd rule sampled at pixel centres, exact on 1/256-pixel fixed point, left
+and top edges inclusive; what `trace` emits fills back to exactly the pixels it came from).  PackedPolygons quantises and flattens
+a clip's shapes on the host; only their edges cross to the device.  Replaces a host rasteriser per frame and object and the upload
+of H * W bytes per frame.  Not pycocotools' frPoly (a five times upsampled outline with its own rounding), nor Pillow's
+ImageDraw.polygon (which also draws the outline): masks can differ from either in boundary pixels.
+
+    gt = polygons.fill_label_stack(frames, (H, W), device)                      # frames[f] = {label value: shape}; uint8 [n, H, W]
+    gt, ids = evaluator.labels_from_polygons(frames, (H, W), device)            # frames[f] = {track id: shape}; value i + 1 = ids[i]
 """
 from __future__ import annotations
 
@@ -19,12 +29,20 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._codec import workspace
-from ._labels import connectivity as _connectivity, frames_per_pass, int_in, is_int, object_keys, stack as _frames
+from ._codec import Packed, stream_of, workspace
+from ._labels import MAX_FRAMES, MAX_PIXELS, WORKSPACE_CAP, connectivity as _connectivity, frames_per_pass, int_in, is_int, object_keys, stack as _frames
 from ._lib import RmemError
 
 ST_CAPACITY, ST_LINK, ST_ORDER = 1, 2, 4     # include/rmem.h
 MAX_EDGES = 2 ** 31 - 1
+FILL_ST_DESC, FILL_ST_PREFIX, FILL_ST_EDGE = 1, 2, 4
+FILL_STATUS_NAMES = {FILL_ST_DESC: 'bad shape table entry, or an edge of a shape outside the pass',
+                     FILL_ST_PREFIX: 'the crossing prefix disagrees with an edge',
+                     FILL_ST_EDGE: 'an edge coordinate out of range or a crossing outside the shape\'s box'}
+FIXED = 256                                  # fixed-point steps per pixel
+MAX_COORD = 2 ** 20                          # |x|, |y| of a vertex, in pixels
+MAX_CROSSINGS = 2 ** 31 - 1
+SHAPE_DTYPE = np.dtype([('frame', '<i4'), ('value', '<i4'), ('x0', '<i4'), ('y0', '<i4'), ('x1', '<i4'), ('y1', '<i4'), ('plane', '<i8')])   # RmemPolyShape
 
 
 def unit() -> int:
@@ -206,3 +224,244 @@ def coco_polygons(frames: List[Dict], size: Tuple[int, int], holes: str = 'rings
 def _area2(ring: np.ndarray) -> int:
     x, y = ring[:, 0].astype(np.int64), ring[:, 1].astype(np.int64)
     return int(np.sum(x * np.roll(y, -1) - np.roll(x, -1) * y))
+
+
+# ---------------------------------------------------------------------------------------------------------------- filling
+
+def _is_number(v) -> bool:
+    return isinstance(v, (int, float, np.integer, np.floating)) and not isinstance(v, bool)
+
+
+def _is_pair(v) -> bool:
+    return isinstance(v, (list, tuple, np.ndarray)) and len(v) == 2 and all(_is_number(c) for c in v)
+
+
+def _ring(r, where: str) -> np.ndarray:
+    """float64 [k, 2], k >= 3, of a ring given as [k, 2] or flat"""
+    try:
+        a = np.asarray(r, dtype=np.float64)
+    except (TypeError, ValueError):
+        a = None
+    if a is not None and a.ndim == 1:
+        if a.size % 2:
+            raise RmemError(f'PackedPolygons: {where}: a flat ring of {a.size} numbers (x0, y0, x1, y1, ...: an even count)')
+        a = a.reshape(-1, 2)
+    if a is None or a.ndim != 2 or a.shape[1] != 2:
+        raise RmemError(f'PackedPolygons: {where}: a ring is an array-like [k, 2] of (x, y) or a flat sequence x0, y0, x1, y1, ...')
+    if a.shape[0] < 3:
+        raise RmemError(f'PackedPolygons: {where}: a ring of {a.shape[0]} vertices (at least 3)')
+    return a
+
+
+def _rings_of(shape, size: Tuple[int, int], where: str) -> List[np.ndarray]:
+    """the rings of a shape in any of the forms PackedPolygons takes"""
+    if isinstance(shape, dict):
+        if 'segmentation' in shape:
+            if 'size' in shape and tuple(int(v) for v in shape['size']) != size:
+                raise RmemError(f'PackedPolygons: {where}: size {list(shape["size"])} differs from the stack\'s {list(size)}')
+            return [_ring(r, where) for r in list(shape['segmentation']) + list(shape.get('holes', ()))]
+        if 'exterior' in shape:
+            return [_ring(shape['exterior'], where)] + [_ring(h, where) for h in shape.get('holes', ())]
+        raise RmemError(f'PackedPolygons: {where}: a polygon dict has \'exterior\' (and \'holes\') or \'segmentation\'')
+    if isinstance(shape, np.ndarray):
+        return [_ring(shape, where)] if shape.ndim <= 2 else [_ring(r, where) for r in shape]
+    if isinstance(shape, (list, tuple)):
+        if len(shape) == 0:
+            return []
+        if all(_is_number(v) for v in shape) or all(_is_pair(v) for v in shape):
+            return [_ring(shape, where)]
+        out: List[np.ndarray] = []
+        for item in shape:
+            out += _rings_of(item, size, where) if isinstance(item, dict) else [_ring(item, where)]
+        return out
+    raise RmemError(f'PackedPolygons: {where}: a shape is a ring, a list of rings, a polygon dict or a list of polygon dicts')
+
+
+class PackedPolygons(Packed):
+    """A clip's polygon annotations, packed once: frames[f] is {value: shape} or [(value, shape), ...] (listing order = painting
+    order, the later shape wins where two overlap; at most 255 per frame), value the label (1..255) the shape paints.  A shape
+    is a set of rings filled under the even-odd rule (include/rmem.h, rmem_polygon_fill_labels), given as one ring, a list of
+    rings (an empty list paints nothing), a polygon dict of trace_label_stack ({'exterior': ring, 'holes': [ring, ...]}, other
+    keys ignored), a list of such dicts (trace_label_stack(...)[f][k]), or a COCO-shaped entry {'segmentation': [flat ring, ...]}
+    with an optional 'holes': [flat ring, ...] (evaluator.polygon_results(...)[f][k]; its 'size', if present, must equal size).
+    A ring is an array-like [k, 2] of (x, y) -- x right, y down, pixel corners at integers, any fractions -- or a flat sequence
+    x0, y0, x1, y1, ...; a list whose elements are all pairs of numbers is one [k, 2] ring.  size = (H, W) of the stack.
+    Packing needs no GPU: it quantises the vertices to 1/256 pixel (numpy.rint, ties to even), flattens every shape into its edges
+    that cross a sample row of the frame, and computes every shape's box and bit-plane offset and the prefix of the edges'
+    crossing counts.  One pinned int32 buffer holds edge_xy [E, 4], edge_shape [E], edge_first [E + 1] and frame_shape [n + 1];
+    the shape table (RmemPolyShape) is the descriptor table.  len() is the number of shapes; status words are per shape.
+    Not pycocotools' frPoly rule: masks can differ from it in boundary pixels."""
+    NOUN, STATUS_NAMES = 'polygon shape', FILL_STATUS_NAMES
+
+    def __init__(self, frames: Sequence, size: Tuple[int, int]):
+        self.height, self.width = H, W = int(size[0]), int(size[1])
+        n = len(frames)
+        if n < 1 or n > MAX_FRAMES or H < 1 or W < 1 or H * W > MAX_PIXELS:
+            raise RmemError(f'PackedPolygons: {n} frames of {H}x{W} (at least one frame, at most 65535, H * W at most 2^26)')
+        self.shape = torch.Size((n, H, W))
+        self.where: List[Tuple[int, int]] = []
+        rings: List[np.ndarray] = []
+        ring_shape: List[int] = []
+        for f, entry in enumerate(frames):
+            items = list(entry.items()) if isinstance(entry, dict) else list(entry)
+            if len(items) > 255:
+                raise RmemError(f'PackedPolygons: frame {f} lists {len(items)} shapes (at most 255)')
+            for value, shape in items:
+                if not _is_number(value) or int(value) != value or not 1 <= int(value) <= 255:
+                    raise RmemError(f'PackedPolygons: frame {f}: label value {value!r} outside 1..255')
+                mine = _rings_of(shape, (H, W), f'frame {f}, value {value}')
+                rings += mine
+                ring_shape += [len(self.where)] * len(mine)
+                self.where.append((f, int(value)))
+        S = self.nshapes = len(self.where)
+        lens = np.array([len(r) for r in rings], dtype=np.int64)
+        V = np.concatenate(rings) if rings else np.zeros((0, 2), dtype=np.float64)
+        bad = np.flatnonzero(~(np.abs(V) <= MAX_COORD).all(axis=1))            # also every NaN and infinity
+        ends = np.cumsum(lens)
+        if bad.size:
+            f, v = self.where[ring_shape[int(np.searchsorted(ends, bad[0], side='right'))]]
+            x, y = V[bad[0]]
+            raise RmemError(f'PackedPolygons: frame {f}, value {v}: vertex ({x}, {y}) is not finite or beyond 2^20 pixels')
+        Q = np.rint(V * FIXED).astype(np.int64)
+        nxt = np.arange(len(Q), dtype=np.int64) + 1
+        nxt[ends - 1] = ends - lens                                            # a ring's last vertex joins its first
+        of_vertex = np.repeat(np.array(ring_shape, dtype=np.int64), lens)      # the shape of every vertex, and of the edge it starts
+        table = np.zeros(S, dtype=SHAPE_DTYPE)
+        table['frame'], table['value'] = [w[0] for w in self.where], [w[1] for w in self.where]
+        per_shape = np.bincount(of_vertex, minlength=S)
+        held = np.flatnonzero(per_shape)
+        if held.size:                                                          # the pixels whose centres a shape can cover, in the frame
+            at = (np.cumsum(per_shape) - per_shape)[held]
+            for lo, hi, col, top in (('x0', 'x1', 0, W), ('y0', 'y1', 1, H)):
+                table[lo][held] = np.clip((np.minimum.reduceat(Q[:, col], at) + 127) >> 8, 0, top)
+                table[hi][held] = np.clip((np.maximum.reduceat(Q[:, col], at) + 127) >> 8, 0, top)
+        empty = (table['x0'] >= table['x1']) | (table['y0'] >= table['y1'])
+        for k in ('x0', 'y0', 'x1', 'y1'):
+            table[k][empty] = 0
+        words = (table['y1'] - table['y0']).astype(np.int64) * ((table['x1'] - table['x0'] + 31) >> 5)
+        table['plane'] = np.cumsum(words) - words
+        X0, Y0, X1, Y1 = Q[:, 0], Q[:, 1], Q[nxt, 0], Q[nxt, 1]
+        rows = np.minimum(H, (np.maximum(Y0, Y1) + 127) >> 8) - np.maximum(0, (np.minimum(Y0, Y1) + 127) >> 8)
+        keep = (rows > 0) & ~empty[of_vertex]                                  # the edges that cross a sample row of a shape with a plane
+        self.edge_xy = np.stack([X0, Y0, X1, Y1], axis=1)[keep].astype(np.int32)
+        self.edge_shape = of_vertex[keep].astype(np.int32)
+        first = np.concatenate([[0], np.cumsum(rows[keep])])
+        E = self.nedges = int(keep.sum())
+        self.crossings = int(first[-1])
+        if self.crossings > MAX_CROSSINGS:
+            raise RmemError(f'PackedPolygons: the edges cross {self.crossings} sample rows (at most 2^31 - 1); pack fewer frames')
+        self.edge_first = first.astype(np.int32)
+        self.table = table
+        self.frame_shape = np.searchsorted(table['frame'], np.arange(n + 1), side='left').astype(np.int32)
+        self.shape_edge = np.searchsorted(self.edge_shape, np.arange(S + 1), side='left').astype(np.int64)   # the first edge of every shape
+        fs = self.frame_shape.astype(np.int64)
+        total = np.concatenate([[0], np.cumsum(words)])
+        self.frame_words = total[fs[1:]] - total[fs[:-1]]                      # plane words per frame
+        self.plane_words = int(total[-1])
+        self.offsets = (0, 16 * E, 20 * E, 24 * E + 4)                         # bytes: edge_xy, edge_shape, edge_first, frame_shape
+        blob = np.concatenate([self.edge_xy.reshape(-1), self.edge_shape, self.edge_first, self.frame_shape]).astype(np.int32)
+        self.buf = torch.from_numpy(blob.view(np.uint8))
+        self.descs = table
+        self.desc_bytes = torch.from_numpy(table.view(np.uint8).reshape(-1).copy() if S else np.zeros(SHAPE_DTYPE.itemsize, dtype=np.uint8))
+        if torch.cuda.is_available():                                          # packing itself needs no GPU
+            self.buf, self.desc_bytes = self.buf.pin_memory(), self.desc_bytes.pin_memory()
+        self._dev = {}
+
+    def __len__(self):
+        return self.nshapes
+
+    def passes(self, workspace_bytes: Optional[int] = None) -> List[_lib.PolyPass]:
+        """The passes of whole frames fill_labels_into makes: as many consecutive frames each as keep
+        rmem_polygon_fill_workspace_bytes of their planes at or below workspace_bytes (default: _labels.WORKSPACE_CAP, or the
+        largest frame's need where that is larger); a budget below the largest frame's need is refused."""
+        need = _lib.lib().rmem_polygon_fill_workspace_bytes
+        largest = int(need(int(self.frame_words.max())))
+        if workspace_bytes is None:
+            workspace_bytes = max(largest, min(int(need(self.plane_words)), WORKSPACE_CAP))
+        elif not is_int(workspace_bytes) or workspace_bytes < largest:
+            raise RmemError(f'polygons.fill_labels_into: workspace_bytes must be an integer of at least the largest frame\'s need, '
+                            f'{largest} bytes (got {workspace_bytes!r})')
+        n = self.shape[0]
+        fs, out, f0 = self.frame_shape, [], 0
+        while f0 < n:
+            f1, words = f0 + 1, int(self.frame_words[f0])
+            while f1 < n and int(need(words + int(self.frame_words[f1]))) <= workspace_bytes:
+                words += int(self.frame_words[f1])
+                f1 += 1
+            s0, s1 = int(fs[f0]), int(fs[f1])
+            e0, e1 = int(self.shape_edge[s0]), int(self.shape_edge[s1])
+            c0, c1 = int(self.edge_first[e0]), int(self.edge_first[e1])
+            plane0 = int(self.table['plane'][s0]) if s0 < self.nshapes else self.plane_words
+            out.append(_lib.PolyPass(f0, f1 - f0, s0, s1 - s0, e0, e1 - e0, c0, c1 - c0, plane0, words))
+            f0 = f1
+        return out
+
+    def check(self, device, first: int = 0, count: Optional[int] = None, stream=None):
+        """Packed.check, naming the frame and the label value of the first bad shape as well"""
+        try:
+            super().check(device, first, count, stream)
+        except RmemError as e:
+            st = self.status(device)[first:first + (len(self) - first if count is None else count)].cpu()
+            k = first + int(torch.nonzero(st).flatten()[0])
+            raise RmemError(f'{e} [shape {k}: frame {self.where[k][0]}, value {self.where[k][1]}]') from None
+
+
+def fill_pass(packed: PackedPolygons, dc, p: _lib.PolyPass, ws: torch.Tensor, out: torch.Tensor, raw_stream: int):
+    """one call of rmem_polygon_fill_labels: pass p of `packed`, whose buffers on the device are dc, into out on a raw stream"""
+    import ctypes
+    n, H, W = packed.shape
+    base = dc.bits.data_ptr()
+    xy, shape, first, frames = (base + o for o in packed.offsets)
+    _lib.check(_lib.lib().rmem_polygon_fill_labels(xy, shape, first, packed.nedges, dc.descs.data_ptr(), packed.nshapes, frames, n, H, W,
+                                                   ctypes.byref(p), ws.data_ptr(), ws.numel(), out.data_ptr(), dc.status.data_ptr(),
+                                                   raw_stream), 'rmem_polygon_fill_labels')
+
+
+def fill_labels_into(packed: PackedPolygons, out: torch.Tensor, stream=None, workspace_bytes: Optional[int] = None):
+    """Every frame of `packed` into out (uint8 [n, H, W], contiguous, device) on ``stream`` (a torch.cuda.Stream or a raw handle;
+    default: the current stream).  Nothing waits for the GPU: the pack is copied from pinned memory on the stream, the status
+    words land in packed.status(device) and are read later by packed.check(device).  The frames go in passes of whole frames
+    whose bit planes fit workspace_bytes (PackedPolygons.passes: 256 MiB by default, or the largest frame's need); a smaller
+    budget is refused.  A pack without any shape zero-fills out."""
+    what = 'polygons.fill_labels_into'
+    if not isinstance(packed, PackedPolygons):
+        raise RmemError(f'{what}: packed must be a PackedPolygons')
+    if not isinstance(out, torch.Tensor) or out.dtype != torch.uint8 or not out.is_cuda:
+        raise RmemError(f'{what}: out must be a uint8 device tensor')
+    if tuple(out.shape) != tuple(packed.shape) or not out.is_contiguous():
+        raise RmemError(f'{what}: out must be a contiguous {list(packed.shape)} tensor (got {list(out.shape)})')
+    plan = packed.passes(workspace_bytes)
+    dev = out.device
+    ts = stream_of(dev, stream)
+    if packed.nshapes == 0:
+        with torch.cuda.stream(ts):
+            out.zero_()
+        return
+    need = _lib.lib().rmem_polygon_fill_workspace_bytes
+    dc = packed.on_device(dev)
+    ws = workspace('polygons.fill', dev, ts, max(int(need(p.plane_words)) for p in plan))
+    dc.used_on(ts)
+    out.record_stream(ts)
+    from . import ops
+    ops.copy_async(dc.bits[:packed.buf.numel()], packed.buf, packed.buf.numel())(ts.cuda_stream)
+    for p in plan:
+        fill_pass(packed, dc, p, ws, out, ts.cuda_stream)
+
+
+def fill_label_stack(frames, size: Optional[Tuple[int, int]] = None, device=None) -> torch.Tensor:
+    """uint8 [n, H, W] label maps on `device` of a clip's polygon annotations (what PackedPolygons takes, or a PackedPolygons):
+    label[shape] = value per frame in listing order, 0 under no shape, under the even-odd rule at pixel centres (include/rmem.h;
+    not pycocotools' frPoly: boundary pixels can differ from it).  One fill, then one synchronisation and one readback of the
+    status words: a non-zero word raises RmemError naming the shape and the reasons."""
+    device = torch.device(device)
+    if device.type != 'cuda':
+        raise RmemError('polygons.fill_label_stack: the target must be a GPU device (there is no host rasteriser)')
+    if device.index is None:
+        device = torch.device('cuda', torch.cuda.current_device())
+    packed = frames if isinstance(frames, PackedPolygons) else PackedPolygons(frames, size)
+    stream = torch.cuda.current_stream(device)
+    out = torch.empty(tuple(packed.shape), dtype=torch.uint8, device=device)
+    fill_labels_into(packed, out, stream)
+    if packed.nshapes:
+        packed.check(device, 0, packed.nshapes, stream)
+    return out
