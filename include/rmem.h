@@ -722,6 +722,53 @@ size_t rmem_label_polygons_workspace_bytes(int n, int H, int W, int max_edges); 
 int rmem_label_polygons(const unsigned char* labels, int n, int H, int W, int num_objs, int connectivity, int max_edges,
                         void* workspace, size_t workspace_bytes, int* rings, int* verts, int* counts, void* stream);
 
+/* The rings of rmem_label_polygons simplified (Douglas-Peucker, exact): a traced ring is a pixel staircase with a vertex at every
+ * corner; a person who corrects a track in a labelling tool wants tens of points per object (polygons.py: simplify,
+ * trace_label_stack(tolerance=...); evaluator.polygon_results(tolerance=...)).  One call on `stream` behind the tracer, no host
+ * sync: R and V are read on the device.
+ * Input: rings [max_rings][8], verts [max_verts][2], counts [4] = (E, R, V, status) as rmem_label_polygons writes them.  Only the
+ * columns 2 (first vertex) and 3 (vertex count) of a ring row and the vertices are interpreted: any table of that form is valid,
+ * not only a traced one.  Coordinates lie in 0..32767, which keeps every product below 2^62.
+ * Tolerance.  T = tolerance_16ths, 0..1024: 1/16 pixel steps, at most 64 pixels.
+ * Rule for one ring p_0 .. p_{k-1}, p_k := p_0, k >= 1.  Anchors: vertex 0 and B, the vertex of 1..k-1 farthest from p_0 by squared
+ * distance, the smallest index among equals (k = 1: the output is that one vertex).  Kept = {0, B} + DP(0, B) + DP(B, k).
+ * DP(i, j): nothing when j - i < 2; else m = the vertex of i < m < j with the largest key(m), the smallest m among equals; if
+ * key(m) > thr, m is kept and DP(i, m) and DP(m, j) follow.  key is the squared distance to the SEGMENT p_i p_j times L: with
+ * a = p_j - p_i, L = |a|^2, b = p_m - p_i, t = a.b:  L = 0: key = |b|^2, thr = floor(T^2 / 256);  L > 0: thr = floor(T^2 L / 256)
+ * and key = |b|^2 L if t <= 0, |p_m - p_j|^2 L if t >= L, (a x b)^2 otherwise.  64-bit integers, no division by data; a x b
+ * needs 64 bits before it is squared; every key is below 2^62 and T^2 L below 2^51.  The segment, not the line: a ring can visit
+ * a vertex twice, so p_i = p_j happens.
+ * Output, all device, in the input's ring order:
+ *   rings_out  [max_rings][8]: the input row with column 2 = the new first vertex, column 3 = the kept count, column 7 = the
+ *              original vertex count; column 4 stays the TRACED area2 (the exact pixel area; its sign still tells hole from
+ *              exterior), column 5 the start edge.
+ *   verts_out  [max_verts][2]: the kept vertices in ring order, ring after ring, contiguous.
+ *   counts_out [4]: (V of the input, R, V_out, status).
+ * Rows beyond R and V_out are not written.  A non-zero input status is passed on with R = V_out = 0 and nothing written.
+ * RMEM_SIMPLIFY_ST_TABLE: R outside 0..max_rings, V outside 0..max_verts, or the vertex counts of the rings sum to more than
+ * max_verts (only when rings share vertices, which a traced table never does): (V, 0, 0, RMEM_SIMPLIFY_ST_TABLE), nothing written.
+ * RMEM_SIMPLIFY_ST_RING: a ring row whose (first, count) is no range of 0..V with count >= 1, or a vertex of a ring outside
+ * 0..32767: that ring is emitted with 0 vertices, the others are unaffected.  Every index read from device memory is checked
+ * before use; every loop is bounded, a ring's refinement runs at most its vertex count of rounds.
+ * Properties: the kept vertices are a subsequence of the ring with both anchors; every dropped vertex is within T / 16 of the
+ * segment of its kept neighbours, so ring and simplification are within Hausdorff distance T / 16 of each other, and under the
+ * even-odd fill below a pixel centre farther than that from every ring edge of its frame keeps its value.  Topology is NOT
+ * preserved: a simplified ring may touch or cross itself or a neighbour (as OpenCV's approxPolyDP).  T = 0 drops exactly the
+ * vertices on the segment between their kept neighbours.
+ * 10 launches whatever the data, no workgroup waits for another: a ring of at most rmem_polygon_simplify_short_max() vertices
+ * lives in one wave, a longer one in one workgroup -- one very long ring runs on one compute unit, for as many rounds as its
+ * recursion is deep.  Both classes give the same bytes; integer maxima and minima only: bit-reproducible.
+ * workspace: rmem_polygon_simplify_workspace_bytes(max_rings, max_verts) bytes, 16-byte aligned (0 for refused arguments): 32
+ * bytes per vertex and 24 per ring of capacity (and 12 per 2048 rings); prior contents do not matter.  Refused (non-zero, nothing launched): a null
+ * pointer, a capacity outside 1..2^31-1, tolerance_16ths outside 0..1024, a misaligned or too small workspace. */
+#define RMEM_SIMPLIFY_ST_TABLE 8
+#define RMEM_SIMPLIFY_ST_RING 16
+int rmem_polygon_simplify_short_max(void);   /* host only */
+size_t rmem_polygon_simplify_workspace_bytes(long long max_rings, long long max_verts);   /* host only, 0 for refused arguments */
+int rmem_polygon_simplify(const int* rings, const int* verts, const int* counts, long long max_rings, long long max_verts,
+                          int tolerance_16ths, void* workspace, size_t workspace_bytes, int* rings_out, int* verts_out,
+                          int* counts_out, void* stream);
+
 /* The inverse: annotation polygons filled into uint8 label maps labels[frames][H][W] (contiguous, device, may start at any byte),
  * the way polygon tracks (CVAT, Labelme, COCO `segmentation` lists) enter a run (polygons.py: PackedPolygons, fill_labels_into,
  * fill_label_stack; evaluator.labels_from_polygons).  One call on `stream`, no host sync, no state kept between calls; only the

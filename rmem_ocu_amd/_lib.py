@@ -187,6 +187,9 @@ SIGNATURES = {
     'rmem_label_polygons_unit': (_i, []),
     'rmem_label_polygons_workspace_bytes': (C.c_size_t, [_i, _i, _i, _i]),
     'rmem_label_polygons': (_i, [_vp, _i, _i, _i, _i, _i, _i, _vp, C.c_size_t, _vp, _vp, _vp, _vp]),
+    'rmem_polygon_simplify_short_max': (_i, []),
+    'rmem_polygon_simplify_workspace_bytes': (C.c_size_t, [_ll, _ll]),
+    'rmem_polygon_simplify': (_i, [_vp, _vp, _vp, _ll, _ll, _i, _vp, C.c_size_t, _vp, _vp, _vp, _vp]),
     'rmem_polygon_fill_workspace_bytes': (C.c_size_t, [_ll]),
     'rmem_polygon_fill_labels': (_i, [_vp, _vp, _vp, _i, _vp, _i, _vp, _i, _i, _i, C.POINTER(PolyPass), _vp, C.c_size_t, _vp, _vp, _vp]),
     'rmem_mask_iou_counts': (_i, [_vp, _vp, _ll, _i, _i, _vp, _vp]),

@@ -557,7 +557,7 @@ def rle_results(labels_u8: torch.Tensor, num_objs: int, squeeze_idx: Optional[Se
 
 
 def polygon_results(labels_u8: torch.Tensor, num_objs: int, squeeze_idx: Optional[Sequence[int]] = None, holes: str = 'rings',
-                    connectivity: int = 8) -> List[Dict[int, dict]]:
+                    connectivity: int = 8, tolerance: Optional[float] = None) -> List[Dict[int, dict]]:
     """rle_results' twin for polygon consumers (COCO `segmentation` lists, CVAT / Labelme tracks): per frame of a stack of device
     label maps ([n, H, W] or [H, W] uint8) {object id: {'size': [H, W], 'segmentation': [[x0, y0, x1, y1, ...], ...], 'area': int}}
     for the objects 1..num_objs, one ring of pixel corners per connected piece, traced on the device
@@ -565,12 +565,19 @@ def polygon_results(labels_u8: torch.Tensor, num_objs: int, squeeze_idx: Optiona
     keys.  'area' is the sum of the listed rings' area2 divided by 2.
     holes='rings': a key 'holes' of the same shape lists the holes' rings (their area2 is negative, so 'area' is the pixel count).
     holes='drop': only the exteriors are listed, which FILLS every hole -- COCO's polygon list cannot express one -- and 'area'
-    is the filled area; use rle_results where holes matter."""
+    is the filled area; use rle_results where holes matter.
+    tolerance (pixels, 0..64; None: nothing changes): the rings are simplified on the device (polygons.simplify: Douglas-Peucker,
+    every dropped vertex within the tolerance of its ring; rings may then touch or cross) and degenerate ones dropped.  'area' is
+    then a FLOAT, the shoelace area of the rings the entry lists: exteriors minus the listed holes under holes='rings', exteriors
+    alone under 'drop' -- no longer the pixel count."""
     from . import polygons
     if holes not in ('rings', 'drop'):
         raise _lib.RmemError(f'polygon_results: holes must be \'rings\' or \'drop\' (got {holes!r})')
-    frames = polygons.trace_label_stack(labels_u8, num_objs, connectivity, squeeze_idx, parents=True)
-    return polygons.coco_polygons(frames, labels_u8.shape[-2:], holes)
+    if tolerance is None:
+        frames = polygons.trace_label_stack(labels_u8, num_objs, connectivity, squeeze_idx, parents=True)
+        return polygons.coco_polygons(frames, labels_u8.shape[-2:], holes)
+    frames = polygons.trace_label_stack(labels_u8, num_objs, connectivity, squeeze_idx, parents=True, tolerance=tolerance)
+    return polygons.coco_polygons(frames, labels_u8.shape[-2:], holes, simplified=True)
 
 
 class SequenceEvaluator:

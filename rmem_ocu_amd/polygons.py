@@ -11,6 +11,15 @@ Replaces labels.cpu() and a sequential border follower per frame and object: onl
     per_frame = polygons.trace_label_stack(labels, num_objs, squeeze_idx=idx)   # [{object id: [{'exterior', 'area2', 'holes'}]}]
     per_frame = evaluator.polygon_results(labels, num_objs, idx, holes='drop')  # [{object id: {'size', 'segmentation', 'area'}}]
 
+Traced rings are pixel staircases; simplify thins them on the device under a tolerance in pixels (include/rmem.h,
+rmem_polygon_simplify, has the contract: Douglas-Peucker against the segment, exact in 64-bit integers, 1/16 pixel steps).  Every
+dropped vertex is within the tolerance of the simplified ring, and filling the simplified rings back changes no pixel whose centre
+is farther than the tolerance from every ring edge of its frame.  Topology is NOT preserved: a simplified ring may touch or cross
+itself or a neighbour, as with OpenCV's approxPolyDP; the even-odd fill takes such rings as they come.
+
+    rings_s, verts_s, counts_s = polygons.simplify(rings, verts, counts, 1.0)   # device tensors, no host sync
+    per_frame = polygons.trace_label_stack(labels, num_objs, tolerance=1.0)     # the same dicts with tens of vertices per ring
+
 The other direction: annotation polygons filled into a uint8 label stack on the device (include/rmem.h,
 rmem_polygon_fill_labels, has the contract: the even-odd rule sampled at pixel centres, exact on 1/256-pixel fixed point, left
 and top edges inclusive; what `trace` emits fills back to exactly the pixels it came from).  PackedPolygons quantises and flattens
@@ -35,6 +44,8 @@ from ._lib import RmemError
 
 ST_CAPACITY, ST_LINK, ST_ORDER = 1, 2, 4     # include/rmem.h
 MAX_EDGES = 2 ** 31 - 1
+TOLERANCE_STEPS, MAX_TOLERANCE = 16, 64      # simplify: steps per pixel and the largest tolerance, in pixels
+SIMPLIFY_ST_TABLE, SIMPLIFY_ST_RING = 8, 16
 FILL_ST_DESC, FILL_ST_PREFIX, FILL_ST_EDGE = 1, 2, 4
 FILL_STATUS_NAMES = {FILL_ST_DESC: 'bad shape table entry, or an edge of a shape outside the pass',
                      FILL_ST_PREFIX: 'the crossing prefix disagrees with an edge',
@@ -96,6 +107,76 @@ def trace(labels_u8: torch.Tensor, num_objs: int, connectivity: int = 8,
     return rings, verts, counts
 
 
+def short_max() -> int:
+    """vertices of the longest ring that `simplify` gives one wave: where its two kernels' seam lies"""
+    return int(_lib.lib().rmem_polygon_simplify_short_max())
+
+
+def _steps(what: str, tolerance) -> int:
+    """T of include/rmem.h: rint(16 * tolerance) of a finite number in 0..64"""
+    if not _is_number(tolerance) or not 0 <= float(tolerance) <= MAX_TOLERANCE:         # NaN fails both comparisons
+        raise RmemError(f'{what}: tolerance must be a finite number in 0..{MAX_TOLERANCE} pixels (got {tolerance!r})')
+    return int(np.rint(TOLERANCE_STEPS * float(tolerance)))
+
+
+def simplify(rings: torch.Tensor, verts: torch.Tensor, counts: torch.Tensor, tolerance: float) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """(rings_s, verts_s, counts_s) on the device, shaped like the inputs: the table of `trace` -- or any int32 table of that form
+    -- with every ring thinned by Douglas-Peucker under `tolerance` pixels (0..64, rounded to 1/16; include/rmem.h,
+    rmem_polygon_simplify, has the rule).  rings_s[:R] are the input's rows with the new first vertex, the kept count and, in
+    column 7, the original count; area2 stays the TRACED area.  verts_s[:V_out] are the kept vertices, ring after ring; counts_s =
+    (V, R, V_out, status).  Rows beyond R and V_out are not written.  A non-zero status of the input is passed on with R = V_out =
+    0; SIMPLIFY_ST_TABLE: counts that do not fit the tensors; SIMPLIFY_ST_RING: a bad ring row or a coordinate outside 0..32767,
+    that ring has 0 vertices.  Every dropped vertex is within the tolerance of the segment between its kept neighbours; topology
+    is NOT preserved: a simplified ring may touch or cross itself or a neighbour.  One call on the current stream, no host sync;
+    the workspace is one buffer per (device, stream) that only grows."""
+    what = 'polygons.simplify'
+    T = _steps(what, tolerance)
+    for name, t, cols in (('rings', rings, 8), ('verts', verts, 2), ('counts', counts, None)):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.int32:
+            raise RmemError(f'{what}: {name} must be an int32 tensor')
+        if not t.is_contiguous() or (t.dim() != 2 or t.shape[1] != cols or t.shape[0] < 1 if cols else tuple(t.shape) != (4,)):
+            raise RmemError(f'{what}: {name} must be a contiguous ' + (f'[k, {cols}] tensor, k >= 1' if cols else '[4] tensor')
+                            + f' (got {tuple(t.shape)}, strides {tuple(t.stride())})')
+    if not rings.device == verts.device == counts.device:
+        raise RmemError(f'{what}: rings, verts and counts must be on one device')
+    if not rings.is_cuda:
+        raise RmemError(f'{what}: rings, verts and counts must be device tensors (there is no host simplifier)')
+    MR, MV = rings.shape[0], verts.shape[0]
+    L = _lib.lib()
+    nbytes = int(L.rmem_polygon_simplify_workspace_bytes(MR, MV))
+    if nbytes == 0:
+        raise RmemError(f'{what}: at most 2^31 - 1 rings and vertices (got {MR}, {MV})')
+    dev = rings.device
+    stream = torch.cuda.current_stream(dev)
+    ws = workspace('polygons.simplify', dev, stream, nbytes)
+    rings_s, verts_s, counts_s = torch.empty_like(rings), torch.empty_like(verts), torch.empty_like(counts)
+    _lib.check(L.rmem_polygon_simplify(rings.data_ptr(), verts.data_ptr(), counts.data_ptr(), MR, MV, T, ws.data_ptr(), ws.numel(),
+                                       rings_s.data_ptr(), verts_s.data_ptr(), counts_s.data_ptr(), stream.cuda_stream),
+               'rmem_polygon_simplify')
+    for t in (rings, verts, counts):
+        t.record_stream(stream)
+    return rings_s, verts_s, counts_s
+
+
+def drop_degenerate(frames: List[Dict]) -> List[Dict]:
+    """trace_label_stack's degenerate='drop', pure host code, in place: an exterior with fewer than 3 vertices or a zero shoelace
+    sum leaves with its holes; so does such a hole (under the key None too)"""
+    def alive(ring):                                                # plain integers: most rings have a handful of vertices
+        if len(ring) < 3:
+            return False
+        p = ring.tolist()
+        return sum(x0 * y1 - x1 * y0 for (x0, y0), (x1, y1) in zip(p, p[1:] + p[:1])) != 0
+    for fr in frames:
+        for k, polys in fr.items():
+            if k is None:
+                polys['holes'] = {o: [h for h in hs if alive(h)] for o, hs in polys['holes'].items()}
+                continue
+            polys[:] = [p for p in polys if alive(p['exterior'])]
+            for p in polys:
+                p['holes'] = [h for h in p['holes'] if alive(h)]
+    return frames
+
+
 def group_rings(rings: np.ndarray, verts: np.ndarray, n: int, num_objs: int, squeeze_idx: Optional[Sequence[int]] = None,
                 roots_at_start: Optional[np.ndarray] = None) -> List[Dict]:
     """trace_label_stack's grouping, pure host code: rings [R, 8] and verts [V, 2] of n frames as
@@ -132,14 +213,15 @@ def group_rings(rings: np.ndarray, verts: np.ndarray, n: int, num_objs: int, squ
     return frames
 
 
-def frame_bytes(H: int, W: int, parents: bool = True) -> int:
-    """what trace_label_stack counts per frame of a pass: the workspace and the outputs of `trace` at default_max_edges, and the
-    roots of the components where holes get parents"""
+def frame_bytes(H: int, W: int, parents: bool = True, simplified: bool = False) -> int:
+    """what trace_label_stack counts per frame of a pass: the workspace and the outputs of `trace` at default_max_edges, the
+    roots of the components where holes get parents, and the workspace and the outputs of `simplify` where a tolerance is given"""
     M = default_max_edges(1, H, W)
     ws = int(_lib.lib().rmem_label_polygons_workspace_bytes(1, H, W, M))
     if ws == 0:
         raise RmemError(f'polygons: bad geometry (H * W at most 2^26; got {H}x{W})')
-    return ws + 16 * M + 32 + (4 * H * W if parents else 0)
+    more = int(_lib.lib().rmem_polygon_simplify_workspace_bytes(M // 4 + 1, M)) + 16 * M + 32 if simplified else 0
+    return ws + 16 * M + 32 + (4 * H * W if parents else 0) + more
 
 
 def _status_text(bits: int) -> str:
@@ -147,7 +229,8 @@ def _status_text(bits: int) -> str:
 
 
 def trace_label_stack(labels_u8: torch.Tensor, num_objs: int, connectivity: int = 8, squeeze_idx: Optional[Sequence[int]] = None,
-                      parents: bool = True, max_edges: Optional[int] = None, workspace_bytes: Optional[int] = None) -> List[Dict]:
+                      parents: bool = True, max_edges: Optional[int] = None, workspace_bytes: Optional[int] = None,
+                      tolerance: Optional[float] = None, degenerate: str = 'drop') -> List[Dict]:
     """Per frame of a uint8 device label stack [n, H, W] or [H, W]: {object id: [polygon, ...]} for the objects 1..num_objs, one
     polygon per connected piece (`connectivity`) in the order of the pieces' first pixels, an empty list for an object the frame
     does not hold.  polygon = {'exterior': int32 [k, 2], 'area2': int, 'holes': [int32 [k, 2], ...]}: rings of (x, y) pixel
@@ -162,12 +245,21 @@ def trace_label_stack(labels_u8: torch.Tensor, num_objs: int, connectivity: int 
     The stack goes in passes of as many frames as keep the workspace and outputs of one `trace` call at or below workspace_bytes
     (default: 256 MiB, or one frame's need where that is larger).  Per pass: one readback of counts, then one readback of the used
     rows.  max_edges (per pass; default: default_max_edges): when the status says ST_CAPACITY the pass is traced once more with
-    max_edges = counts[0]."""
+    max_edges = counts[0].
+    tolerance (pixels, 0..64; None: the traced rings as they are): `simplify` is launched directly behind `trace`, both count
+    vectors come back in the pass's one counts readback, the capacity retry traces and simplifies again, and the used rows that
+    come back are the simplified tables'.  'area2' stays the TRACED pixel area.  Topology is NOT preserved: simplified rings may
+    touch or cross themselves or each other.  degenerate='drop' (only with a tolerance) then removes every exterior with fewer
+    than 3 kept vertices or a zero shoelace sum together with its holes, and every such hole; 'keep' leaves everything."""
     what = 'polygons.trace_label_stack'
     K, conn = int_in(what, 'num_objs', num_objs, 1, 255), _connectivity(what, connectivity)
+    if tolerance is not None:
+        _steps(what, tolerance)
+    if degenerate not in ('drop', 'keep'):
+        raise RmemError(f'{what}: degenerate must be \'drop\' or \'keep\' (got {degenerate!r})')
     a = _frames(what, labels_u8)
     n, H, W = a.shape
-    per_frame = frame_bytes(H, W, parents)
+    per_frame = frame_bytes(H, W, parents, tolerance is not None)
     k = frames_per_pass(what, n, per_frame, workspace_bytes, 'one frame\'s need')[1]     # at least 1: the budget holds a frame
     if max_edges is not None:
         _max_edges(what, max_edges, n, H, W)
@@ -175,20 +267,31 @@ def trace_label_stack(labels_u8: torch.Tensor, num_objs: int, connectivity: int 
     for f0 in range(0, n, k):
         part = a[f0:f0 + k]
         m = part.shape[0]
-        rings, verts, counts = trace(part, K, conn, max_edges)
+        def traced(cap):
+            """trace, simplify behind it where asked, and the one readback of the counts of both"""
+            t = trace(part, K, conn, cap)
+            if tolerance is None:
+                return t, t[2].cpu().tolist(), None
+            s = simplify(*t, tolerance)
+            both = torch.cat([t[2], s[2]]).cpu().tolist()
+            return s, both[:4], both[4:]
+
+        (rings, verts, counts), c, cs = traced(max_edges)
         roots = cc_status = None
         if parents:
             from .components import label_components
             roots, cc_status = label_components(part, conn)
-        c = counts.cpu().tolist()
         if c[3] & ST_CAPACITY:
             if c[0] >= MAX_EDGES:
                 raise RmemError(f'{what}: {m} frames of {H} x {W} have 2^31 - 1 edges or more; give fewer frames a pass (workspace_bytes)')
-            rings, verts, counts = trace(part, K, conn, max(4, c[0]))
-            c = counts.cpu().tolist()
+            (rings, verts, counts), c, cs = traced(max(4, c[0]))
         if c[3]:
             raise RmemError(f'{what}: the tracer failed (status {c[3]}: {_status_text(c[3])}); this is a bug')
         R, V = c[1], c[2]
+        if cs is not None:
+            if cs[3] or cs[1] != R:
+                raise RmemError(f'{what}: the simplifier failed (status {cs[3]}, {cs[1]} of {R} rings); this is a bug')
+            V = cs[2]
         used = [rings[:R].reshape(-1), verts[:V].reshape(-1)]
         if parents:
             at = rings[:R, 0].long() * (H * W) + (rings[:R, 5] >> 2).long()
@@ -200,11 +303,15 @@ def trace_label_stack(labels_u8: torch.Tensor, num_objs: int, connectivity: int 
                 raise RmemError(f'{what}: a bounded loop of the component kernels ran out (status {int(host[-1])}); this is a bug')
             at_start = host[8 * R + 2 * V:8 * R + 2 * V + R]
         out += group_rings(host[:8 * R].reshape(R, 8), host[8 * R:8 * R + 2 * V].reshape(V, 2), m, K, squeeze_idx, at_start)
+    if tolerance is not None and degenerate == 'drop':
+        drop_degenerate(out)
     return out
 
 
-def coco_polygons(frames: List[Dict], size: Tuple[int, int], holes: str = 'rings') -> List[Dict]:
-    """evaluator.polygon_results' shaping of trace_label_stack's output (parents=True), pure host code"""
+def coco_polygons(frames: List[Dict], size: Tuple[int, int], holes: str = 'rings', simplified: bool = False) -> List[Dict]:
+    """evaluator.polygon_results' shaping of trace_label_stack's output (parents=True), pure host code.  simplified: 'area' is
+    the shoelace area of the rings the entry lists, a float (exteriors minus the listed holes under 'rings', exteriors alone under
+    'drop'); otherwise the pixel count from the traced 'area2'."""
     H, W = int(size[0]), int(size[1])
     out = []
     for fr in frames:
@@ -213,6 +320,10 @@ def coco_polygons(frames: List[Dict], size: Tuple[int, int], holes: str = 'rings
             e = {'size': [H, W], 'segmentation': [p['exterior'].reshape(-1).tolist() for p in polys]}
             if holes == 'rings':
                 e['holes'] = [h.reshape(-1).tolist() for p in polys for h in p['holes']]
+            if simplified:
+                inner = sum(_area2(h) for p in polys for h in p['holes']) if holes == 'rings' else 0     # negative: holes run the other way
+                e['area'] = (sum(_area2(p['exterior']) for p in polys) + inner) / 2.0
+            elif holes == 'rings':
                 e['area'] = sum(p['area2'] for p in polys) // 2
             else:
                 e['area'] = sum(p['area2'] - sum(_area2(h) for h in p['holes']) for p in polys) // 2
