@@ -679,6 +679,35 @@ int rmem_label_component_stats(const unsigned char* labels, const int* roots, in
 int rmem_label_clean(const unsigned char* src, unsigned char* dst, const int* roots, const int* stats, const int* table, int n, int H,
                      int W, int max_hole_area, int max_sprinkle_area, int keep_largest, void* stream);
 
+/* Exact Euclidean distance transform of uint8 label stacks and the peaks of a distance map (distance.py: label_edt, peaks,
+ * hausdorff2, hausdorff; evaluator.surface_distance, next_clicks).  Squared distances between pixel centres as int32; integers
+ * only, no float anywhere.  labels: uint8 [n][H][W], contiguous, device, may start at any byte; frames are independent; every
+ * value 0..255 is treated alike (a void label of 255 is an ordinary value).
+ *   value = -1  "other": dist2[f][y][x] = min |p - q|^2 over the pixels q of frame f with labels[q] != labels[p] -- the interior
+ *               depth of every object, and for the background the distance to the nearest object.  border = 1: the outside of the
+ *               frame counts as another value, min(y + 1, H - y, x + 1, W - x)^2 joins the minimum (what padding the frame with
+ *               one ring of a value it does not hold does); border = 0: the outside counts as nothing.
+ *   value 0..255 "to value": dist2 = min |p - q|^2 over q with labels[q] == value, 0 on the pixels of value.  border must be 0.
+ * Where no q exists (a frame of one value without border; value absent from the frame) dist2 = 2^31 - 1.  H and W are at most
+ * 16384, so every real distance is below 2^30.  rmem_label_edt writes every entry of dist2; prior contents of dist2 and of the
+ * workspace do not matter.  workspace: rmem_label_edt_workspace_bytes(n, H, W) bytes (0 for refused geometry), 4-byte aligned:
+ * the vertical distances of the column pass, 16 bits per pixel.  Two launches; the scan of the row pass is bounded by the root
+ * of the result, and a frame without any site is filled without a scan.
+ * rmem_label_edt_peaks: table int32 [n][256][2], table[f][v] = (the largest dist2 among the pixels of frame f with keys == v,
+ * the flat index y * W + x of the FIRST such pixel in raster order that attains it), (-1, -1) for a value no pixel holds.  keys:
+ * any uint8 stack [n][H][W] (the labels themselves, or the other stack of a pair), may start at any byte.  dist2 must not be
+ * negative (rmem_label_edt writes none).  Every entry of table is written.  workspace: rmem_label_edt_peaks_workspace_bytes(n)
+ * bytes (0 for n outside 1..65535), 8-byte aligned: one 64-bit key per frame and value.  Three launches.
+ * No state between calls, no host sync, integer atomics only: both are bit-reproducible and independent of scheduling.  Refused
+ * (non-zero, nothing launched): a null pointer, n outside 1..65535, non-positive H / W, H * W above 2^26, (rmem_label_edt) H or
+ * W above 16384, value outside -1..255, border other than 0 / 1 or 1 with a value, a workspace too small or misaligned. */
+long long rmem_label_edt_workspace_bytes(int n, int H, int W);   /* host only */
+int rmem_label_edt(const unsigned char* labels, int n, int H, int W, int value, int border, int* dist2, void* workspace,
+                   long long workspace_bytes, void* stream);
+long long rmem_label_edt_peaks_workspace_bytes(int n);   /* host only */
+int rmem_label_edt_peaks(const int* dist2, const unsigned char* keys, int n, int H, int W, int* table, void* workspace,
+                         long long workspace_bytes, void* stream);
+
 /* Label stacks traced into polygon rings: the outer contours and the holes of every object of every frame, the last way a run's
  * labels leave the device (polygons.py: trace, trace_label_stack; evaluator.polygon_results) -- what CVAT / Labelme tracks and
  * COCO `segmentation` lists are made of, and what labels.cpu() plus a sequential border follower per frame and object computes.

@@ -30,7 +30,10 @@ Mirrors what networks/managers/evaluator.py:330-568 does for one sequence, witho
     identity swap from a lost object -- rmem_label_pair_census, pairs.py, relabel_to_match, identity_report;
   * the boundary counts of every such pair come from the device as well, and with them the DAVIS unsupervised protocol (proposals
     matched to annotated objects on the mean of J and F) and clip scoring for up to 255 objects -- rmem_pair_boundary_counts,
-    pairs.pair_jf, score_unsupervised_clip, score_clip_objects.
+    pairs.pair_jf, score_unsupervised_clip, score_clip_objects;
+  * the distance of every pixel to the nearest pixel of another kind is an exact integer transform on the device, and with it
+    the Hausdorff distance of every object and the next click of an interactive protocol -- rmem_label_edt,
+    rmem_label_edt_peaks, distance.py, surface_distance, next_clicks.
 """
 from __future__ import annotations
 
@@ -403,6 +406,47 @@ def object_fragments(labels_u8: torch.Tensor, num_objs: int, connectivity: int =
     (components.object_fragments).  The current stream, no host sync."""
     from .components import object_fragments as fragments
     return fragments(labels_u8, num_objs, connectivity)
+
+
+def surface_distance(pred_u8: torch.Tensor, gt_u8: torch.Tensor, num_objs: int) -> np.ndarray:
+    """float64 numpy [n, num_objs]: the Hausdorff distance in pixels between the predicted and the annotated mask of object
+    1..num_objs on every frame (distance.hausdorff): 0 where both are empty, inf where exactly one is.  The third number reported
+    for a segmentation next to J and F, and the one a far-away false blob shows in.  A void label is an ordinary value here.  Exact
+    integer distance transforms on the device, one readback."""
+    from .distance import hausdorff
+    return hausdorff(pred_u8, gt_u8, num_objs)
+
+
+def next_clicks(pred_u8: torch.Tensor, gt_u8: torch.Tensor, num_objs: int) -> np.ndarray:
+    """int32 numpy [n, num_objs, 4]: (y, x, positive, d2) of the next corrective click of an interactive protocol for object
+    1..num_objs on every frame; (-1, -1, 0, 0) where the object has no error on the frame.  The DEEPEST-POINT rule: per object the
+    error stack E is 0 where pred and gt agree on "is object i", 1 on a false negative (gt == i, pred != i) and 2 on a false
+    positive; d2 = distance.label_edt(E, border=True) is every error pixel's squared distance to the nearest pixel of another
+    kind, the outside of the frame included; the click goes to the peak of the kind with the larger d2 (distance.peaks: the first
+    pixel in raster order among equals), positive = 1 for a false-negative peak, and to the false positive on equal depth.
+    RITM-style simulators vary this rule (the peak of an inner mask at half the maximum, a random choice among equals); this is
+    the plain form and the steps above are its specification.  A void label is an ordinary value.  E is built with torch ops on
+    the device; one transform and one peaks call per object, one readback in all."""
+    from .distance import label_edt, peaks
+    what = 'evaluator.next_clicks'
+    K = _labels.int_in(what, 'num_objs', num_objs, 1, 255)
+    pred, gt = _labels.stack_pair(what, pred_u8, gt_u8, ('pred', 'gt'))
+    n, H, W = pred.shape
+    tops = torch.empty(n, K, 2, 2, dtype=torch.int32, device=pred.device)
+    d2 = torch.empty(n, H, W, dtype=torch.int32, device=pred.device)
+    for i in range(1, K + 1):
+        p, g = pred == i, gt == i
+        E = (g & ~p).to(torch.uint8) + (p & ~g).to(torch.uint8) * 2
+        label_edt(E, border=True, out=d2)
+        tops[:, i - 1] = peaks(d2, E)[:, 1:3]
+    t = tops.cpu().numpy().astype(np.int64)                           # [n, K, kind (fn, fp), (d2, index)]
+    fn, fp = t[:, :, 0], t[:, :, 1]
+    positive = fn[..., 0] > fp[..., 0]
+    best = np.where(positive[..., None], fn, fp)
+    none = best[..., 0] < 0
+    out = np.stack([best[..., 1] // W, best[..., 1] % W, positive.astype(np.int64), best[..., 0]], axis=-1)
+    out[none] = (-1, -1, 0, 0)
+    return out.astype(np.int32)
 
 
 def relabel_to_match(pred_u8: torch.Tensor, gt_u8: torch.Tensor, num_pred: int, num_gt: int):
