@@ -708,6 +708,40 @@ long long rmem_label_edt_peaks_workspace_bytes(int n);   /* host only */
 int rmem_label_edt_peaks(const int* dist2, const unsigned char* keys, int n, int H, int W, int* table, void* workspace,
                          long long workspace_bytes, void* stream);
 
+/* Surface distances of two label stacks: the surfaces, a distance transform evaluated on chosen pixels only, and the census that
+ * reduces every object's surface-to-surface distances to a few integers (surface.py: label_surface, edt_at, surface_census,
+ * surface_metrics; evaluator.surface_metrics).  Integers only, integer atomics only: bit-reproducible.  All stacks [n][H][W],
+ * contiguous, device; uint8 stacks may start at any byte.  SENTINEL = 2^31 - 1.
+ * rmem_label_surface: surface[p] = labels[p] where a 4-neighbour of p holds another value or lies outside the frame, else 0 (for
+ * a value v: mask & ~binary_erosion(mask, cross, border_value=0), mask = labels == v).  One launch, every byte of surface is
+ * written, nothing outside the frame is read.  A void label of 255 is an ordinary value.
+ * rmem_label_edt_at: rmem_label_edt's to-value transform at the pixels with keys[p] == key alone: there samples[p] = min |p - q|^2
+ * over q with labels[q] == value, SENTINEL where the frame holds none; every other entry of samples is left untouched.  value and
+ * key in 0..255.  workspace: rmem_label_edt_workspace_bytes(n, H, W) bytes, 4-byte aligned.  Two launches: the column pass, and a
+ * row pass that leaves a row without a key pixel before it reads anything else.
+ * rmem_surface_census: keys_a / keys_b are surface stacks, samples_a / samples_b int32 stacks read only where the key is in
+ * 1..num_objs: samples_a[p], key i, is the squared distance of p on the surface of object i of a to that surface of b (what
+ * rmem_label_edt_at(keys_b, keys_a, .., i, i, samples_a, ..) writes), samples_b the mirror image.  Per frame f and object i the sets
+ * 0 (a -> b), 1 (b -> a) and 2 (both pooled) of samples; a set holds sentinels only (the other surface is empty) or none.
+ * table int64 [n][num_objs][3][9] = (count m, sum_fix = sum of floor(sqrt(d2 * 2^32)), max, lo, hi, within[0..3]): lo and hi are
+ * the samples of rank r_lo = (m - 1) * q / 10000 and r_hi = min(r_lo + 1, m - 1) in ascending order (q in hundredths of a percent:
+ * with frac = ((m - 1) * q % 10000) / 10000, sqrt(lo) + frac * (sqrt(hi) - sqrt(lo)) is the linear percentile of the distances);
+ * within[t] counts the samples with d2 <= tol2[t], t < num_tol <= 4, 0 for unused t; tol2: HOST array, entries in 0..2^30 - 1.  An
+ * empty set: (0, 0, -1, -1, -1, 0, 0, 0, 0); sentinels only: (m, 0, SENTINEL, SENTINEL, SENTINEL, 0, 0, 0, 0).  Every entry of
+ * table is written.  workspace: rmem_surface_census_workspace_bytes(n, num_objs) bytes (0 for n or num_objs out of range), 8-byte
+ * aligned; prior contents do not matter.  A memset and eight launches: an accumulate walk, a radix select of lo over three
+ * 10-bit digits (a histogram walk and a pick each), an integer-min walk for hi, the table.  No state between calls, no host sync.
+ * Refused (non-zero, nothing launched): a null pointer, n outside 1..65535, non-positive H / W, H * W above 2^26, H or W above
+ * 16384, value / key outside 0..255, num_objs outside 1..255, num_tol outside 0..4, q outside 0..10000, a tol2 entry outside
+ * 0..2^30 - 1, a workspace too small or misaligned. */
+int rmem_label_surface(const unsigned char* labels, int n, int H, int W, unsigned char* surface, void* stream);
+int rmem_label_edt_at(const unsigned char* labels, const unsigned char* keys, int n, int H, int W, int value, int key, int* samples,
+                      void* workspace, long long workspace_bytes, void* stream);
+long long rmem_surface_census_workspace_bytes(int n, int num_objs);   /* host only */
+int rmem_surface_census(const int* samples_a, const unsigned char* keys_a, const int* samples_b, const unsigned char* keys_b, int n,
+                        int H, int W, int num_objs, const int* tol2, int num_tol, int q, long long* table, void* workspace,
+                        long long workspace_bytes, void* stream);
+
 /* Label stacks traced into polygon rings: the outer contours and the holes of every object of every frame, the last way a run's
  * labels leave the device (polygons.py: trace, trace_label_stack; evaluator.polygon_results) -- what CVAT / Labelme tracks and
  * COCO `segmentation` lists are made of, and what labels.cpu() plus a sequential border follower per frame and object computes.

@@ -188,6 +188,10 @@ SIGNATURES = {
     'rmem_label_edt': (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp, _ll, _vp]),
     'rmem_label_edt_peaks_workspace_bytes': (_ll, [_i]),
     'rmem_label_edt_peaks': (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _ll, _vp]),
+    'rmem_label_surface': (_i, [_vp, _i, _i, _i, _vp, _vp]),
+    'rmem_label_edt_at': (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _ll, _vp]),
+    'rmem_surface_census_workspace_bytes': (_ll, [_i, _i]),
+    'rmem_surface_census': (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, C.POINTER(_i), _i, _i, _vp, _vp, _ll, _vp]),
     'rmem_label_polygons_unit': (_i, []),
     'rmem_label_polygons_workspace_bytes': (C.c_size_t, [_i, _i, _i, _i]),
     'rmem_label_polygons': (_i, [_vp, _i, _i, _i, _i, _i, _i, _vp, C.c_size_t, _vp, _vp, _vp, _vp]),

@@ -1,6 +1,6 @@
 // Exact Euclidean distance transform of uint8 label stacks and the peaks of a distance map (include/rmem.h: rmem_label_edt,
-// rmem_label_edt_peaks; distance.py).  Squared distances between pixel centres as int32, integers only, no float anywhere.
-// Element-type agnostic (uint8 in, int32 out): built once.
+// rmem_label_edt_at, rmem_label_edt_peaks; distance.py, surface.py).  Squared distances between pixel centres as int32, integers
+// only, no float anywhere.  Element-type agnostic (uint8 in, int32 out): built once.
 //
 // A SITE of pixel p is what p's distance is measured to: in the "other" mode (value = -1) a pixel of the frame that holds another
 // value than p, and with `border` the first pixel outside the frame; in the "to value" mode the pixels that hold `value`.
@@ -20,6 +20,9 @@
 //                step, so columns without a site and flat stretches of g cost a look per 32 pixels.  A row that holds no site at
 //                all (one value, every g none; known from a workgroup-wide OR while the row is loaded) is filled with the
 //                sentinel without a scan.
+//   k_edt_rows_at
+//                The to-value row pass at the pixels with keys == key alone (rmem_label_edt_at): a row without a key
+//                pixel leaves before it reads g, in the others a thread per pixel skips the pixels without the key.
 //   k_peaks_init, k_peaks, k_peaks_table
 //                keys[f][v] = max over the pixels of frame f with key v of (d2 << 32) | (2^32 - 1 - flat index): the largest
 //                distance, and among equals the first pixel in raster order.  A table per workgroup in LDS (64-bit integer max),
@@ -161,6 +164,71 @@ __global__ __launch_bounds__(kThreads) void k_edt_rows(const unsigned char* __re
   }
 }
 
+// ------------------------------------------------------------------------------------------------------ sampled row pass
+// The to-value row pass at the pixels with keys == key alone (rmem_label_edt_at).  One workgroup per row.  It reads the row's keys
+// first and leaves at once when none is the key (a workgroup-wide OR): such a row never reads g.  Otherwise the row's g and the
+// segment summaries go to LDS as in k_edt_rows (33 KB at W = 16384), and a thread takes pixels x = t, t + 256, ... and skips those
+// without the key.  Labels are not needed: a site is where g == 0.  Compacting the key pixels into a list first was measured and
+// gained nothing on sparse keys.
+__global__ __launch_bounds__(kThreads) void k_edt_rows_at(const unsigned short* __restrict__ g, const unsigned char* __restrict__ keys,
+                                                          int H, int W, int wpad, int key, int* __restrict__ samples) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  const int nseg = (W + kSeg - 1) / kSeg;
+  unsigned short* sg = (unsigned short*)smem;      // [wpad] the row's g
+  unsigned short* smin = sg + wpad;                // [nseg] the smallest g of a segment of kSeg pixels
+  const int t = threadIdx.x;
+  const size_t base = ((size_t)blockIdx.y * H + blockIdx.x) * W;
+  int has = 0;
+  for (int x = t; x < W; x += kThreads) has |= keys[base + x] == key;
+  if (!__syncthreads_or(has)) return;              // the same in every thread
+  int any = 0;
+  for (int x = t; x < W; x += kThreads) {
+    const int gg = g[base + x];
+    sg[x] = (unsigned short)gg;
+    any |= gg != kNone;
+  }
+  any = __syncthreads_or(any);                     // the barrier too
+  for (int k = t; k < nseg; k += kThreads) {
+    const int x0 = k * kSeg, x1 = min(x0 + kSeg, W);
+    int mn = kNone;
+    for (int x = x0; x < x1; ++x) mn = min(mn, (int)sg[x]);
+    smin[k] = (unsigned short)mn;
+  }
+  __syncthreads();
+  for (int x = t; x < W; x += kThreads) {
+    if (keys[base + x] != key) continue;
+    const int g0 = sg[x];
+    int best = g0 == kNone ? kSentinel : g0 * g0;
+    // k_edt_rows' scan in its to-value form: no labels, a rest is skipped where dx^2 + (its smallest g)^2 cannot win
+    int ql = x - 1, qr = x + 1;
+    bool left = any && ql >= 0, right = any && qr < W;               // no site in the frame: the sentinel without a scan
+    while (left || right) {
+      if (left) {
+        const int dx = x - ql, k = ql / kSeg, mn = smin[k];
+        if (dx * dx >= best) {
+          left = false;
+        } else {
+          if (mn != kNone && dx * dx + mn * mn < best) left = scan_piece(sg, nullptr, x, ql, k * kSeg, -1, false, 0, best);
+          ql = k * kSeg - 1;
+          left = left && ql >= 0;
+        }
+      }
+      if (right) {
+        const int dx = qr - x, k = qr / kSeg, mn = smin[k];
+        if (dx * dx >= best) {
+          right = false;
+        } else {
+          const int end = min(k * kSeg + kSeg, W) - 1;
+          if (mn != kNone && dx * dx + mn * mn < best) right = scan_piece(sg, nullptr, x, qr, end, 1, false, 0, best);
+          qr = end + 1;
+          right = right && qr < W;
+        }
+      }
+    }
+    samples[base + x] = best;
+  }
+}
+
 // ------------------------------------------------------------------------------------------------------------------- peaks
 __global__ __launch_bounds__(kThreads) void k_peaks_init(unsigned long long* __restrict__ keys) {
   keys[(size_t)blockIdx.x * 256 + threadIdx.x] = 0ull;
@@ -217,6 +285,25 @@ extern "C" int rmem_label_edt(const unsigned char* labels, int n, int H, int W, 
   hipLaunchKernelGGL(k_edt_rows, dim3(H, n), dim3(kThreads), (size_t)wpad * 2 + (size_t)((W + kSeg - 1) / kSeg) * 4 + W, (hipStream_t)stream, labels, g, H, W, wpad, value, border,
                      dist2);
   return rmem_check_launch("rmem_label_edt");
+}
+
+extern "C" int rmem_label_edt_at(const unsigned char* labels, const unsigned char* keys, int n, int H, int W, int value, int key, int* samples,
+                                 void* workspace, long long workspace_bytes, void* stream) {
+  RMEM_REQUIRE(labels && keys && samples && workspace, "rmem_label_edt_at: null pointer (labels, keys, samples and workspace are required)");
+  RMEM_REQUIRE(n >= 1 && n <= kMaxFrames, "rmem_label_edt_at: n must be in 1..65535");
+  RMEM_REQUIRE(stack_geometry_ok(n, H, W), "rmem_label_edt_at: H and W must be positive, H * W at most 2^26");
+  RMEM_REQUIRE(H <= kMaxSide && W <= kMaxSide, "rmem_label_edt_at: H and W must be at most 16384");
+  RMEM_REQUIRE(value >= 0 && value <= 255, "rmem_label_edt_at: value must be in 0..255");
+  RMEM_REQUIRE(key >= 0 && key <= 255, "rmem_label_edt_at: key must be in 0..255");
+  RMEM_REQUIRE(workspace_bytes >= rmem_label_edt_workspace_bytes(n, H, W), "rmem_label_edt_at: workspace too small (rmem_label_edt_workspace_bytes)");
+  RMEM_REQUIRE(((uintptr_t)workspace & 3u) == 0, "rmem_label_edt_at: workspace must be 4-byte aligned");
+  unsigned short* g = (unsigned short*)workspace;
+  const int wpad = (W + 7) & ~7;
+  hipLaunchKernelGGL(k_edt_cols, dim3((W + kColThreads - 1) / kColThreads, n), dim3(kColThreads), 0, (hipStream_t)stream, labels, H, W, value,
+                     0, g);
+  hipLaunchKernelGGL(k_edt_rows_at, dim3(H, n), dim3(kThreads), (size_t)wpad * 2 + (size_t)((W + kSeg - 1) / kSeg) * 2, (hipStream_t)stream, g,
+                     keys, H, W, wpad, key, samples);
+  return rmem_check_launch("rmem_label_edt_at");
 }
 
 extern "C" long long rmem_label_edt_peaks_workspace_bytes(int n) {

@@ -33,7 +33,10 @@ Mirrors what networks/managers/evaluator.py:330-568 does for one sequence, witho
     pairs.pair_jf, score_unsupervised_clip, score_clip_objects;
   * the distance of every pixel to the nearest pixel of another kind is an exact integer transform on the device, and with it
     the Hausdorff distance of every object and the next click of an interactive protocol -- rmem_label_edt,
-    rmem_label_edt_peaks, distance.py, surface_distance, next_clicks.
+    rmem_label_edt_peaks, distance.py, surface_distance, next_clicks;
+  * the robust surface distances (95th-percentile Hausdorff, average symmetric surface distance, surface Dice at a tolerance) come
+    from a census of surface-to-surface distances on the device -- rmem_label_surface, rmem_label_edt_at, rmem_surface_census,
+    surface.py, surface_metrics.
 """
 from __future__ import annotations
 
@@ -415,6 +418,17 @@ def surface_distance(pred_u8: torch.Tensor, gt_u8: torch.Tensor, num_objs: int) 
     integer distance transforms on the device, one readback."""
     from .distance import hausdorff
     return hausdorff(pred_u8, gt_u8, num_objs)
+
+
+def surface_metrics(pred_u8: torch.Tensor, gt_u8: torch.Tensor, num_objs: int, tolerances: Sequence[float] = (1.0, 2.0),
+                    percentile: float = 95.0, pooled: bool = True) -> Dict[str, np.ndarray]:
+    """dict of float64 numpy arrays [n, num_objs] ('nsd': [n, num_objs, len(tolerances)]): the robust companions of
+    surface_distance, measured surface to surface between the predicted and the annotated mask of object 1..num_objs on every frame
+    (surface.surface_metrics): 'hd' the Hausdorff distance of the two surfaces, 'hd95' its 95th-percentile form (one stray pixel
+    does not decide it), 'assd' the average symmetric surface distance, 'nsd' the surface Dice at each tolerance in pixels.  Both
+    surfaces empty: distances 0, nsd 1; exactly one: inf and 0.  Integer census on the device, one readback."""
+    from .surface import surface_metrics as _metrics
+    return _metrics(pred_u8, gt_u8, num_objs, tolerances, percentile, pooled)
 
 
 def next_clicks(pred_u8: torch.Tensor, gt_u8: torch.Tensor, num_objs: int) -> np.ndarray:
