@@ -742,6 +742,45 @@ int rmem_surface_census(const int* samples_a, const unsigned char* keys_a, const
                         int H, int W, int num_objs, const int* tol2, int num_tol, int q, long long* table, void* workspace,
                         long long workspace_bytes, void* stream);
 
+/* Label stacks thinned to skeletons (Guo and Hall 1989, algorithm A1; the rule of bwmorph's 'thin') and the list of a stack's
+ * non-zero pixels (skeleton.py: thin, pixels, tile, table; evaluator.next_scribbles).  Bytes and integers only: bit-identical to a
+ * host restatement.  labels: uint8 [n][H][W], contiguous, device, may start at any byte; frames are independent.
+ * The rule.  Value 0 is background and never changes.  For a pixel p of value L != 0 the neighbour bit x_i is 1 iff that neighbour
+ * lies inside the frame and holds L; x1..x8 = E, NE, N, NW, W, SW, S, SE (y grows downward), x9 = x1.  Pixels of other values count
+ * as background for p: every value is thinned as if it were alone in the frame, a void label of 255 is an ordinary value.  p is
+ * deleted (set to 0) in a sub-iteration iff  X_H = sum_{i=1..4} [x_{2i-1} = 0 and (x_{2i} = 1 or x_{2i+1} = 1)] = 1,
+ * 2 <= min(n1, n2) <= 3 with n1 = sum_{k=1..4} (x_{2k-1} | x_{2k}), n2 = sum_{k=1..4} (x_{2k} | x_{2k+1}), and in an even
+ * sub-iteration (x2 | x3 | !x8) & x1 = 0, in an odd one (x6 | x7 | !x4) & x5 = 0.  A sub-iteration is synchronous: every decision
+ * is taken from the state before it.  With mask bit k = x_{k+1} each rule is a 256-entry table of 37 set entries.
+ * rmem_label_thin applies the sub-iterations first, first + 1, .., first + count - 1 (sub-iteration s uses table s & 1) to labels
+ * and writes every byte of out; out may be the same pointer as labels (otherwise labels is read only and the two must not
+ * overlap).  lost int32 [n][2], every entry written: lost[f][0] = the pixels frame f lost during the call, lost[f][1] = those lost
+ * in the call's last two sub-iterations (in the only one if count = 1): with count >= 2, lost[f][1] == 0 means that frame f is at
+ * its fixed point.  workspace: rmem_label_thin_workspace_bytes(n, H, W) bytes (0 for refused geometry), 4-byte aligned, prior
+ * contents do not matter: a second stack and two bytes per tile and frame.  A memset and ceil(count / k) launches of up to k
+ * sub-iterations each on tiles of th x tw pixels with a halo of k (rmem_label_thin_tile), one device copy more where out ==
+ * labels and that number is odd; a tile none of whose 3 x 3 tiles changed in the round before is skipped (RMEM_THIN_SKIP=0 in the
+ * environment: never, for A/B runs).  rmem_label_thin_table: the table of a parity as 256 bits, bit m of byte m / 8 = mask m is
+ * deleted; host only, the constant the kernels use.
+ * rmem_label_pixels_count / _write: the non-zero pixels of a uint8 stack as a list in raster order, frame by frame.  count writes
+ * totals int32 [n] = the non-zero pixels of every frame and leaves offsets in the workspace; write, on the same stack and workspace,
+ * writes row i of entries int32 [total][4] = (frame, y, x, value) and, with samples (an int32 stack [n][H][W]; NULL with sampled
+ * NULL: none), sampled[i] = samples at that pixel.  Rows at or beyond `capacity` are not written.  workspace:
+ * rmem_label_pixels_workspace_bytes(n, H, W) bytes, 8-byte aligned.  Three launches and one.
+ * No state between calls, no host sync, integer atomics only.  Refused (non-zero, nothing launched): a null pointer, n outside
+ * 1..65535, non-positive H / W, H * W above 2^26, first < 0, count < 1, first + count above 2^31 - 1, parity other than 0 / 1,
+ * capacity < 0, samples without sampled or the reverse, a workspace too small or misaligned. */
+int rmem_label_thin_tile(int* th, int* tw, int* k);   /* host only */
+int rmem_label_thin_table(int parity, unsigned char* out /* [32] */);   /* host only */
+long long rmem_label_thin_workspace_bytes(int n, int H, int W);   /* host only */
+int rmem_label_thin(const unsigned char* labels, int n, int H, int W, int first, int count, unsigned char* out, int* lost,
+                    void* workspace, long long workspace_bytes, void* stream);
+long long rmem_label_pixels_workspace_bytes(int n, int H, int W);   /* host only */
+int rmem_label_pixels_count(const unsigned char* stack, int n, int H, int W, int* totals, void* workspace, long long workspace_bytes,
+                            void* stream);
+int rmem_label_pixels_write(const unsigned char* stack, const int* samples, int n, int H, int W, long long capacity, int* entries,
+                            int* sampled, const void* workspace, long long workspace_bytes, void* stream);
+
 /* Label stacks traced into polygon rings: the outer contours and the holes of every object of every frame, the last way a run's
  * labels leave the device (polygons.py: trace, trace_label_stack; evaluator.polygon_results) -- what CVAT / Labelme tracks and
  * COCO `segmentation` lists are made of, and what labels.cpu() plus a sequential border follower per frame and object computes.

@@ -192,6 +192,13 @@ SIGNATURES = {
     'rmem_label_edt_at': (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _ll, _vp]),
     'rmem_surface_census_workspace_bytes': (_ll, [_i, _i]),
     'rmem_surface_census': (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, C.POINTER(_i), _i, _i, _vp, _vp, _ll, _vp]),
+    'rmem_label_thin_tile': (_i, [C.POINTER(_i), C.POINTER(_i), C.POINTER(_i)]),
+    'rmem_label_thin_table': (_i, [_i, _vp]),
+    'rmem_label_thin_workspace_bytes': (_ll, [_i, _i, _i]),
+    'rmem_label_thin': (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _ll, _vp]),
+    'rmem_label_pixels_workspace_bytes': (_ll, [_i, _i, _i]),
+    'rmem_label_pixels_count': (_i, [_vp, _i, _i, _i, _vp, _vp, _ll, _vp]),
+    'rmem_label_pixels_write': (_i, [_vp, _vp, _i, _i, _i, _ll, _vp, _vp, _vp, _ll, _vp]),
     'rmem_label_polygons_unit': (_i, []),
     'rmem_label_polygons_workspace_bytes': (C.c_size_t, [_i, _i, _i, _i]),
     'rmem_label_polygons': (_i, [_vp, _i, _i, _i, _i, _i, _i, _vp, C.c_size_t, _vp, _vp, _vp, _vp]),

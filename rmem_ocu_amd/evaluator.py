@@ -36,7 +36,10 @@ Mirrors what networks/managers/evaluator.py:330-568 does for one sequence, witho
     rmem_label_edt_peaks, distance.py, surface_distance, next_clicks;
   * the robust surface distances (95th-percentile Hausdorff, average symmetric surface distance, surface Dice at a tolerance) come
     from a census of surface-to-surface distances on the device -- rmem_label_surface, rmem_label_edt_at, rmem_surface_census,
-    surface.py, surface_metrics.
+    surface.py, surface_metrics;
+  * the centre line of every object is a thinning on the device (Guo and Hall's rule, bit-identical to a host restatement), and
+    with it the scribble of an interactive protocol: the longest path through the skeleton of the largest error --
+    rmem_label_thin, rmem_label_pixels_count / _write, skeleton.py, next_scribbles.
 """
 from __future__ import annotations
 
@@ -461,6 +464,50 @@ def next_clicks(pred_u8: torch.Tensor, gt_u8: torch.Tensor, num_objs: int) -> np
     out = np.stack([best[..., 1] // W, best[..., 1] % W, positive.astype(np.int64), best[..., 0]], axis=-1)
     out[none] = (-1, -1, 0, 0)
     return out.astype(np.int32)
+
+
+def next_scribbles(pred_u8: torch.Tensor, gt_u8: torch.Tensor, num_objs: int, min_depth2: int = 4) -> List[Dict[int, dict]]:
+    """The scribble twin of next_clicks: per frame {object id: {'positive': bool, 'path': int32 numpy [k, 2] of (y, x), 'depth2':
+    int}} for the objects 1..num_objs that get a corrective scribble; an object without one is absent.  All objects are handled in
+    TWO stacks: FN = gt where pred != gt, else 0 (the false negatives of object v carry value v) and FP = pred where pred != gt,
+    else 0, values above num_objs zeroed in both.  Per stack: d2 = distance.label_edt(stack, border=True), skeleton.thin,
+    skeleton.pixels(skeleton, samples=d2), then one readback of the lists.  Per frame and object the kind whose deepest skeleton
+    pixel has the larger d2 is taken, the false positive on equal depth (as next_clicks does); below min_depth2 there is no
+    scribble; otherwise the 8-connected skeleton component that holds the deepest pixel (the first in raster order among equals)
+    goes through skeleton.longest_path.  positive = True for a false negative.  The DAVIS interactive robot's own choices (an
+    opening first, Bezier smoothing, a sampling of the path) are not reproduced; these steps are the specification.  A void label
+    is an ordinary value."""
+    from .distance import label_edt
+    from .skeleton import component, longest_path, pixels, thin
+    what = 'evaluator.next_scribbles'
+    K = _labels.int_in(what, 'num_objs', num_objs, 1, 255)
+    D = _labels.int_in(what, 'min_depth2', min_depth2, 0, 2 ** 31 - 1)
+    pred, gt = _labels.stack_pair(what, pred_u8, gt_u8, ('pred', 'gt'))
+    n = pred.shape[0]
+    differ = pred != gt
+    lists = []
+    for src in (gt, pred):                                            # false negatives, false positives
+        stack = torch.where(differ & (src <= K), src, torch.zeros_like(src))
+        e, _, s = pixels(thin(stack), samples=label_edt(stack, border=True))
+        lists.append((e, s))
+    lists = [(e.cpu().numpy(), s.cpu().numpy()) for e, s in lists]
+    out: List[Dict[int, dict]] = [{} for _ in range(n)]
+    best: Dict[Tuple[int, int], tuple] = {}
+    for positive, (e, s) in ((True, lists[0]), (False, lists[1])):
+        if e.shape[0] == 0:
+            continue
+        key = e[:, 0].astype(np.int64) * 256 + e[:, 3]
+        order = np.argsort(key, kind='stable')                       # raster order kept inside every (frame, value)
+        cuts = np.nonzero(np.diff(key[order]))[0] + 1
+        for rows in np.split(order, cuts):
+            k = int(np.argmax(s[rows]))                               # the first in raster order among equals
+            depth, fv = int(s[rows[k]]), (int(e[rows[0], 0]), int(e[rows[0], 3]))
+            if fv not in best or depth >= best[fv][0]:                # the false positive on equal depth
+                best[fv] = (depth, positive, e[rows][:, 1:3], k)
+    for (f, v), (depth, positive, yx, k) in sorted(best.items()):
+        if depth >= D:
+            out[f][v] = {'positive': positive, 'path': longest_path(yx[component(yx, k)]), 'depth2': depth}
+    return out
 
 
 def relabel_to_match(pred_u8: torch.Tensor, gt_u8: torch.Tensor, num_pred: int, num_gt: int):
