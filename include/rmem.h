@@ -708,6 +708,31 @@ long long rmem_label_edt_peaks_workspace_bytes(int n);   /* host only */
 int rmem_label_edt_peaks(const int* dist2, const unsigned char* keys, int n, int H, int W, int* table, void* workspace,
                          long long workspace_bytes, void* stream);
 
+/* Nearest-site feature transform of uint8 label stacks: which pixel the nearest site is, and the label there (distance.py:
+ * nearest, grow; evaluator.expand_masks, fill_void, labels_from_seeds).  Integers only, no atomics: bit-reproducible and
+ * independent of scheduling.  labels: uint8 [n][H][W], contiguous, device, may start at any byte; frames are independent.
+ * site_bits, fill_bits: HOST arrays of 256 bits read during the call, bit (v & 31) of word v >> 5 = value v is in the set;
+ * fill_bits NULL: every value.  A pixel is a SITE if its value is in site_bits; an empty set is legal (nothing has a site).
+ * max_d2: -1 (no limit) or 0..2^30: a site farther than max_d2 (squared) does not count, d2 == max_d2 still does.
+ * Per pixel p of frame f, each output int32 / uint8 [n][H][W] and each may be NULL (not all three):
+ *   index[p]  the flat index y * W + x, within the frame, of the site nearest to p by squared Euclidean distance between pixel
+ *             centres; AMONG EQUALLY NEAR SITES THE ONE WITH THE SMALLEST FLAT INDEX (the first in raster order); -1 where the
+ *             frame holds no site within the limit.  A site maps to itself.
+ *   dist2[p]  that squared distance, 2^31 - 1 where index is -1.
+ *   taken[p]  labels[f][index[p]] if labels[p] is in fill_bits and index[p] >= 0, else labels[p].  taken must not overlap labels.
+ * Every entry of every non-NULL output is written; prior contents of the outputs and of the workspace do not matter.  workspace:
+ * rmem_label_nearest_workspace_bytes(n, H, W) bytes (0 for refused geometry), 4-byte aligned: the signed vertical offset to the
+ * nearest site of every pixel's own column, 16 bits per pixel.  Two launches, no host sync, no state between calls: a column pass
+ * in which the site above wins a tie against the site below, and a row pass that takes the minimum of (d2, index) over the
+ * columns; its scan is bounded by the root of the result or of max_d2.  With index and dist2 NULL, pixels outside fill_bits are
+ * copied without a scan.  Refused (non-zero, nothing launched): null labels, site_bits or workspace, all three outputs NULL,
+ * taken == labels, n outside 1..65535, non-positive H / W, H * W above 2^26, H or W above 16384, max_d2 outside -1..2^30, a
+ * workspace too small or misaligned. */
+long long rmem_label_nearest_workspace_bytes(int n, int H, int W);   /* host only */
+int rmem_label_nearest(const unsigned char* labels, int n, int H, int W, const unsigned int site_bits[8],
+                       const unsigned int fill_bits[8], int max_d2, int* index, int* dist2, unsigned char* taken, void* workspace,
+                       long long workspace_bytes, void* stream);
+
 /* Surface distances of two label stacks: the surfaces, a distance transform evaluated on chosen pixels only, and the census that
  * reduces every object's surface-to-surface distances to a few integers (surface.py: label_surface, edt_at, surface_census,
  * surface_metrics; evaluator.surface_metrics).  Integers only, integer atomics only: bit-reproducible.  All stacks [n][H][W],

@@ -188,6 +188,8 @@ SIGNATURES = {
     'rmem_label_edt': (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp, _ll, _vp]),
     'rmem_label_edt_peaks_workspace_bytes': (_ll, [_i]),
     'rmem_label_edt_peaks': (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _ll, _vp]),
+    'rmem_label_nearest_workspace_bytes': (_ll, [_i, _i, _i]),
+    'rmem_label_nearest': (_i, [_vp, _i, _i, _i, C.POINTER(C.c_uint), C.POINTER(C.c_uint), _i, _vp, _vp, _vp, _vp, _ll, _vp]),
     'rmem_label_surface': (_i, [_vp, _i, _i, _i, _vp, _vp]),
     'rmem_label_edt_at': (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _ll, _vp]),
     'rmem_surface_census_workspace_bytes': (_ll, [_i, _i]),

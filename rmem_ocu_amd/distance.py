@@ -1,23 +1,28 @@
 """Exact Euclidean distance transform of label stacks on the device, and what is built on it: the peaks of a distance map per
-key value, and the Hausdorff distance of every object of two stacks (include/rmem.h: rmem_label_edt, rmem_label_edt_peaks).
+key value, and the Hausdorff distance of every object of two stacks (include/rmem.h: rmem_label_edt, rmem_label_edt_peaks); and
+the nearest-site feature transform, which says WHICH pixel the nearest site is and reads the label there (rmem_label_nearest:
+nearest, grow).
 
 All distances are SQUARED distances between pixel centres as int32: exact, no float anywhere on the device.  2^31 - 1 (SENTINEL)
 stands where there is nothing to measure a distance to.  Everything runs on the current stream; the stacks never leave the device.
 """
 from __future__ import annotations
 
-from typing import Optional
+import ctypes as C
+import math
+from typing import Iterable, Optional, Tuple
 
 import numpy as np
 import torch
 
 from . import _lib
 from ._codec import workspace
-from ._labels import frames_per_pass, int_in, stack as _frames, stack_pair
+from ._labels import frames_per_pass, int_in, is_int, stack as _frames, stack_pair
 from ._lib import RmemError
 
 SENTINEL = 2 ** 31 - 1
-MAX_SIDE = 16384                             # csrc/label_edt.hip: kMaxSide
+MAX_SIDE = 16384                             # csrc/label_edt.hip, csrc/label_nearest.hip: kMaxSide
+MAX_D2 = 2 ** 30                             # csrc/label_nearest.hip: kMaxD2, above every real squared distance
 
 
 def _geometry(what: str, a: torch.Tensor):
@@ -140,3 +145,103 @@ def hausdorff(a_u8: torch.Tensor, b_u8: torch.Tensor, num_objs: int) -> np.ndarr
     square root of hausdorff2, inf where exactly one of the two sets is empty, 0 where both are.  One readback."""
     h2 = hausdorff2(a_u8, b_u8, num_objs).cpu().numpy()
     return np.where(h2 == SENTINEL, np.inf, np.sqrt(h2.astype(np.float64)))
+
+
+# ------------------------------------------------------------------------------------------------- nearest site, grow
+def _value_set(what: str, name: str, values) -> frozenset:
+    """an iterable of integers in 0..255 as a set; anything else raises"""
+    if isinstance(values, (str, bytes, torch.Tensor)) or not isinstance(values, Iterable):
+        raise RmemError(f'{what}: {name} must be an iterable of integers in 0..255 (got {values!r})')
+    vals = list(values)
+    for v in vals:
+        if not is_int(v) or not 0 <= int(v) <= 255:
+            raise RmemError(f'{what}: {name} must be an iterable of integers in 0..255 (got {v!r} in it)')
+    return frozenset(int(v) for v in vals)
+
+
+def _bits(values) -> C.Array:
+    """the set as rmem_label_nearest takes it: eight 32-bit words, bit (v & 31) of word v >> 5"""
+    w = (C.c_uint * 8)()
+    for v in values:
+        w[v >> 5] |= 1 << (v & 31)
+    return w
+
+
+def _limit(what: str, max_distance, max_d2) -> int:
+    """max_d2 as the entry point takes it: -1 without a limit; max_distance = r is max_d2 = int(r * r)"""
+    if max_distance is not None and max_d2 is not None:
+        raise RmemError(f'{what}: give max_distance or max_d2, not both')
+    if max_d2 is not None:
+        return int_in(what, 'max_d2', max_d2, 0, MAX_D2, 'None or an integer in')
+    if max_distance is None:
+        return -1
+    if isinstance(max_distance, bool) or not isinstance(max_distance, (int, float, np.integer, np.floating)) \
+            or not math.isfinite(max_distance) or max_distance < 0:
+        raise RmemError(f'{what}: max_distance must be None or a finite number that is not negative (got {max_distance!r})')
+    r = float(max_distance)
+    return int(min(r * r, float(MAX_D2)))                            # no real squared distance reaches 2^30
+
+
+def _nearest(a, sites, fill, max_d2, index, dist2, taken, stream):
+    n, H, W = a.shape
+    L = _lib.lib()
+    ws = workspace('nearest', a.device, stream, int(L.rmem_label_nearest_workspace_bytes(n, H, W)))
+    _lib.check(L.rmem_label_nearest(a.data_ptr(), n, H, W, _bits(sites), None if fill is None else _bits(fill), max_d2,
+                                    None if index is None else index.data_ptr(), None if dist2 is None else dist2.data_ptr(),
+                                    None if taken is None else taken.data_ptr(), ws.data_ptr(), ws.numel(), stream.cuda_stream),
+               'rmem_label_nearest')
+    for t in (a, index, dist2, taken):
+        if t is not None:
+            t.record_stream(stream)
+
+
+def nearest(labels_u8: torch.Tensor, sites, max_distance: Optional[float] = None, max_d2: Optional[int] = None,
+            return_distance: bool = True) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
+    """(index, dist2), both int32 on the device and shaped like labels_u8 ([n, H, W] or [H, W]); dist2 is None with
+    return_distance=False.  A pixel is a SITE if its value is in `sites` (an iterable of integers in 0..255; empty: no sites).
+      index  the flat index y * W + x, within its frame, of the site nearest to the pixel by squared Euclidean distance between
+             pixel centres, AMONG EQUALLY NEAR SITES THE ONE WITH THE SMALLEST FLAT INDEX (the first in raster order); -1 where the
+             frame holds no site within the limit.  A site maps to itself.  scipy's distance_transform_edt(return_indices=True)
+             returns one of the equally near sites, not always this one.
+      dist2  that squared distance, SENTINEL where index is -1: label_edt(value=v)'s map for sites = {v} without a limit.
+    The limit: max_d2 (an integer in 0..2^30; a site at exactly max_d2 still counts), or max_distance = r for max_d2 = int(r * r);
+    giving both is refused, neither means no limit.  With a limit no scan is longer than its root.  H and W at most 16384.  The
+    vertical offsets live in a workspace per (device, stream).  Two launches on the current stream, no host sync."""
+    what = 'distance.nearest'
+    s = _value_set(what, 'sites', sites)
+    d2max = _limit(what, max_distance, max_d2)
+    a = _frames(what, labels_u8)
+    _geometry(what, a)
+    index = torch.empty(a.shape, dtype=torch.int32, device=a.device)
+    dist2 = torch.empty(a.shape, dtype=torch.int32, device=a.device) if return_distance else None
+    _nearest(a, s, None, d2max, index, dist2, None, torch.cuda.current_stream(a.device))
+    return index.view(labels_u8.shape), None if dist2 is None else dist2.view(labels_u8.shape)
+
+
+def grow(labels_u8: torch.Tensor, fill=(0,), sites=None, max_distance: Optional[float] = None, max_d2: Optional[int] = None,
+         out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """uint8 stack like labels_u8 on the device: every pixel whose value is in `fill` takes the value of its nearest site (nearest's
+    rule, ties to the smallest flat index) if there is one within the limit; every other pixel keeps its value.  sites: the values
+    that are sites; None: every value not in `fill`.  A value in both sets stays where it is (a site maps to itself); a value in
+    neither (a void label, say) is neither overwritten nor spread.  fill = (0,) grows the objects over the background without
+    ever overwriting one another; fill = (255,) with sites=None replaces a void label by the nearest real value.  max_distance /
+    max_d2: as nearest.  out: None allocates; a contiguous uint8 device tensor of the labels' shape that is not the labels is
+    written.  Only the stack is asked of the kernel: pixels outside `fill` are copied without a scan.  Two launches on the
+    current stream, no host sync."""
+    what = 'distance.grow'
+    f = _value_set(what, 'fill', fill)
+    s = frozenset(range(256)) - f if sites is None else _value_set(what, 'sites', sites)
+    d2max = _limit(what, max_distance, max_d2)
+    a = _frames(what, labels_u8)
+    _geometry(what, a)
+    if out is None:
+        taken = torch.empty(a.shape, dtype=torch.uint8, device=a.device)
+    else:
+        if (not isinstance(out, torch.Tensor) or out.dtype != torch.uint8 or out.device != a.device or out.shape != labels_u8.shape
+                or not out.is_contiguous()):
+            raise RmemError(f'{what}: out must be a contiguous uint8 tensor of the labels\' shape on their device')
+        if out.data_ptr() == a.data_ptr():
+            raise RmemError(f'{what}: out must not be the labels (they are read at the nearest site while out is written)')
+        taken = out.view(a.shape)
+    _nearest(a, s, f, d2max, None, None, taken, torch.cuda.current_stream(a.device))
+    return taken.view(labels_u8.shape) if out is None else out

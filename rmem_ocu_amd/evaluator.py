@@ -39,7 +39,11 @@ Mirrors what networks/managers/evaluator.py:330-568 does for one sequence, witho
     surface.py, surface_metrics;
   * the centre line of every object is a thinning on the device (Guo and Hall's rule, bit-identical to a host restatement), and
     with it the scribble of an interactive protocol: the longest path through the skeleton of the largest error --
-    rmem_label_thin, rmem_label_pixels_count / _write, skeleton.py, next_scribbles.
+    rmem_label_thin, rmem_label_pixels_count / _write, skeleton.py, next_scribbles;
+  * which pixel the nearest site is, not only how far, comes from the same two passes with the site carried along (ties to the
+    first site in raster order), and with the label read there objects grow without overlap, void pixels take the nearest real
+    value and sparse seeds become a full label map -- rmem_label_nearest, distance.nearest / grow, expand_masks, fill_void,
+    labels_from_seeds.
 """
 from __future__ import annotations
 
@@ -508,6 +512,46 @@ def next_scribbles(pred_u8: torch.Tensor, gt_u8: torch.Tensor, num_objs: int, mi
         if depth >= D:
             out[f][v] = {'positive': positive, 'path': longest_path(yx[component(yx, k)]), 'depth2': depth}
     return out
+
+
+def expand_masks(labels_u8: torch.Tensor, distance: float, void: Optional[int] = None) -> torch.Tensor:
+    """A new uint8 stack like labels_u8 ([n, H, W] or [H, W], device) in which every background pixel (value 0) within `distance`
+    pixels of an object has taken the nearest object's value -- skimage.segmentation.expand_labels' rule: objects grow without
+    ever overwriting one another, which closes the one-pixel gaps polygon and run-length annotations leave between touching
+    objects and builds tolerance bands.  Between equally near objects the pixel goes to the one whose nearest pixel comes first
+    in raster order (distance.nearest's rule; scikit-image takes whichever its host transform returns).  distance = r means squared distances
+    up to int(r * r).  void (1..255), if given, is neither filled nor spread.  distance.grow; the current stream, no host sync."""
+    from .distance import grow
+    what = 'evaluator.expand_masks'
+    if distance is None:
+        raise _lib.RmemError(f'{what}: distance must be a finite number that is not negative (got None)')
+    sites = set(range(1, 256))
+    if void is not None:
+        sites.discard(_labels.int_in(what, 'void', void, 1, 255, 'None or an integer in'))
+    return grow(labels_u8, fill=(0,), sites=sorted(sites), max_distance=distance)
+
+
+def fill_void(labels_u8: torch.Tensor, void: int = 255, max_distance: Optional[float] = None) -> torch.Tensor:
+    """A new uint8 stack like labels_u8 in which every pixel of value `void` (the 255 DAVIS-2016 / VOC-style annotations put on
+    uncertain boundary pixels, which png.decode_label_stack delivers as it is) has become the nearest other value, background
+    included, ties to the site that comes first in raster order: what a first-frame label or a ground truth for score_clip needs.
+    max_distance: void pixels farther than that from every other value stay void; a frame of nothing but void stays as it is.
+    distance.grow; the current stream, no host sync."""
+    from .distance import grow
+    return grow(labels_u8, fill=(_labels.int_in('evaluator.fill_void', 'void', void, 0, 255),), sites=None, max_distance=max_distance)
+
+
+def labels_from_seeds(seeds_u8: torch.Tensor, background: Optional[int] = None, max_distance: Optional[float] = None) -> torch.Tensor:
+    """A new uint8 label stack from a sparse seed stack (clicks, scribbles: next_clicks, next_scribbles): every pixel of value 0
+    takes the value of the nearest seed (a non-zero pixel), ties to the seed that comes first in raster order -- the nearest-seed
+    partition, the baseline rule of interactive protocols.  background (1..255), if given, is the value of NEGATIVE seeds: they
+    claim their region like any other and are then written as 0 (a masked_fill on the device).  max_distance: pixels farther than
+    that from every seed stay 0.  A frame without seeds is returned as it is.  distance.grow; the current stream, no host sync."""
+    from .distance import grow
+    what = 'evaluator.labels_from_seeds'
+    b = None if background is None else _labels.int_in(what, 'background', background, 1, 255, 'None or an integer in')
+    out = grow(seeds_u8, fill=(0,), sites=None, max_distance=max_distance)
+    return out if b is None else out.masked_fill_(out == b, 0)
 
 
 def relabel_to_match(pred_u8: torch.Tensor, gt_u8: torch.Tensor, num_pred: int, num_gt: int):
