@@ -1,5 +1,6 @@
 """Argument checks and small rules the modules on uint8 label stacks share (pairs, components, polygons, rle, the label part of
-evaluator): integers in a range, connectivity, the stack and its limits, a pair of stacks, the workspace budget of a call that
+evaluator, distance, surface, skeleton): integers in a range, connectivity, the stack and its limits, the sides the separable
+transforms take, a tensor that goes with a stack, a pair of stacks, the workspace budget of a call that
 passes over a stack, the keys of un-squeezed objects, the boundary P / R / F.  Streams, workspaces and packed files are _codec's."""
 from __future__ import annotations
 
@@ -12,6 +13,7 @@ from ._codec import uint8_stack
 from ._lib import RmemError
 
 MAX_FRAMES, MAX_PIXELS = 65535, 1 << 26      # csrc/label_wave.h: kMaxFrames, kMaxPixels
+MAX_SIDE = 16384                             # csrc/label_sep.h: kMaxSide, the separable transforms (distance, surface)
 WORKSPACE_CAP = 256 << 20                    # bytes one pass over a stack keeps, unless one frame needs more
 
 
@@ -38,6 +40,22 @@ def stack(what: str, t, name: str = 'labels') -> torch.Tensor:
     if H * W > MAX_PIXELS or n > MAX_FRAMES:
         raise RmemError(f'{what}: {name} of {n} x {H} x {W} are too large (H * W at most 2^26, at most 65535 frames)')
     return a
+
+
+def geometry(what: str, a: torch.Tensor) -> Tuple[int, int, int]:
+    """(n, H, W) of a stack() view whose sides the separable transforms take"""
+    n, H, W = a.shape
+    if H > MAX_SIDE or W > MAX_SIDE:
+        raise RmemError(f'{what}: frames of {H} x {W} are too large (H and W at most {MAX_SIDE})')
+    return n, H, W
+
+
+def like_labels(what: str, t, name: str, dtype: torch.dtype, labels: torch.Tensor, a: torch.Tensor) -> torch.Tensor:
+    """t, a tensor the caller passed to go with `labels` (whose stack() view is a), viewed to a's shape; refused unless it is a
+    contiguous tensor of that dtype, of the labels' shape, on their device"""
+    if not isinstance(t, torch.Tensor) or t.dtype != dtype or t.device != a.device or t.shape != labels.shape or not t.is_contiguous():
+        raise RmemError(f'{what}: {name} must be a contiguous {str(dtype)[6:]} tensor of the labels\' shape on their device')
+    return t.view(a.shape)
 
 
 def stack_pair(what: str, a_u8, b_u8, names: Tuple[str, str] = ('a', 'b'), devices: bool = True) -> Tuple[torch.Tensor, torch.Tensor]:

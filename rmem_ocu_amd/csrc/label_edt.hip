@@ -4,7 +4,7 @@
 //
 // A SITE of pixel p is what p's distance is measured to: in the "other" mode (value = -1) a pixel of the frame that holds another
 // value than p, and with `border` the first pixel outside the frame; in the "to value" mode the pixels that hold `value`.
-// Separable, two passes:
+// Separable, two passes (label_sep.h holds what they share with label_nearest.hip, the row pass' scan included):
 //
 //   k_edt_cols   One thread per column, 64 columns per workgroup: consecutive lanes read consecutive bytes of a row.  A sweep down
 //                the column and one up keep the vertical distance to the last site met, g[y][x] = the smaller of the two as 16
@@ -13,13 +13,12 @@
 //   k_edt_rows   One workgroup per row.  The row's labels and g go to LDS (50 KB at W = 16384, summaries included), then a thread
 //                takes pixels x = t, t + 256, ...: d2(x) = min over x' of (x - x')^2 + f(x'), f = g^2 where the row holds p's value
 //                at x' (to value: everywhere) and 0 at the first pixel of another value on either side, where that side ends.
-//                It scans outward and stops when dx^2 >= the best so far: the length is bounded by the root of the result, not by
-//                W.  Stride-1 LDS reads.  The two sides take turns, the rest of a segment of kSeg pixels at a time, and a segment
-//                keeps a summary in LDS (its smallest g; the value its pixels share, if they do): a rest whose summary says that
-//                it cannot win -- no pixel of another value, dx^2 + (smallest g)^2 not below the best so far -- is skipped in one
-//                step, so columns without a site and flat stretches of g cost a look per 32 pixels.  A row that holds no site at
-//                all (one value, every g none; known from a workgroup-wide OR while the row is loaded) is filled with the
-//                sentinel without a scan.
+//                label_sep.h's outward scan under EdtRule: it stops when dx^2 >= the best so far, so its length is bounded by the
+//                root of the result, not by W.  Stride-1 LDS reads.  A segment keeps a summary in LDS (its smallest g; the value
+//                its pixels share, if they do): a rest whose summary says that it cannot win -- no pixel of another value,
+//                dx^2 + (smallest g)^2 not below the best so far -- is skipped in one step, so columns without a site and flat
+//                stretches of g cost a look per 32 pixels.  A row that holds no site at all (one value, every g none; known from
+//                a workgroup-wide OR while the row is loaded) is filled with the sentinel without a scan.
 //   k_edt_rows_at
 //                The to-value row pass at the pixels with keys == key alone (rmem_label_edt_at): a row without a key
 //                pixel leaves before it reads g, in the others a thread per pixel skips the pixels without the key.
@@ -30,16 +29,11 @@
 //                The last launch unpacks the keys into (d2, index), (-1, -1) where the key is still 0 (no pixel).
 //
 // No kernel waits for another workgroup, every loop is bounded by H or W, nothing is indexed beyond [0, H) x [0, W).
-#include <limits.h>
-#include "label_wave.h"
+#include "label_sep.h"
 #include "../../include/rmem.h"
 
 namespace {
-constexpr int kMaxSide = 16384;                    // every real distance below 2^30: no meeting the sentinel, no overflow
 constexpr int kNone = 0xffff;                      // g: no site in this column (a real g is at most kMaxSide)
-constexpr int kSentinel = INT_MAX;                 // dist2: no site in this frame
-constexpr int kColThreads = 64;
-constexpr int kSeg = 32;                           // pixels of a row that share one summary in the row pass
 constexpr int kMixed = 0x100;                      // a segment's value: its pixels differ
 static_assert(2 * kMaxSide * kMaxSide < (1 << 30) + 1 && kMaxSide < kNone, "distance range");
 
@@ -72,31 +66,42 @@ __global__ __launch_bounds__(kColThreads) void k_edt_cols(const unsigned char* _
   }
 }
 
-// one side of a pixel's scan over the rest of the segment the cursor q stands in, towards `end` (inclusive) in steps of `step`;
-// false: this side is done (a pixel of another value was met, or nothing farther can win)
-__device__ __forceinline__ bool scan_piece(const unsigned short* sg, const unsigned char* sl, int x, int q, int end, int step, bool other,
-                                           int me, int& best) {
-  for (;; q += step) {
-    const int dx = (q - x) * step;
-    if (dx * dx >= best) return false;
-    if (other && sl[q] != me) {
-      best = dx * dx;
+// label_sep.h's rule of the distance alone: best = min over the columns q of dx^2 + g(q)^2.  Only a strictly smaller distance
+// improves it, so what can at most equal it is left out: >= in far and idle (NearestRule, which breaks ties by index, has >).
+// kOther: the other-value mode, where a side ends at its first pixel of another value than `me`, at distance dx^2; the to-value
+// mode reads neither sl nor suni.  A compile-time parameter: as a run-time member it keeps the mode's tests inside the scan's
+// loops, which was measured slower in both modes.
+template <bool kOther>
+struct EdtRule {
+  const unsigned short *sg, *smin, *suni;          // the row's g; per segment its smallest g and the value its pixels share
+  const unsigned char* sl;                         // the row's labels
+  int me, best;
+  __device__ __forceinline__ bool far(int dx2) const { return dx2 >= best; }
+  __device__ __forceinline__ bool idle(int k, int dx2) const {
+    const int m = smin[k];
+    return (m == kNone || dx2 + m * m >= best) && (!kOther || suni[k] == me);
+  }
+  __device__ __forceinline__ bool visit(int q, int dx2) {
+    if (kOther && sl[q] != me) {
+      best = dx2;
       return false;
     }
     const int gq = sg[q];
-    if (gq != kNone) best = min(best, dx * dx + gq * gq);
-    if (q == end) return true;
+    best = gq != kNone ? min(best, dx2 + gq * gq) : best;
+    return true;
   }
-}
+};
+
+// LDS of k_edt_rows: [wpad] the row's g, [nseg] the smallest g of a segment, [nseg] the value all its pixels hold (kMixed if they
+// differ), 16 bits each, then [W] the row's labels
+inline size_t edt_rows_lds(int W) { return (size_t)row_wpad(W) * 2 + (size_t)row_segments(W) * 4 + W; }
 
 __global__ __launch_bounds__(kThreads) void k_edt_rows(const unsigned char* __restrict__ labels, const unsigned short* __restrict__ g, int H,
                                                        int W, int wpad, int value, int border, int* __restrict__ dist2) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  const int nseg = (W + kSeg - 1) / kSeg;
-  unsigned short* sg = (unsigned short*)smem;      // [wpad] the row's g
-  unsigned short* smin = sg + wpad;                // [nseg] the smallest g of a segment of kSeg pixels
-  unsigned short* suni = smin + nseg;              // [nseg] the value all its pixels hold, kMixed if they differ
-  unsigned char* sl = (unsigned char*)(suni + nseg);   // [W] the row's labels
+  const int nseg = row_segments(W);
+  unsigned short *sg = (unsigned short*)smem, *smin = sg + wpad, *suni = smin + nseg;
+  unsigned char* sl = (unsigned char*)(suni + nseg);
   const int t = threadIdx.x;
   const size_t base = ((size_t)blockIdx.y * H + blockIdx.x) * W;
   const bool other = value < 0;
@@ -125,40 +130,20 @@ __global__ __launch_bounds__(kThreads) void k_edt_rows(const unsigned char* __re
   }
   __syncthreads();
   for (int x = t; x < W; x += kThreads) {
-    const int me = sl[x], g0 = sg[x];
+    const int g0 = sg[x];
     int best = g0 == kNone ? kSentinel : g0 * g0;
-    if (other && border) {
-      const int e = min(x + 1, W - x);
-      best = min(best, e * e);
-    }
-    // the two sides take turns, a segment's rest at a time; a rest is skipped where its summary says that it cannot win:
-    // no pixel of another value in it, and dx^2 + (its smallest g)^2 not below the best so far
-    int ql = x - 1, qr = x + 1;
-    bool left = ql >= 0, right = qr < W;
-    while (left || right) {
-      if (left) {
-        const int dx = x - ql, k = ql / kSeg, m = smin[k];
-        if (dx * dx >= best) {
-          left = false;
-        } else {
-          const bool skip = (m == kNone || dx * dx + m * m >= best) && (!other || suni[k] == me);
-          if (!skip) left = scan_piece(sg, sl, x, ql, k * kSeg, -1, other, me, best);
-          ql = k * kSeg - 1;
-          left = left && ql >= 0;
-        }
+    if (other) {                                   // the same in every thread
+      if (border) {
+        const int e = min(x + 1, W - x);
+        best = min(best, e * e);
       }
-      if (right) {
-        const int dx = qr - x, k = qr / kSeg, m = smin[k];
-        if (dx * dx >= best) {
-          right = false;
-        } else {
-          const bool skip = (m == kNone || dx * dx + m * m >= best) && (!other || suni[k] == me);
-          const int end = min(k * kSeg + kSeg, W) - 1;
-          if (!skip) right = scan_piece(sg, sl, x, qr, end, 1, other, me, best);
-          qr = end + 1;
-          right = right && qr < W;
-        }
-      }
+      EdtRule<true> r{sg, smin, suni, sl, sl[x], best};
+      scan_outward(r, x, W);
+      best = r.best;
+    } else {
+      EdtRule<false> r{sg, smin, nullptr, nullptr, 0, best};
+      scan_outward(r, x, W);
+      best = r.best;
     }
     dist2[base + x] = best;
   }
@@ -168,14 +153,16 @@ __global__ __launch_bounds__(kThreads) void k_edt_rows(const unsigned char* __re
 // The to-value row pass at the pixels with keys == key alone (rmem_label_edt_at).  One workgroup per row.  It reads the row's keys
 // first and leaves at once when none is the key (a workgroup-wide OR): such a row never reads g.  Otherwise the row's g and the
 // segment summaries go to LDS as in k_edt_rows (33 KB at W = 16384), and a thread takes pixels x = t, t + 256, ... and skips those
-// without the key.  Labels are not needed: a site is where g == 0.  Compacting the key pixels into a list first was measured and
-// gained nothing on sparse keys.
+// without the key, under EdtRule<false>, the to-value form.  Labels are not needed: a site is where g == 0.  Compacting the key pixels
+// into a list first was measured and gained nothing on sparse keys.
+// LDS of k_edt_rows_at: [wpad] the row's g, [nseg] the smallest g of a segment, 16 bits each
+inline size_t edt_rows_at_lds(int W) { return (size_t)row_wpad(W) * 2 + (size_t)row_segments(W) * 2; }
+
 __global__ __launch_bounds__(kThreads) void k_edt_rows_at(const unsigned short* __restrict__ g, const unsigned char* __restrict__ keys,
                                                           int H, int W, int wpad, int key, int* __restrict__ samples) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  const int nseg = (W + kSeg - 1) / kSeg;
-  unsigned short* sg = (unsigned short*)smem;      // [wpad] the row's g
-  unsigned short* smin = sg + wpad;                // [nseg] the smallest g of a segment of kSeg pixels
+  const int nseg = row_segments(W);
+  unsigned short *sg = (unsigned short*)smem, *smin = sg + wpad;
   const int t = threadIdx.x;
   const size_t base = ((size_t)blockIdx.y * H + blockIdx.x) * W;
   int has = 0;
@@ -198,34 +185,9 @@ __global__ __launch_bounds__(kThreads) void k_edt_rows_at(const unsigned short* 
   for (int x = t; x < W; x += kThreads) {
     if (keys[base + x] != key) continue;
     const int g0 = sg[x];
-    int best = g0 == kNone ? kSentinel : g0 * g0;
-    // k_edt_rows' scan in its to-value form: no labels, a rest is skipped where dx^2 + (its smallest g)^2 cannot win
-    int ql = x - 1, qr = x + 1;
-    bool left = any && ql >= 0, right = any && qr < W;               // no site in the frame: the sentinel without a scan
-    while (left || right) {
-      if (left) {
-        const int dx = x - ql, k = ql / kSeg, mn = smin[k];
-        if (dx * dx >= best) {
-          left = false;
-        } else {
-          if (mn != kNone && dx * dx + mn * mn < best) left = scan_piece(sg, nullptr, x, ql, k * kSeg, -1, false, 0, best);
-          ql = k * kSeg - 1;
-          left = left && ql >= 0;
-        }
-      }
-      if (right) {
-        const int dx = qr - x, k = qr / kSeg, mn = smin[k];
-        if (dx * dx >= best) {
-          right = false;
-        } else {
-          const int end = min(k * kSeg + kSeg, W) - 1;
-          if (mn != kNone && dx * dx + mn * mn < best) right = scan_piece(sg, nullptr, x, qr, end, 1, false, 0, best);
-          qr = end + 1;
-          right = right && qr < W;
-        }
-      }
-    }
-    samples[base + x] = best;
+    EdtRule<false> r{sg, smin, nullptr, nullptr, 0, g0 == kNone ? kSentinel : g0 * g0};
+    scan_outward(r, x, W, any);                    // no site in the frame: the sentinel without a scan
+    samples[base + x] = r.best;
   }
 }
 
@@ -258,51 +220,38 @@ __global__ __launch_bounds__(kThreads) void k_peaks_table(const unsigned long lo
   table[2 * i] = key ? (int)(unsigned)(key >> 32) : -1;
   table[2 * i + 1] = key ? (int)(0xffffffffu - (unsigned)(key & 0xffffffffull)) : -1;
 }
-
-inline bool edt_geometry_ok(int n, int H, int W) { return stack_geometry_ok(n, H, W) && H <= kMaxSide && W <= kMaxSide; }
 }  // namespace
 
-extern "C" long long rmem_label_edt_workspace_bytes(int n, int H, int W) {
-  if (!edt_geometry_ok(n, H, W)) return 0;
-  return ((long long)n * H * W * 2 + 15) & ~15LL;                  // g, 16 bits per pixel
-}
+extern "C" long long rmem_label_edt_workspace_bytes(int n, int H, int W) { return sep_workspace_bytes(n, H, W); }   // g
 
 extern "C" int rmem_label_edt(const unsigned char* labels, int n, int H, int W, int value, int border, int* dist2, void* workspace,
                               long long workspace_bytes, void* stream) {
   RMEM_REQUIRE(labels && dist2 && workspace, "rmem_label_edt: null pointer (labels, dist2 and workspace are required)");
-  RMEM_REQUIRE(n >= 1 && n <= kMaxFrames, "rmem_label_edt: n must be in 1..65535");
-  RMEM_REQUIRE(stack_geometry_ok(n, H, W), "rmem_label_edt: H and W must be positive, H * W at most 2^26");
-  RMEM_REQUIRE(H <= kMaxSide && W <= kMaxSide, "rmem_label_edt: H and W must be at most 16384");
+  RMEM_REQUIRE_SEP_STACK("rmem_label_edt", n, H, W);
   RMEM_REQUIRE(value >= -1 && value <= 255, "rmem_label_edt: value must be -1 (every other value) or in 0..255");
   RMEM_REQUIRE(border == 0 || border == 1, "rmem_label_edt: border must be 0 or 1");
   RMEM_REQUIRE(!(value >= 0 && border), "rmem_label_edt: border must be 0 with a value (the frame's edge is no pixel of it)");
-  RMEM_REQUIRE(workspace_bytes >= rmem_label_edt_workspace_bytes(n, H, W), "rmem_label_edt: workspace too small (rmem_label_edt_workspace_bytes)");
-  RMEM_REQUIRE(((uintptr_t)workspace & 3u) == 0, "rmem_label_edt: workspace must be 4-byte aligned");
+  RMEM_REQUIRE_SEP_WORKSPACE("rmem_label_edt", "rmem_label_edt_workspace_bytes", n, H, W, workspace, workspace_bytes);
   unsigned short* g = (unsigned short*)workspace;
-  const int wpad = (W + 7) & ~7;
   hipLaunchKernelGGL(k_edt_cols, dim3((W + kColThreads - 1) / kColThreads, n), dim3(kColThreads), 0, (hipStream_t)stream, labels, H, W, value,
                      border, g);
-  hipLaunchKernelGGL(k_edt_rows, dim3(H, n), dim3(kThreads), (size_t)wpad * 2 + (size_t)((W + kSeg - 1) / kSeg) * 4 + W, (hipStream_t)stream, labels, g, H, W, wpad, value, border,
-                     dist2);
+  hipLaunchKernelGGL(k_edt_rows, dim3(H, n), dim3(kThreads), edt_rows_lds(W), (hipStream_t)stream, labels, g, H, W, row_wpad(W), value,
+                     border, dist2);
   return rmem_check_launch("rmem_label_edt");
 }
 
 extern "C" int rmem_label_edt_at(const unsigned char* labels, const unsigned char* keys, int n, int H, int W, int value, int key, int* samples,
                                  void* workspace, long long workspace_bytes, void* stream) {
   RMEM_REQUIRE(labels && keys && samples && workspace, "rmem_label_edt_at: null pointer (labels, keys, samples and workspace are required)");
-  RMEM_REQUIRE(n >= 1 && n <= kMaxFrames, "rmem_label_edt_at: n must be in 1..65535");
-  RMEM_REQUIRE(stack_geometry_ok(n, H, W), "rmem_label_edt_at: H and W must be positive, H * W at most 2^26");
-  RMEM_REQUIRE(H <= kMaxSide && W <= kMaxSide, "rmem_label_edt_at: H and W must be at most 16384");
+  RMEM_REQUIRE_SEP_STACK("rmem_label_edt_at", n, H, W);
   RMEM_REQUIRE(value >= 0 && value <= 255, "rmem_label_edt_at: value must be in 0..255");
   RMEM_REQUIRE(key >= 0 && key <= 255, "rmem_label_edt_at: key must be in 0..255");
-  RMEM_REQUIRE(workspace_bytes >= rmem_label_edt_workspace_bytes(n, H, W), "rmem_label_edt_at: workspace too small (rmem_label_edt_workspace_bytes)");
-  RMEM_REQUIRE(((uintptr_t)workspace & 3u) == 0, "rmem_label_edt_at: workspace must be 4-byte aligned");
+  RMEM_REQUIRE_SEP_WORKSPACE("rmem_label_edt_at", "rmem_label_edt_workspace_bytes", n, H, W, workspace, workspace_bytes);
   unsigned short* g = (unsigned short*)workspace;
-  const int wpad = (W + 7) & ~7;
   hipLaunchKernelGGL(k_edt_cols, dim3((W + kColThreads - 1) / kColThreads, n), dim3(kColThreads), 0, (hipStream_t)stream, labels, H, W, value,
                      0, g);
-  hipLaunchKernelGGL(k_edt_rows_at, dim3(H, n), dim3(kThreads), (size_t)wpad * 2 + (size_t)((W + kSeg - 1) / kSeg) * 2, (hipStream_t)stream, g,
-                     keys, H, W, wpad, key, samples);
+  hipLaunchKernelGGL(k_edt_rows_at, dim3(H, n), dim3(kThreads), edt_rows_at_lds(W), (hipStream_t)stream, g, keys, H, W, row_wpad(W), key,
+                     samples);
   return rmem_check_launch("rmem_label_edt_at");
 }
 

@@ -14,7 +14,7 @@
 //   k_nearest_rows  One workgroup per row.  The row's s and the smallest |s| of every segment of kSeg pixels go to LDS (33 KB at
 //                   W = 16384); labels are not staged, a site is where s == 0.  A thread takes pixels x = t, t + 256, ... and
 //                   keeps the lexicographic minimum of (d2, index) over the columns x': d2 = (x - x')^2 + s(x')^2, index =
-//                   (y + s(x')) * W + x'.  k_edt_rows' outward scan with segment skipping, but both bounds STRICT: a side ends
+//                   (y + s(x')) * W + x'.  label_sep.h's outward scan under NearestRule, whose bounds are both STRICT: a side ends
 //                   only when dx^2 > the best d2, a segment's rest is skipped only when dx^2 + (its smallest |s|)^2 > the best
 //                   d2, because a candidate at exactly the best d2 may still win on its index.  With a limit the scan starts at
 //                   best = max_d2 and is never longer than its root.  taken[p] = labels[index[p]] where labels[p] is in `fill`
@@ -24,18 +24,13 @@
 //
 // The two sets are kernel arguments (eight 32-bit words each): no table on the device, no upload.  No kernel waits for another
 // workgroup, every loop is bounded by H, W or a segment, nothing is indexed beyond [0, H) x [0, W).
-#include <limits.h>
-#include "label_wave.h"
+#include "label_sep.h"
 #include "../../include/rmem.h"
 
 namespace {
-constexpr int kMaxSide = 16384;                    // |s| <= 16383 fits 15 bits, every real distance is below 2^30
-constexpr int kNoSite = -32768;                    // s: no site in this column (0x8000)
+constexpr int kNoSite = -32768;                    // s: no site in this column (0x8000); |s| <= kMaxSide - 1 fits 15 bits
 constexpr int kNoMin = 0xffff;                     // a segment's smallest |s|: no site in any of its columns
-constexpr int kSentinel = INT_MAX;                 // dist2: no site in this frame within the limit
-constexpr int kMaxD2 = 1 << 30;
-constexpr int kColThreads = 64;
-constexpr int kSeg = 32;                           // pixels of a row that share one summary in the row pass
+constexpr int kMaxD2 = 1 << 30;                    // above every real squared distance
 static_assert(2 * (kMaxSide - 1) * (kMaxSide - 1) < kMaxD2 && kMaxSide - 1 < -kNoSite, "distance range");
 
 struct Bits256 {
@@ -66,34 +61,39 @@ __global__ __launch_bounds__(kColThreads) void k_nearest_cols(const unsigned cha
   }
 }
 
-// the candidate of column q for the pixel at column x of row y joins the lexicographic minimum of (d2, index)
-__device__ __forceinline__ void consider(int sq, int dx2, int y, int q, int W, int& best, int& bidx) {
-  const int d2 = dx2 + sq * sq, idx = (y + sq) * W + q;
-  if (d2 < best || (d2 == best && idx < bidx)) {
-    best = d2;
-    bidx = idx;
+// label_sep.h's rule of the nearest site: (best, bidx) = the lexicographic minimum over the columns q of (d2, index), d2 = dx^2 +
+// s(q)^2, index = (y + s(q)) * W + q.  A candidate at exactly the best d2 may still win on its index, so only what is strictly
+// farther is left out: > in far and idle (EdtRule, which keeps the distance alone, has >=).  bidx INT_MAX: nothing found yet;
+// any real index beats it on a tie.
+struct NearestRule {
+  const short* ss;                                 // the row's s
+  const unsigned short* smin;                      // per segment its smallest |s|
+  int y, W, best, bidx;
+  __device__ __forceinline__ bool far(int dx2) const { return dx2 > best; }
+  __device__ __forceinline__ bool idle(int k, int dx2) const {
+    const int m = smin[k];
+    return m == kNoMin || dx2 + m * m > best;
   }
-}
+  __device__ __forceinline__ bool visit(int q, int dx2) {
+    const int sq = ss[q], d2 = dx2 + sq * sq, idx = (y + sq) * W + q;
+    if (sq != kNoSite && (d2 < best || (d2 == best && idx < bidx))) {
+      best = d2;
+      bidx = idx;
+    }
+    return true;
+  }
+};
 
-// one side of a pixel's scan over the rest of the segment the cursor q stands in, towards `end` (inclusive) in steps of `step`;
-// false: this side is done (nothing farther can win or tie)
-__device__ __forceinline__ bool scan_piece(const short* ss, int x, int y, int W, int q, int end, int step, int& best, int& bidx) {
-  for (;; q += step) {
-    const int dx = (q - x) * step;
-    if (dx * dx > best) return false;
-    const int sq = ss[q];
-    if (sq != kNoSite) consider(sq, dx * dx, y, q, W, best, bidx);
-    if (q == end) return true;
-  }
-}
+// LDS of k_nearest_rows: [wpad] the row's s, [nseg] the smallest |s| of a segment, 16 bits each
+inline size_t nearest_rows_lds(int W) { return (size_t)row_wpad(W) * 2 + (size_t)row_segments(W) * 2; }
 
 __global__ __launch_bounds__(kThreads) void k_nearest_rows(const unsigned char* __restrict__ labels, const short* __restrict__ s, int H, int W,
                                                            int wpad, Bits256 fill, int max_d2, int* __restrict__ index,
                                                            int* __restrict__ dist2, unsigned char* __restrict__ taken) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  const int nseg = (W + kSeg - 1) / kSeg;
-  short* ss = (short*)smem;                        // [wpad] the row's s
-  unsigned short* smin = (unsigned short*)(ss + wpad);   // [nseg] the smallest |s| of a segment of kSeg pixels
+  const int nseg = row_segments(W);
+  short* ss = (short*)smem;
+  unsigned short* smin = (unsigned short*)(ss + wpad);
   const int t = threadIdx.x, y = blockIdx.x;
   const size_t frame = (size_t)blockIdx.y * H * W, base = frame + (size_t)y * W;
   const bool maps = index || dist2;                // the same in every thread
@@ -137,48 +137,18 @@ __global__ __launch_bounds__(kThreads) void k_nearest_rows(const unsigned char* 
       taken[base + x] = (unsigned char)me;
       continue;
     }
-    int best = max_d2 < 0 ? kSentinel : max_d2, bidx = INT_MAX;      // bidx INT_MAX: nothing found; any real index beats it on a tie
-    const int s0 = ss[x];
-    if (s0 != kNoSite) consider(s0, 0, y, x, W, best, bidx);
-    // the two sides take turns, a segment's rest at a time; a rest is skipped where its summary says that it can neither win nor
-    // tie: dx^2 + (its smallest |s|)^2 above the best so far
-    int ql = x - 1, qr = x + 1;
-    bool left = ql >= 0, right = qr < W;
-    while (left || right) {
-      if (left) {
-        const int dx = x - ql, k = ql / kSeg, m = smin[k];
-        if (dx * dx > best) {
-          left = false;
-        } else {
-          if (m != kNoMin && dx * dx + m * m <= best) left = scan_piece(ss, x, y, W, ql, k * kSeg, -1, best, bidx);
-          ql = k * kSeg - 1;
-          left = left && ql >= 0;
-        }
-      }
-      if (right) {
-        const int dx = qr - x, k = qr / kSeg, m = smin[k];
-        if (dx * dx > best) {
-          right = false;
-        } else {
-          const int end = min(k * kSeg + kSeg, W) - 1;
-          if (m != kNoMin && dx * dx + m * m <= best) right = scan_piece(ss, x, y, W, qr, end, 1, best, bidx);
-          qr = end + 1;
-          right = right && qr < W;
-        }
-      }
-    }
-    const bool found = bidx != INT_MAX;
-    if (index) index[base + x] = found ? bidx : -1;
-    if (dist2) dist2[base + x] = found ? best : kSentinel;
-    if (taken) taken[base + x] = (fills && found) ? labels[frame + bidx] : (unsigned char)me;
+    NearestRule r{ss, smin, y, W, max_d2 < 0 ? kSentinel : max_d2, INT_MAX};
+    r.visit(x, 0);                                 // the pixel's own column
+    scan_outward(r, x, W);
+    const bool found = r.bidx != INT_MAX;
+    if (index) index[base + x] = found ? r.bidx : -1;
+    if (dist2) dist2[base + x] = found ? r.best : kSentinel;
+    if (taken) taken[base + x] = (fills && found) ? labels[frame + r.bidx] : (unsigned char)me;
   }
 }
 }  // namespace
 
-extern "C" long long rmem_label_nearest_workspace_bytes(int n, int H, int W) {
-  if (!stack_geometry_ok(n, H, W) || H > kMaxSide || W > kMaxSide) return 0;
-  return ((long long)n * H * W * 2 + 15) & ~15LL;                  // s, 16 bits per pixel
-}
+extern "C" long long rmem_label_nearest_workspace_bytes(int n, int H, int W) { return sep_workspace_bytes(n, H, W); }   // s
 
 extern "C" int rmem_label_nearest(const unsigned char* labels, int n, int H, int W, const unsigned int site_bits[8],
                                   const unsigned int fill_bits[8], int max_d2, int* index, int* dist2, unsigned char* taken, void* workspace,
@@ -186,23 +156,18 @@ extern "C" int rmem_label_nearest(const unsigned char* labels, int n, int H, int
   RMEM_REQUIRE(labels && site_bits && workspace, "rmem_label_nearest: null pointer (labels, site_bits and workspace are required)");
   RMEM_REQUIRE(index || dist2 || taken, "rmem_label_nearest: no output (at least one of index, dist2 and taken is required)");
   RMEM_REQUIRE(taken != labels, "rmem_label_nearest: taken must not be labels (labels are read at the nearest site while taken is written)");
-  RMEM_REQUIRE(n >= 1 && n <= kMaxFrames, "rmem_label_nearest: n must be in 1..65535");
-  RMEM_REQUIRE(stack_geometry_ok(n, H, W), "rmem_label_nearest: H and W must be positive, H * W at most 2^26");
-  RMEM_REQUIRE(H <= kMaxSide && W <= kMaxSide, "rmem_label_nearest: H and W must be at most 16384");
+  RMEM_REQUIRE_SEP_STACK("rmem_label_nearest", n, H, W);
   RMEM_REQUIRE(max_d2 >= -1 && max_d2 <= kMaxD2, "rmem_label_nearest: max_d2 must be -1 (no limit) or in 0..2^30");
-  RMEM_REQUIRE(workspace_bytes >= rmem_label_nearest_workspace_bytes(n, H, W),
-               "rmem_label_nearest: workspace too small (rmem_label_nearest_workspace_bytes)");
-  RMEM_REQUIRE(((uintptr_t)workspace & 3u) == 0, "rmem_label_nearest: workspace must be 4-byte aligned");
+  RMEM_REQUIRE_SEP_WORKSPACE("rmem_label_nearest", "rmem_label_nearest_workspace_bytes", n, H, W, workspace, workspace_bytes);
   Bits256 sites, fill;
   for (int i = 0; i < 8; ++i) {
     sites.w[i] = site_bits[i];
     fill.w[i] = fill_bits ? fill_bits[i] : 0xffffffffu;
   }
   short* s = (short*)workspace;
-  const int wpad = (W + 7) & ~7;
   hipLaunchKernelGGL(k_nearest_cols, dim3((W + kColThreads - 1) / kColThreads, n), dim3(kColThreads), 0, (hipStream_t)stream, labels, H, W, sites,
                      s);
-  hipLaunchKernelGGL(k_nearest_rows, dim3(H, n), dim3(kThreads), (size_t)wpad * 2 + (size_t)((W + kSeg - 1) / kSeg) * 2, (hipStream_t)stream,
-                     labels, s, H, W, wpad, fill, max_d2, index, dist2, taken);
+  hipLaunchKernelGGL(k_nearest_rows, dim3(H, n), dim3(kThreads), nearest_rows_lds(W), (hipStream_t)stream, labels, s, H, W, row_wpad(W), fill,
+                     max_d2, index, dist2, taken);
   return rmem_check_launch("rmem_label_nearest");
 }

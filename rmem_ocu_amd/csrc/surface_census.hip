@@ -25,7 +25,7 @@
 #include "../../include/rmem.h"
 
 namespace {
-constexpr int kMaxSide = 16384;                    // label_edt.hip: every real sample is below 2^30
+constexpr int kMaxSide = 16384;                    // label_sep.h: every real sample is below 2^30
 constexpr int kSentinel = INT_MAX;
 constexpr int kDigitBits = 10, kBins = 1 << kDigitBits, kDigits = 3;
 constexpr int kAcc = 7;                            // count, sum_fix, max, within[4]

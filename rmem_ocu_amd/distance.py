@@ -17,19 +17,12 @@ import torch
 
 from . import _lib
 from ._codec import workspace
-from ._labels import frames_per_pass, int_in, is_int, stack as _frames, stack_pair
+from ._labels import MAX_SIDE  # noqa: F401  (part of this module's interface)
+from ._labels import frames_per_pass, geometry, int_in, is_int, like_labels, stack as _frames, stack_pair
 from ._lib import RmemError
 
 SENTINEL = 2 ** 31 - 1
-MAX_SIDE = 16384                             # csrc/label_edt.hip, csrc/label_nearest.hip: kMaxSide
 MAX_D2 = 2 ** 30                             # csrc/label_nearest.hip: kMaxD2, above every real squared distance
-
-
-def _geometry(what: str, a: torch.Tensor):
-    n, H, W = a.shape
-    if H > MAX_SIDE or W > MAX_SIDE:
-        raise RmemError(f'{what}: frames of {H} x {W} are too large (H and W at most {MAX_SIDE})')
-    return n, H, W
 
 
 def _edt(a, value, border, dist2, g, stream):
@@ -58,14 +51,11 @@ def label_edt(labels_u8: torch.Tensor, value: Optional[int] = None, border: bool
     what = 'distance.label_edt'
     v = -1 if value is None else int_in(what, 'value', value, 0, 255, 'None or an integer in')
     a = _frames(what, labels_u8)
-    n, H, W = _geometry(what, a)
+    n, H, W = geometry(what, a)
     if out is None:
         dist2 = torch.empty(a.shape, dtype=torch.int32, device=a.device)
     else:
-        if (not isinstance(out, torch.Tensor) or out.dtype != torch.int32 or out.device != a.device or out.shape != labels_u8.shape
-                or not out.is_contiguous()):
-            raise RmemError(f'{what}: out must be a contiguous int32 tensor of the labels\' shape on their device')
-        dist2 = out.view(a.shape)
+        dist2 = like_labels(what, out, 'out', torch.int32, labels_u8, a)
     stream = torch.cuda.current_stream(a.device)
     g = workspace('edt', a.device, stream, int(_lib.lib().rmem_label_edt_workspace_bytes(n, H, W)))
     _edt(a, v, int(bool(border)) if value is None else 0, dist2, g, stream)
@@ -110,7 +100,7 @@ def hausdorff2(a_u8: torch.Tensor, b_u8: torch.Tensor, num_objs: int, workspace_
     a, b = stack_pair(what, a_u8, b_u8)
     for t in (a, b):
         _frames(what, t)
-    n, H, W = _geometry(what, a)
+    n, H, W = geometry(what, a)
     L = _lib.lib()
     HW4 = H * W * 4
     g1, p1 = int(L.rmem_label_edt_workspace_bytes(1, H, W)), int(L.rmem_label_edt_peaks_workspace_bytes(1))
@@ -211,7 +201,7 @@ def nearest(labels_u8: torch.Tensor, sites, max_distance: Optional[float] = None
     s = _value_set(what, 'sites', sites)
     d2max = _limit(what, max_distance, max_d2)
     a = _frames(what, labels_u8)
-    _geometry(what, a)
+    geometry(what, a)
     index = torch.empty(a.shape, dtype=torch.int32, device=a.device)
     dist2 = torch.empty(a.shape, dtype=torch.int32, device=a.device) if return_distance else None
     _nearest(a, s, None, d2max, index, dist2, None, torch.cuda.current_stream(a.device))
@@ -233,15 +223,12 @@ def grow(labels_u8: torch.Tensor, fill=(0,), sites=None, max_distance: Optional[
     s = frozenset(range(256)) - f if sites is None else _value_set(what, 'sites', sites)
     d2max = _limit(what, max_distance, max_d2)
     a = _frames(what, labels_u8)
-    _geometry(what, a)
+    geometry(what, a)
     if out is None:
         taken = torch.empty(a.shape, dtype=torch.uint8, device=a.device)
     else:
-        if (not isinstance(out, torch.Tensor) or out.dtype != torch.uint8 or out.device != a.device or out.shape != labels_u8.shape
-                or not out.is_contiguous()):
-            raise RmemError(f'{what}: out must be a contiguous uint8 tensor of the labels\' shape on their device')
+        taken = like_labels(what, out, 'out', torch.uint8, labels_u8, a)
         if out.data_ptr() == a.data_ptr():
             raise RmemError(f'{what}: out must not be the labels (they are read at the nearest site while out is written)')
-        taken = out.view(a.shape)
     _nearest(a, s, f, d2max, None, None, taken, torch.cuda.current_stream(a.device))
     return taken.view(labels_u8.shape) if out is None else out

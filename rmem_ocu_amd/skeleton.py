@@ -17,7 +17,7 @@ import torch
 
 from . import _lib
 from ._codec import workspace
-from ._labels import frames_per_pass, is_int, stack as _frames
+from ._labels import frames_per_pass, is_int, like_labels, stack as _frames
 from ._lib import RmemError
 
 # (dy, dx) of the neighbours x1..x8: E, NE, N, NW, W, SW, S, SE (y grows downward)
@@ -68,10 +68,7 @@ def thin(labels_u8: torch.Tensor, max_iterations: Optional[int] = None, batch: i
     if out is None:
         res = torch.empty_like(a)
     else:
-        if (not isinstance(out, torch.Tensor) or out.dtype != torch.uint8 or out.device != a.device or out.shape != labels_u8.shape
-                or not out.is_contiguous()):
-            raise RmemError(f'{what}: out must be a contiguous uint8 tensor of the labels\' shape on their device')
-        res = out.view(a.shape)
+        res = like_labels(what, out, 'out', torch.uint8, labels_u8, a)
     L = _lib.lib()
     per_frame = int(L.rmem_label_thin_workspace_bytes(1, H, W))
     k = frames_per_pass(what, n, per_frame, workspace_bytes, 'one frame\'s need')[1]

@@ -19,9 +19,9 @@ import torch
 
 from . import _lib
 from ._codec import workspace
-from ._labels import frames_per_pass, int_in, stack as _frames, stack_pair
+from ._labels import MAX_SIDE, frames_per_pass, geometry, int_in, like_labels, stack as _frames, stack_pair
 from ._lib import RmemError
-from .distance import MAX_SIDE, SENTINEL, _geometry
+from .distance import SENTINEL
 
 FIELDS = ('count', 'sum_fix', 'max', 'lo', 'hi', 'within0', 'within1', 'within2', 'within3')
 MAX_TOL2 = 2 ** 30 - 1
@@ -51,7 +51,7 @@ def label_surface(labels_u8: torch.Tensor) -> torch.Tensor:
     One launch on the current stream, no host sync."""
     what = 'surface.label_surface'
     a = _frames(what, labels_u8)
-    _geometry(what, a)
+    geometry(what, a)
     out = torch.empty_like(a)
     stream = torch.cuda.current_stream(a.device)
     _surface(a, out, stream)
@@ -70,10 +70,8 @@ def edt_at(labels_u8: torch.Tensor, keys_u8: torch.Tensor, value: int, key: int,
     a, b = stack_pair(what, labels_u8, keys_u8, ('labels', 'keys'))
     for t in (a, b):
         _frames(what, t)
-    n, H, W = _geometry(what, a)
-    if (not isinstance(samples, torch.Tensor) or samples.dtype != torch.int32 or samples.device != a.device
-            or samples.shape != labels_u8.shape or not samples.is_contiguous()):
-        raise RmemError(f'{what}: samples must be a contiguous int32 tensor of the labels\' shape on their device')
+    n, H, W = geometry(what, a)
+    like_labels(what, samples, 'samples', torch.int32, labels_u8, a)
     stream = torch.cuda.current_stream(a.device)
     g = workspace('edt', a.device, stream, int(_lib.lib().rmem_label_edt_workspace_bytes(n, H, W)))
     _edt_at(a, b, v, k, samples, g, stream)
@@ -105,7 +103,7 @@ def surface_census(a_u8: torch.Tensor, b_u8: torch.Tensor, num_objs: int, tol2: 
     a, b = stack_pair(what, a_u8, b_u8)
     for t in (a, b):
         _frames(what, t)
-    n, H, W = _geometry(what, a)
+    n, H, W = geometry(what, a)
     L = _lib.lib()
     HW = H * W
     c1, g1 = int(L.rmem_surface_census_workspace_bytes(1, K)), int(L.rmem_label_edt_workspace_bytes(1, H, W))

@@ -1,8 +1,9 @@
 """The distance transform of label stacks on the MI355X against tests/edt_ref.py: exact integer equality everywhere, no tolerance.
 The stack sits between guard bytes and starts at any byte, outputs and workspace are dirtied first and followed by guard ints.  The
 shapes are the smallest that can go wrong: one pixel, one row, one column, rows longer than a workgroup's stride and columns taller
-than any band, and the two 16384-long lines with a single site at index 0 (the largest distances, a full row image in LDS, a scan
-as long as the row).  Content and references are computed once per case and shared."""
+than any band, rows that end on, one before and one after the end of a 32-pixel segment of the row pass (EDGES, also run by
+test_hip_nearest and test_hip_surface), and the two 16384-long lines with a single site at index 0 (the largest distances, a
+full row image in LDS, a scan as long as the row).  Content and references are computed once per case and shared."""
 import functools
 
 import numpy as np
@@ -19,6 +20,7 @@ CANARY = 0xA5
 CANARY32 = int(np.array([0xA5A5A5A5], dtype=np.uint32).view(np.int32)[0])
 OFFSETS = (0, 1, 3, 13)
 SHAPES = [(1, 1, 1), (1, 1, 17), (1, 17, 1), (2, 3, 5), (3, 17, 33), (2, 37, 131), (1, 40, 1100), (1, 1100, 40), (1, 150, 200)]
+EDGES = [(2, 3, W) for W in (31, 32, 33, 63, 64, 65)]               # a row that ends on, one before and one after a segment's end
 LINES = [(1, 1, 16384), (1, 16384, 1)]
 CONTENTS = ['one', 'blobs', 'noise', 'dots', 'corner', 'rim', 'hstripes', 'vstripes', 'last', 'absent']
 MODES = [(None, False), (None, True), (0, False), (3, False), (255, False)]          # (value, border)
@@ -141,7 +143,7 @@ def _run_peaks(dev, d2, keys, offset=0):
 
 
 @pytest.mark.parametrize('content', CONTENTS)
-@pytest.mark.parametrize('shape', SHAPES, ids=lambda s: 'x'.join(map(str, s)))
+@pytest.mark.parametrize('shape', SHAPES + EDGES, ids=lambda s: 'x'.join(map(str, s)))
 def test_transform(dev, shape, content):
     """both modes, both borders, the values 0, 3 and 255, the stack starting at a byte offset that changes from mode to mode"""
     a = _content(shape, content)

@@ -22,6 +22,7 @@ CANARY = 0xA5
 CANARY32 = int(np.array([0xA5A5A5A5], dtype=np.uint32).view(np.int32)[0])
 OFFSETS = (0, 1, 3, 13)
 SHAPES = [(1, 1, 1), (1, 1, 17), (1, 17, 1), (2, 3, 5), (3, 17, 33), (2, 37, 131), (1, 40, 1100), (1, 1100, 40), (1, 150, 200)]
+EDGES = [(2, 3, W) for W in (31, 32, 33, 63, 64, 65)]               # a row that ends on, one before and one after a segment's end
 LINES = [(1, 1, 16384), (1, 16384, 1)]
 CONTENTS = ['one', 'blobs', 'noise', 'dots', 'corner', 'rim', 'hstripes', 'vstripes', 'last', 'absent']
 SITE_SETS = [(3,), (1, 2, 3), (0,), (255,), ()]
@@ -149,7 +150,7 @@ def _where(got, want):
 
 
 @pytest.mark.parametrize('content', CONTENTS)
-@pytest.mark.parametrize('shape', SHAPES, ids=lambda s: 'x'.join(map(str, s)))
+@pytest.mark.parametrize('shape', SHAPES + EDGES, ids=lambda s: 'x'.join(map(str, s)))
 def test_transform(dev, shape, content):
     """every site set and every limit, all three outputs; the fill set and the byte offset of the stack change from set to set"""
     a = _content(shape, content)

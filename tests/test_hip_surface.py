@@ -12,7 +12,7 @@ import torch
 
 import census_ref
 import surface_ref as R
-from test_hip_edt import CANARY, CANARY32, OFFSETS, _content, _dirty, _guarded, _guards_intact, _moved, _tail_intact
+from test_hip_edt import CANARY, CANARY32, EDGES, OFFSETS, _content, _dirty, _guarded, _guards_intact, _moved, _tail_intact
 
 pytestmark = pytest.mark.gpu
 
@@ -99,7 +99,7 @@ def _full(shape, content, value):
 
 
 @pytest.mark.parametrize('content', CONTENTS)
-@pytest.mark.parametrize('shape', SHAPES, **IDS)
+@pytest.mark.parametrize('shape', SHAPES + EDGES, **IDS)
 def test_edt_at(dev, shape, content):
     """keys in the stack itself and in another one; a key and a value that no pixel holds"""
     a = _content(shape, content)
