@@ -3,6 +3,7 @@
 #include "../../include/rmem.h"
 #include <string.h>
 #include <stdio.h>
+#include <stdlib.h>
 #include <atomic>
 #include <mutex>
 #include <vector>
@@ -21,6 +22,11 @@ int rmem_check_launch(const char* what) {
   snprintf(buf, sizeof(buf), "%s: %s", what, hipGetErrorString(e));
   rmem_set_error(buf);
   return -2;
+}
+
+int rmem_env_int(const char* name, int dflt) {
+  const char* v = getenv(name);
+  return v ? atoi(v) : dflt;
 }
 
 extern "C" int rmem_abi_version(void) { return RMEM_ABI_VERSION; }

@@ -20,28 +20,13 @@
 // Everything a workgroup needs from memory is requested before it computes anything: both operand panels, the first W1' panels
 // and (into registers) its 64 x 256 shortcut tile -- ~90 KB in flight per workgroup, which is what an HBM-bound kernel wants.
 #include "common.h"
+#include "lds_dma.h"
 #include "../../include/rmem.h"
 #include <stdlib.h>
 
 namespace {
 
-typedef __attribute__((address_space(3))) void* lptr_t;
-#if defined(__HIP_DEVICE_COMPILE__)
-typedef __amdgpu_buffer_rsrc_t rsrc_t;
-__device__ __forceinline__ rsrc_t make_rsrc(const void* base, long bytes) {
-  return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), 0, (int)bytes, 0x00020000);
-}
-__device__ __forceinline__ void buf_load_lds16(rsrc_t r, lptr_t dst, int voff, int soff) {
-  __builtin_amdgcn_raw_ptr_buffer_load_lds(r, dst, 16, voff, soff, 0, 0);
-}
-#else
-struct rsrc_t {};
-__device__ inline rsrc_t make_rsrc(const void*, long) { return {}; }
-__device__ inline void buf_load_lds16(rsrc_t, lptr_t, int, int) {}
-#endif
-
 constexpr int BM = 64, N1 = 256, BK = 64;
-constexpr int OOB = (int)0x80000000;
 constexpr int R1_BYTES = N1 * BK * 2, CP = 132, R2_BYTES = 16 * CP * 4, R3_BYTES = 32768;
 static_assert(R2_BYTES >= BM * BK * 2, "the A panel shares the staging region");
 constexpr int LDS_BYTES = R1_BYTES + R2_BYTES + R3_BYTES;
@@ -53,9 +38,6 @@ struct BnParams {
   int Ho, Wo, HoWo, H2, W2, Cin2, stride2;
   long b_bytes, x2_bytes;
 };
-
-// element index of (row, 16-byte chunk) in a [rows][64] e16 panel: the chunk is XOR-swizzled with (row >> 1) & 7 (gemm_conv.hip)
-__device__ __forceinline__ int swz(int row, int chunk) { return row * 64 + ((chunk ^ ((row >> 1) & 7)) << 3); }
 
 template <int N2, bool DUAL>
 __global__ __launch_bounds__(256) void k_bneck_chain(BnParams p) {

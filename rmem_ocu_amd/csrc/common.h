@@ -130,6 +130,9 @@ __device__ __forceinline__ float rmem_bilerp(float a, float b, float c, float d,
 // error plumbing shared by the C-ABI translation units (api.hip owns the storage)
 extern "C" void rmem_set_error(const char* msg);
 int rmem_check_launch(const char* what);
+// integer environment knob (api.hip): atoi of the variable when it is set, else dflt.  It reads the environment on every call: a
+// caller that wants a knob read once per process keeps the result in a static const.
+int rmem_env_int(const char* name, int dflt);
 // opt-in launch timers (api.hip): channel 0 = memory-read attention, 1 = gated attention's value GEMM.  begin() returns a slot
 // (>= 0) after recording the start event on the stream, or -1 when the channel is off, full, or the stream is being captured.
 enum { RMEM_PROF_MEM_READ = 0, RMEM_PROF_GATED_PV = 1 };

@@ -14,31 +14,16 @@
 // (tests/test_hip_ops.py::test_conv3x3_direct).  256 threads = 2 (channel halves) x 2 (pixel halves) waves, the next input row in flight
 // behind a counted vmcnt, one shared object and raw barriers (see stem.hip for why).
 #include "common.h"
+#include "lds_dma.h"
 #include "../../include/rmem.h"
 #include <stdlib.h>
 
 namespace {
 
-typedef __attribute__((address_space(3))) void* lptr_t;
-#if defined(__HIP_DEVICE_COMPILE__)
-typedef __amdgpu_buffer_rsrc_t rsrc_t;
-__device__ __forceinline__ rsrc_t make_rsrc(const void* base, long bytes) {
-  return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), 0, (int)bytes, 0x00020000);
-}
-__device__ __forceinline__ void buf_load_lds16(rsrc_t r, lptr_t dst, int voff, int soff) {
-  __builtin_amdgcn_raw_ptr_buffer_load_lds(r, dst, 16, voff, soff, 0, 0);
-}
-#else
-struct rsrc_t {};
-__device__ inline rsrc_t make_rsrc(const void*, long) { return {}; }
-__device__ inline void buf_load_lds16(rsrc_t, lptr_t, int, int) {}
-#endif
-
 constexpr int TP = 64;                          // output pixels a tile computes (one piece of an output row) ...
 constexpr int TPV = 62;                         // ... of which it delivers 62: the input row piece is then 64 pixels = exactly 2 LDS-DMA
 constexpr int PWP = 64;                         // instructions per thread, and a ring slot has no dead bytes
 constexpr int NSLOT = 8, DEPTH = NSLOT - 3;     // three rows in use, five in flight
-constexpr int OOB = (int)0x80000000;
 
 struct C3Params {
   const e16* x; const e16* w; const float* bias; e16* y;
@@ -198,8 +183,8 @@ extern "C" int RMEM_API(rmem_conv3x3_direct)(const void* x, int images, int H, i
   RMEM_REQUIRE(p.x_bytes + (long)(W + TP + 2) * C * 2 < (1L << 31) - (1L << 22), "rmem_conv3x3_direct: the input exceeds the 2 GB a buffer descriptor addresses");
   // runs of output rows per column strip: enough workgroups for two (C = 64) / one (C = 128) per CU, rows per run as long as that allows
   // (every run re-reads 2 rows and re-loads the weights)
-  static const int wgs64 = getenv("RMEM_CONV3_WGS") ? atoi(getenv("RMEM_CONV3_WGS")) : 512;
-  static const int wgs128 = getenv("RMEM_CONV3_WGS128") ? atoi(getenv("RMEM_CONV3_WGS128")) : 256;
+  static const int wgs64 = rmem_env_int("RMEM_CONV3_WGS", 512);
+  static const int wgs128 = rmem_env_int("RMEM_CONV3_WGS128", 256);
   const int wgs = C == 64 ? wgs64 : wgs128;
   const long strips = (long)images * p.tiles_x;
   long nruns = (wgs + strips - 1) / strips;

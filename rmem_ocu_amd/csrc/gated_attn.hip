@@ -821,7 +821,7 @@ void launch_all(GpParams& p, const GpPlan& g, GpCombine& c, bool timed, double f
   // half flavour keeps the exact two passes (as its memory read always takes the SAFE pass, attention.hip)
   static const bool sample = false;
 #else
-  static const bool sample = !(getenv("RMEM_GP_SAMPLE") && atoi(getenv("RMEM_GP_SAMPLE")) == 0);
+  static const bool sample = rmem_env_int("RMEM_GP_SAMPLE", 1) != 0;
 #endif
   unsigned* flag = reinterpret_cast<unsigned*>(reinterpret_cast<char*>(p.mpart) + g.total - 256);
   if (sample) {
@@ -840,7 +840,7 @@ void launch_all(GpParams& p, const GpPlan& g, GpCombine& c, bool timed, double f
   const int slot = timed ? rmem_prof_begin(RMEM_PROF_GATED_PV, s, flops) : -1;      // rmem_gated_profile_start: bench.py's DeAOT roofline leg
   // loader waves + MFMA waves (default; RMEM_GP_PC=0: every wave does both).  Measured at cfg 2, T = 9, 8 clips per launch: 610 -> 479 us
   // per launch (671 -> 858 TFLOP/s), the DeAOT workload 1670 -> 1735 frames/s; same MFMA order, so the outputs are bit-identical
-  static const bool pc = !(getenv("RMEM_GP_PC") && atoi(getenv("RMEM_GP_PC")) == 0);
+  static const bool pc = rmem_env_int("RMEM_GP_PC", 1) != 0;
   if (slot >= 0) {
     if (pc) hipLaunchKernelGGL((k_gp_pv<PM, true, true>), pg, dim3(512), 0, s, p);
     else hipLaunchKernelGGL((k_gp_pv<PM, true>), pg, dim3(256), 0, s, p);
@@ -912,7 +912,7 @@ extern "C" int RMEM_API(rmem_gated_attn_clips)(const void* q, int ldq, const voi
   p.mpart = (float*)ws; p.lpart = (float*)(ws + g.off_l); p.P = (e16*)(ws + g.off_p); p.slabs = (float*)(ws + g.off_s);
   p.qscale = LOG2E / sqrtf((float)DQ);
   p.DV = DV; p.nq = g.Lqp / QT; p.ncs = DV / CW; p.groups = g.groups; p.rows_per_group = g.rpg;
-  { static const int dbg = getenv("RMEM_GP_DEBUG") ? atoi(getenv("RMEM_GP_DEBUG")) : 0; p.debug = dbg; }
+  { static const int dbg = rmem_env_int("RMEM_GP_DEBUG", 0); p.debug = dbg; }
   GpCombine c = {};
   c.slabs = p.slabs; c.groups = g.groups; c.lpart = p.lpart; c.nrows = nrows; c.Lq = Lq; c.Lqp = g.Lqp; c.DV = DV;
   c.ua = (const e16*)u_a; c.ldua = ldua; c.ub = (const e16*)u_b; c.ldub = ldub; c.usplit = usplit;
@@ -950,7 +950,7 @@ extern "C" int RMEM_API(rmem_local_gated_attn_clips)(const void* q, int ldq, con
   // key ranges (= score workgroups per query tile and clip): 8 for a single clip; with several clips per launch the grid is full
   // anyway and a workgroup's fixed prologue (Q fragments, window coordinates) is spread over more key tiles
   // (8 clips, cfg 2: 8 -> 4 ranges, DeAOT workload 1757 -> 1782 frames/s)
-  static const int rows_env = getenv("RMEM_GP_LOCAL_ROWS") ? atoi(getenv("RMEM_GP_LOCAL_ROWS")) : 0;      // kernel experiments only
+  static const int rows_env = rmem_env_int("RMEM_GP_LOCAL_ROWS", 0);      // kernel experiments only
   const int tiles_q = ((L + QT - 1) / QT) * nclips;
   const int want = rows_env > 0 ? rows_env : max(2, min(8, (448 + tiles_q - 1) / tiles_q));
   p.per = ((L + want - 1) / want + KT - 1) / KT * KT;
@@ -964,7 +964,7 @@ extern "C" int RMEM_API(rmem_local_gated_attn_clips)(const void* q, int ldq, con
   p.qscale = LOG2E / sqrtf((float)DQ);
   p.H = H; p.W = W; p.rel = rel; p.ldrel = ldrel;
   p.DV = DV; p.nq = g.Lqp / QT; p.ncs = DV / CW; p.groups = g.groups; p.rows_per_group = g.rpg;
-  { static const int dbg = getenv("RMEM_GP_DEBUG") ? atoi(getenv("RMEM_GP_DEBUG")) : 0; p.debug = dbg; }
+  { static const int dbg = rmem_env_int("RMEM_GP_DEBUG", 0); p.debug = dbg; }
   GpCombine c = {};
   c.slabs = p.slabs; c.groups = g.groups; c.lpart = p.lpart; c.nrows = p.nrows; c.Lq = L; c.Lqp = g.Lqp; c.DV = DV;
   c.ua = (const e16*)u_a; c.ldua = ldua; c.ub = (const e16*)u_b; c.ldub = ldub; c.usplit = usplit;

@@ -40,6 +40,7 @@
 // pure host function of the geometry, the entry point and the four knobs of GemmKnobs; launch() turns a plan into the
 // launch, and rmem_conv_plan() shows the plan to the host (tests/test_gemm_plan_host.py checks it without a GPU).
 #include "common.h"
+#include "lds_dma.h"
 #include "../../include/rmem.h"
 #include <stdlib.h>
 
@@ -87,11 +88,6 @@ __device__ __forceinline__ bool tile_of_block(const ConvParams& p, int BM, int& 
   by = j - xl * p.xcd_ny;
   return bx * BM < p.M;
 }
-
-// LDS tile rows are 128 B (BK = 64 e16 = 8 chunks of 16 B).  Physical chunk = chunk ^ ((row >> 1) & 7): the 16 lanes of
-// every ds_read_b128 lane group (rows r..r+3, r+12..r+15 at chunk c and rows r+4..r+11 at chunk c+1) then land on 16
-// distinct 16-byte slots of the 256-byte bank row.
-__device__ __forceinline__ int swz(int row, int chunk) { return row * 64 + ((chunk ^ ((row >> 1) & 7)) << 3); }
 
 // finish 8 consecutive channels n..n+7 of output row m (v = accumulator + nothing yet)
 __device__ __forceinline__ void finish8(const ConvParams& p, int m, int n, float (&v)[8]) {
@@ -180,25 +176,6 @@ __device__ __forceinline__ void finish1(const ConvParams& p, int m, int n, float
 // 8 workgroups per CU (see gemm_plan()).
 static __device__ uint4 g_zero16[1];
 
-typedef __attribute__((address_space(1))) const void* gptr_t;
-typedef __attribute__((address_space(3))) void* lptr_t;
-
-// buffer-descriptor LDS-DMA (buffer_load_dwordx4 ... offen lds).  The descriptor type and these builtins exist only in the
-// device pass of hipcc; the host pass just needs the names to parse.
-#if defined(__HIP_DEVICE_COMPILE__)
-typedef __amdgpu_buffer_rsrc_t rsrc_t;
-__device__ __forceinline__ rsrc_t make_rsrc(const void* base, int bytes) {
-  return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), 0, bytes, 0x00020000);
-}
-__device__ __forceinline__ void buf_load_lds16(rsrc_t r, lptr_t dst, int voff, int soff) {
-  __builtin_amdgcn_raw_ptr_buffer_load_lds(r, dst, 16, voff, soff, 0, 0);
-}
-#else
-struct rsrc_t {};
-__device__ inline rsrc_t make_rsrc(const void*, int) { return {}; }
-__device__ inline void buf_load_lds16(rsrc_t, lptr_t, int, int) {}
-#endif
-
 //
 // FAST (Cin % 64 == 0, which every 3x3 / 1x1 layer of the path satisfies): a k-step never leaves one filter tap, so the k-walk
 // (tap, ci) is wave-uniform and lives in SGPRs; each lane keeps ONE 32-bit byte offset per piece plus a bit mask of the taps
@@ -246,7 +223,6 @@ __device__ __forceinline__ void conv_gemm_dma_body(const ConvParams& p, const in
   int b_c[NB];
   long b_base[NB];
   // FAST: per-lane byte offsets (31 bits) and tap masks; wave-uniform k-walk
-  constexpr int OOB = (int)0x80000000;
   int f_aoff[NA], f_boff[NB];
   unsigned f_amask[NA], f_cmask[NA];
   int f_aoff2[NA];
@@ -633,13 +609,12 @@ struct GemmKnobs {
 };
 const GemmKnobs& gemm_knobs() {
   static const GemmKnobs knobs = [] {
-    auto num = [](const char* name, int dflt) { const char* v = getenv(name); return v ? atoi(v) : dflt; };
     GemmKnobs k;
     k.pc = kPcRing;
     if (const char* v = getenv("RMEM_GEMM_PC")) k.pc = (v[0] >= '0' && v[0] <= '3' && v[1] == 0) ? v[0] - '0' : -1;
-    k.fast = num("RMEM_GEMM_FAST", 1) != 0;
-    k.xcd = num("RMEM_GEMM_XCD", 1) != 0;
-    k.debug = num("RMEM_GEMM_DEBUG", 0);
+    k.fast = rmem_env_int("RMEM_GEMM_FAST", 1) != 0;
+    k.xcd = rmem_env_int("RMEM_GEMM_XCD", 1) != 0;
+    k.debug = rmem_env_int("RMEM_GEMM_DEBUG", 0);
     return k;
   }();
   return knobs;

@@ -15,25 +15,11 @@
 // 256 threads = 2 (channel halves) x 2 (position halves of 32) waves; tile = 64 positions x 128 channels, a 3-deep weight ring
 // (measured: 64 channels x 8 stages 113 us against 72 us -- every workgroup builds the one-hot fragments of its positions again).
 #include "common.h"
+#include "lds_dma.h"
 #include "../../include/rmem.h"
 #include <stdlib.h>
 
 namespace {
-
-typedef __attribute__((address_space(3))) void* lptr_t;
-#if defined(__HIP_DEVICE_COMPILE__)
-typedef __amdgpu_buffer_rsrc_t rsrc_t;
-__device__ __forceinline__ rsrc_t make_rsrc(const void* base, long bytes) {
-  return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), 0, (int)bytes, 0x00020000);
-}
-__device__ __forceinline__ void buf_load_lds16(rsrc_t r, lptr_t dst, int voff, int soff) {
-  __builtin_amdgcn_raw_ptr_buffer_load_lds(r, dst, 16, voff, soff, 0, 0);
-}
-#else
-struct rsrc_t {};
-__device__ inline rsrc_t make_rsrc(const void*, long) { return {}; }
-__device__ inline void buf_load_lds16(rsrc_t, lptr_t, int, int) {}
-#endif
 
 #ifndef RMEM_IDB_TCH
 #define RMEM_IDB_TCH 128
@@ -52,8 +38,6 @@ struct IdParams {
   const e16* w; const float* bias; e16* out;
   int images, Hpd, Wpd, Ho, Wo, KH, KW, stride, ncls, M, K, nk;
 };
-
-__device__ __forceinline__ int swz(int row, int chunk) { return row * 64 + ((chunk ^ ((row >> 1) & 7)) << 3); }
 
 // the 8-element one-hot fragment of label L for channel half `half` (channels 8 half .. + 7): 1.0 at element L & 7, or zeros
 __device__ __forceinline__ e16x8 onehot_frag(int L, int half, int ncls) {

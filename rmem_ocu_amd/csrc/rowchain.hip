@@ -27,6 +27,7 @@
 // one B fragment, no LDS, no barrier, no address arithmetic; a ring of 4 k-chunks (16 KiB per workgroup) stays in flight.
 // All workgroups read the same weights (128 KiB - 512 KiB per matrix): they are L2 hits after the first workgroup of an XCD.
 #include "common.h"
+#include "lds_dma.h"
 #include "../../include/rmem.h"
 
 namespace {
@@ -43,9 +44,6 @@ constexpr int BM = 32;            // rows per workgroup
 constexpr int XS = 260;           // fp32 staging row stride (floats): 4 rows apart = 16 banks apart, conflict-free ds_write_b32
 constexpr int PANEL = BM * 64;    // elements of one [32 rows][64 k] A panel (128-byte rows, XOR-swizzled 16-byte chunks)
 constexpr int PF = 16 / JT;       // k-chunks (of 32) of B fragments in flight per wave (64 registers; PF <= 8 = the k-chunks of the shortest K)
-constexpr int OOB = (int)0x80000000;   // byte offset beyond every buffer: the hardware range check drops the store
-
-__device__ __forceinline__ int swz(int row, int chunk) { return row * 64 + ((chunk ^ ((row >> 1) & 7)) << 3); }
 
 __device__ __forceinline__ f32x4 ld4(const float* p) { return *reinterpret_cast<const f32x4*>(p); }
 __device__ __forceinline__ e16x4 cvt4(f32x4 v) { return e16x4{(e16)v[0], (e16)v[1], (e16)v[2], (e16)v[3]}; }
@@ -57,15 +55,9 @@ __device__ __forceinline__ f32x4 up4(e16x4 v) { return f32x4{(float)v[0], (float
 typedef __attribute__((ext_vector_type(2))) unsigned u32x2;
 typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
 #if defined(__HIP_DEVICE_COMPILE__)
-typedef __amdgpu_buffer_rsrc_t rsrc_t;
-__device__ __forceinline__ rsrc_t make_rsrc(const void* base, long bytes) {
-  return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), 0, (int)bytes, 0x00020000);
-}
 __device__ __forceinline__ void st8(rsrc_t r, int off, e16x4 v) { __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, v), r, off, 0, 0); }
 __device__ __forceinline__ void st16(rsrc_t r, int off, f32x4 v) { __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), r, off, 0, 0); }
 #else
-struct rsrc_t {};
-__device__ inline rsrc_t make_rsrc(const void*, long) { return {}; }
 __device__ inline void st8(rsrc_t, int, e16x4) {}
 __device__ inline void st16(rsrc_t, int, f32x4) {}
 #endif

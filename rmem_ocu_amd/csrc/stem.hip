@@ -16,25 +16,11 @@
 // 256 threads = 2 (channel halves) x 2 (pixel halves) waves; the patch is double-buffered across tiles so that the next tile's
 // copy is in flight behind the MFMAs and the stores of the current one (counted vmcnt: stores count too on CDNA4).
 #include "common.h"
+#include "lds_dma.h"
 #include "../../include/rmem.h"
 #include <stdlib.h>
 
 namespace {
-
-typedef __attribute__((address_space(3))) void* lptr_t;
-#if defined(__HIP_DEVICE_COMPILE__)
-typedef __amdgpu_buffer_rsrc_t rsrc_t;
-__device__ __forceinline__ rsrc_t make_rsrc(const void* base, long bytes) {
-  return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), 0, (int)bytes, 0x00020000);
-}
-__device__ __forceinline__ void buf_load_lds16(rsrc_t r, lptr_t dst, int voff, int soff) {
-  __builtin_amdgcn_raw_ptr_buffer_load_lds(r, dst, 16, voff, soff, 0, 0);
-}
-#else
-struct rsrc_t {};
-__device__ inline rsrc_t make_rsrc(const void*, long) { return {}; }
-__device__ inline void buf_load_lds16(rsrc_t, lptr_t, int, int) {}
-#endif
 
 constexpr int TP = 64;                          // output pixels per tile
 constexpr int PW = 2 * TP + 8;                  // patch width in pixels (2 * 63 + 8 = 134, rounded to a multiple of 4 pixels)
@@ -43,7 +29,6 @@ constexpr int PCHUNKS = 8 * PROW / 16;          // 16-byte pieces per patch (8 i
 constexpr int NDMA = (PCHUNKS + 255) / 256;     // LDS-DMA instructions per thread and patch
 constexpr int PATCH_BYTES = NDMA * 256 * 16;    // (the last instruction's surplus lanes read out of range: zero fill, never used)
 constexpr int SROW = 144;                       // staging row: 64 channels x 2 B + 16 B (conflict-free 8-byte writes, aligned 16-byte reads)
-constexpr int OOB = (int)0x80000000;
 
 struct StemParams {
   const e16* x; const e16* w; const float* bias; e16* y;
@@ -334,7 +319,7 @@ extern "C" int RMEM_API(rmem_stem7x7s2_pool)(const void* x_padded, int images, i
   p.strips = (p.WP + SP_PV - 1) / SP_PV;
   p.x_bytes = (long)images * p.Hp * p.Wp * 8;
   RMEM_REQUIRE(p.x_bytes < (1L << 31) - (1L << 22), "rmem_stem7x7s2_pool: the padded frames exceed the 2 GB a buffer descriptor addresses");
-  static const int wgs = getenv("RMEM_STEM_POOL_WGS") ? atoi(getenv("RMEM_STEM_POOL_WGS")) : 1024;     // 91.5 us at 640, 81 at 1024, 88 at 2048 (16 frames)
+  static const int wgs = rmem_env_int("RMEM_STEM_POOL_WGS", 1024);     // 91.5 us at 640, 81 at 1024, 88 at 2048 (16 frames)
   const long cols = (long)images * p.strips;
   long nruns = (wgs + cols - 1) / cols;
   if (nruns < 1) nruns = 1;
@@ -359,7 +344,7 @@ extern "C" int RMEM_API(rmem_stem7x7s2)(const void* x_padded, int images, int H,
   p.x_bytes = (long)images * p.Hp * p.Wp * 8;
   RMEM_REQUIRE(p.x_bytes < (1L << 31) - (1L << 22) && nt < (1L << 30), "rmem_stem7x7s2: the padded frames exceed the 2 GB a buffer descriptor addresses");
   p.ntiles = (int)nt;
-  static const int wgs = getenv("RMEM_STEM_WGS") ? atoi(getenv("RMEM_STEM_WGS")) : 1024;      // persistent workgroups (4 per CU)
+  static const int wgs = rmem_env_int("RMEM_STEM_WGS", 1024);      // persistent workgroups (4 per CU)
   const unsigned grid = (unsigned)(nt < wgs ? nt : wgs);
   hipLaunchKernelGGL(k_stem7x7s2, dim3(grid), dim3(256), 0, (hipStream_t)stream, p);
   return rmem_check_launch("rmem_stem7x7s2");
