@@ -185,6 +185,25 @@ int rmem_lstt_attn_pair_clips(const void* q, int ldq, const void* k_bank, const 
                               const void* k_short, const void* v_short, int lk_short, long long kv_short_clip_stride,
                               void* out_short, long long out_short_clip_stride, void* workspace, void* stream);
 
+/* The same launch with the merge of the key groups DEFERRED to the consumer of out_long.  At bench geometry the memory read
+ * splits the keys into several groups (RMEM_ATTN_WGS) whose normalised partial outputs and (m, l) pairs a row-local pass then
+ * merges into out_long; this form does not launch that pass when there is more than one group and fills *merge with what the
+ * merge needs, for rmem_lstt_chain_b_merged to do it while it stages its rows (out_long is then neither written nor read).
+ * With one group nothing changes: out_long is final and merge->ngroups = 1.  The mass output is as in the plain form. */
+typedef struct rmem_attn_merge {
+  int ngroups, heads, Lq, reserved;   /* key groups (<= 1: nothing was deferred), heads, queries per clip */
+  const void* opart;                  /* partial outputs, normalised by their own sum: 16-bit [clip][group][head][8][Lq][4] */
+  const float* mlg;                   /* (reference maximum, sum) of every partial: fp32 [clip][group][head][Lq][2] */
+  long long opart_cs, mlg_cs;         /* clip strides of the two, in 4-byte units */
+} rmem_attn_merge;
+int rmem_lstt_attn_pair_clips_deferred(const void* q, int ldq, const void* k_bank, const void* v_bank, long long slot_stride, int ldkv,
+                                       const rmem_attn_chunk* chunks, int nchunks, int lk_total, const float* pe_cur, const float* pe_mem,
+                                       int Lq, int heads, void* out_long, int ldo, float* attn_mass, int T, int nclips,
+                                       long long q_clip_stride, long long out_clip_stride,
+                                       const void* k_short, const void* v_short, int lk_short, long long kv_short_clip_stride,
+                                       void* out_short, long long out_short_clip_stride, void* workspace,
+                                       rmem_attn_merge* merge, void* stream);
+
 /* Optional timing of the memory-read launches (chunks != NULL) with HIP events on the launch stream:
  * between start and stop every such launch outside a graph capture is bracketed by two events;
  * start() also calibrates what an event bracket costs around an empty kernel and stop() subtracts that per launch;
@@ -210,8 +229,8 @@ int rmem_layernorm256_pair(const void* a0, const void* b0, void* y0, const void*
 /* ------------------------------------------------------------------ LSTT block chains (row-local sequences as ONE launch)
  * Between its three attentions an LSTT block (layers/transformer.py:553-692) is a sequence of row-local operations on the
  * [tokens][256] residual stream.  Each entry point below runs one such sequence for all rows of `clips` clips of L tokens
- * (rows are [clip][token], everything contiguous unless a leading dimension is given), a workgroup owning 32 consecutive
- * tokens of one clip with the rows resident in LDS; results are bit-identical to the same sequence of rmem_conv2d_nhwc /
+ * (rows are [clip][token], everything contiguous unless a leading dimension is given), a workgroup owning 32 or 64 consecutive
+ * tokens of one clip (rmem_lstt_chain_rows) with the rows resident in LDS; results do not depend on that choice and are bit-identical to the same sequence of rmem_conv2d_nhwc /
  * rmem_layernorm256 / rmem_layernorm256_pair launches (same accumulation order, same points of rounding).
  * Weights are 16-bit [N][K] matrices (nn.Linear layout) re-packed once in FRAGMENT ORDER for NW = rmem_lstt_chain_waves()
  * waves per workgroup: [N / 256][NW][K / 32][16 / NW][64][8] = [column block][wave][k chunk][column tile j][lane][8 consecutive k],
@@ -223,6 +242,10 @@ int rmem_layernorm256_pair(const void* a0, const void* b0, void* y0, const void*
  *   x += att . w_proj^T + b_proj;  curr_v = LN2(x);  curr_q = curr_v . w_q^T + b_q;
  *   k4 = LN4(short_k + curr_q);  v4 = LN4(short_v + curr_v) */
 int rmem_lstt_chain_waves(void);      /* waves per workgroup the chain kernels were built for (4 or 8): the weight packing depends on it */
+/* Rows per workgroup a chain launch over `clips` clips of L tokens takes on a device with `cus` compute units: 64 when the
+ * 32-row grid, ceil(L / 32) * clips workgroups of one per CU, would need more than one round, else 32.  A pure function; the
+ * launches apply it to the current device unless the environment sets RMEM_CHAIN_ROWS = 32 | 64 (read per call). */
+int rmem_lstt_chain_rows(int L, int clips, int cus);
 typedef struct rmem_chain_a_desc {
   int L, clips; float eps; int reserved;
   const void* att; float* x;
@@ -234,8 +257,8 @@ int rmem_lstt_chain_a(const rmem_chain_a_desc* d, void* stream);
 
 /* chain B, after the long-term and the short-term attention (transformer.py:635, 662, 673-685):
  *   x += att_long . w_long^T + b_long;  tgt3 = att_short . w_short^T + b_short;  x += tgt3;  h1 = LN3(x) . w1^T + b1   ([rows][1024])
- * gn_partial (optional): per-row-block (sum, sum of squares) of h1 over each of the 32 GroupNorm groups of 32 channels,
- * fp32 [clips][32][gn_splits][2], entry `split` = the row block (gn_splits >= ceil(L / 32); the caller keeps the unused
+ * gn_partial (optional): per-32-row-block (sum, sum of squares) of h1 over each of the 32 GroupNorm groups of 32 channels,
+ * fp32 [clips][32][gn_splits][2], entry `split` = the 32-row block whatever the workgroup's height (gn_splits >= ceil(L / 32); the caller keeps the unused
  * entries zero): with gn_splits = 64 the statistics rmem_gn_act_dwconv5x5_prestats_nhwc_images consumes (layers/basic.py:27-35). */
 typedef struct rmem_chain_b_desc {
   int L, clips; float eps; int gn_splits;
@@ -244,6 +267,12 @@ typedef struct rmem_chain_b_desc {
   const float* ln3_g; const float* ln3_b; const void* w1; const float* b1; void* h1; float* gn_partial;
 } rmem_chain_b_desc;
 int rmem_lstt_chain_b(const rmem_chain_b_desc* d, void* stream);
+/* chain B behind rmem_lstt_attn_pair_clips_deferred: with merge->ngroups > 1 the rows of att_long are not read from d->att_long
+ * but merged from the memory read's key groups while they are staged, per (row, head, 4 channels) exactly the merge pass's
+ * sequence (maximum over the groups with l > 0, w = exp2(m - m_max) l, weighted sum in group order, times 1 / sum of w, one
+ * rounding to 16 bits): bit-identical to the merge pass followed by rmem_lstt_chain_b.  merge->ngroups <= 1: rmem_lstt_chain_b.
+ * *merge is read at the call (the deferred launch fills it just before), heads must be 8 and Lq = d->L. */
+int rmem_lstt_chain_b_merged(const rmem_chain_b_desc* d, const rmem_attn_merge* merge, void* stream);
 
 /* chain C, after GroupNorm + GELU + depth-wise 5x5 (transformer.py:685-687, 250-259; 565-569 of the NEXT block):
  *   h3 != NULL:     x += h3 . w2^T + b2  (h3 [rows][1024]);  dec_out[row * ld_dec + 0..255] = LN_dec(x)
@@ -1227,6 +1256,7 @@ int rmem_conv2d_nhwc_f16(const rmem_conv_desc* desc, const void* x, const void* 
 int rmem_mem_read_attn_f16(const void* q, int ldq, const void* k_bank, const void* v_bank, long long slot_stride, int ldkv, const rmem_attn_chunk* chunks, int nchunks, int lk_single, const float* pe_cur, const float* pe_mem, int Lq, int heads, void* out, int ldo, float* attn_mass, int T, void* workspace, void* stream);
 int rmem_mem_read_attn_clips_f16(const void* q, int ldq, const void* k_bank, const void* v_bank, long long slot_stride, int ldkv, const rmem_attn_chunk* chunks, int nchunks, int lk_single, const float* pe_cur, const float* pe_mem, int Lq, int heads, void* out, int ldo, float* attn_mass, int T, int nclips, long long q_clip_stride, long long kv_clip_stride, long long out_clip_stride, void* workspace, void* stream);
 int rmem_lstt_attn_pair_clips_f16(const void* q, int ldq, const void* k_bank, const void* v_bank, long long slot_stride, int ldkv, const rmem_attn_chunk* chunks, int nchunks, int lk_total, const float* pe_cur, const float* pe_mem, int Lq, int heads, void* out_long, int ldo, float* attn_mass, int T, int nclips, long long q_clip_stride, long long out_clip_stride, const void* k_short, const void* v_short, int lk_short, long long kv_short_clip_stride, void* out_short, long long out_short_clip_stride, void* workspace, void* stream);
+int rmem_lstt_attn_pair_clips_deferred_f16(const void* q, int ldq, const void* k_bank, const void* v_bank, long long slot_stride, int ldkv, const rmem_attn_chunk* chunks, int nchunks, int lk_total, const float* pe_cur, const float* pe_mem, int Lq, int heads, void* out_long, int ldo, float* attn_mass, int T, int nclips, long long q_clip_stride, long long out_clip_stride, const void* k_short, const void* v_short, int lk_short, long long kv_short_clip_stride, void* out_short, long long out_short_clip_stride, void* workspace, rmem_attn_merge* merge, void* stream);
 int rmem_layernorm256_f16(const void* a, int a_is_f32, int lda, const void* b, int b_is_f32, int ldb, const float* gamma, const float* beta, float eps, int M, void* y_bf16, int ldy, const float* pos, void* ypos_bf16, int ldyp, float* y_f32, int ldyf, void* stream);
 int rmem_layernorm_f16(const void* a, int a_is_f32, int lda, const float* gamma, const float* beta, float eps, int M, int C, void* y_bf16, int ldy, float* y_f32, int ldyf, void* stream);
 int rmem_patch_merge_ln_f16(const float* x, int H, int W, int C, const float* gamma, const float* beta, float eps, void* y_bf16, void* stream);
@@ -1237,6 +1267,7 @@ int rmem_add16_f16(const void* a, const void* b, void* y, long long n, void* str
 int rmem_add16_grouped_f16(int n, const void* const* a, const void* const* b, void* const* y, long long count, void* stream);
 int rmem_lstt_chain_a_f16(const rmem_chain_a_desc* d, void* stream);
 int rmem_lstt_chain_b_f16(const rmem_chain_b_desc* d, void* stream);
+int rmem_lstt_chain_b_merged_f16(const rmem_chain_b_desc* d, const rmem_attn_merge* merge, void* stream);
 int rmem_lstt_chain_c_f16(const rmem_chain_c_desc* d, void* stream);
 int rmem_layernorm256_pair_f16(const void* a0, const void* b0, void* y0, const void* a1, const void* b1, void* y1, const float* gamma, const float* beta, float eps, int M, void* stream);
 int rmem_bneck_chain_f16(const rmem_bneck_chain_desc* desc, const void* b, const void* x2, const void* w3, const float* bias3, const void* res, void* y, const void* w1, const float* bias1, void* a2, void* stream);

@@ -97,6 +97,11 @@ class LabelRoute(C.Structure):
 ROUTE_LIVE, ROUTE_IDLE, ROUTE_SKIP = 0, 1, 2                           # rmem_label_route.mode
 
 
+class AttnMerge(C.Structure):
+    """rmem_attn_merge: what the deferred-merge memory read hands to chain B (filled by the one call, read by the other)."""
+    _fields_ = [('ngroups', _i), ('heads', _i), ('Lq', _i), ('reserved', _i), ('opart', _vp), ('mlg', _vp), ('opart_cs', _ll), ('mlg_cs', _ll)]
+
+
 def _desc(name, ints, ptrs):
     """ctypes mirror of an rmem_chain_*_desc: (int, int, float, int) header + device pointers, in include/rmem.h's order."""
     return type(name, (C.Structure,), {'_fields_': [(ints[0], _i), (ints[1], _i), ('eps', _f), (ints[2], _i)] + [(n, _vp) for n in ptrs]})
@@ -131,8 +136,10 @@ SIGNATURES = {
     'rmem_add16_grouped': (_i, [_i, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), _ll, _vp]),
     'rmem_layernorm256_pair': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _f, _i, _vp]),
     'rmem_lstt_chain_waves': (_i, []),
+    'rmem_lstt_chain_rows': (_i, [_i, _i, _i]),
     'rmem_lstt_chain_a': (_i, [C.POINTER(ChainA), _vp]),
     'rmem_lstt_chain_b': (_i, [C.POINTER(ChainB), _vp]),
+    'rmem_lstt_chain_b_merged': (_i, [C.POINTER(ChainB), C.POINTER(AttnMerge), _vp]),
     'rmem_lstt_chain_c': (_i, [C.POINTER(ChainC), _vp]),
     'rmem_conv1x1_dual_nhwc': (_i, [C.POINTER(ConvDesc), _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
     'rmem_bneck_chain': (_i, [C.POINTER(BneckChainDesc), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
@@ -148,6 +155,8 @@ SIGNATURES = {
     'rmem_mem_read_attn_clips': (_i, [_vp, _i, _vp, _vp, _ll, _i, _vp, _i, _i, _vp, _vp, _i, _i, _vp, _i, _vp, _i, _i, _ll, _ll, _ll, _vp, _vp]),
     'rmem_lstt_attn_pair_clips': (_i, [_vp, _i, _vp, _vp, _ll, _i, _vp, _i, _i, _vp, _vp, _i, _i, _vp, _i, _vp, _i, _i, _ll, _ll,
                                        _vp, _vp, _i, _ll, _vp, _ll, _vp, _vp]),
+    'rmem_lstt_attn_pair_clips_deferred': (_i, [_vp, _i, _vp, _vp, _ll, _i, _vp, _i, _i, _vp, _vp, _i, _i, _vp, _i, _vp, _i, _i, _ll, _ll,
+                                                _vp, _vp, _i, _ll, _vp, _ll, _vp, C.POINTER(AttnMerge), _vp]),
     'rmem_gn_act_dwconv5x5_nhwc': (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _f, _i, _vp, _vp, _vp, _vp]),
     'rmem_dwconv5x5_nhwc': (_i, [_vp, _vp, _vp, _i, _i, _i, _vp]),
     'rmem_image_to_nhwc8': (_i, [_vp, _vp, _i, _i, _vp]),
@@ -256,8 +265,8 @@ SIGNATURES = {
 }
 
 # entry points with 16-bit operands exist twice: <name> (bfloat16) and <name>_f16 (IEEE half), same signature (include/rmem.h)
-F16_TWINS = ('rmem_conv2d_nhwc', 'rmem_mem_read_attn', 'rmem_mem_read_attn_clips', 'rmem_lstt_attn_pair_clips', 'rmem_layernorm256', 'rmem_layernorm', 'rmem_patch_merge_ln',
-             'rmem_window_attn', 'rmem_window_attn_images', 'rmem_patch_merge_ln_images', 'rmem_add16', 'rmem_add16_grouped', 'rmem_layernorm256_pair', 'rmem_lstt_chain_a', 'rmem_lstt_chain_b', 'rmem_lstt_chain_c', 'rmem_conv1x1_dual_nhwc', 'rmem_bneck_chain', 'rmem_label_id_embed', 'rmem_image_ptrs_to_nhwc4p', 'rmem_stem7x7s2', 'rmem_stem7x7s2_pool', 'rmem_conv3x3_c64_direct', 'rmem_conv3x3_direct', 'rmem_linear_grouped',
+F16_TWINS = ('rmem_conv2d_nhwc', 'rmem_mem_read_attn', 'rmem_mem_read_attn_clips', 'rmem_lstt_attn_pair_clips', 'rmem_lstt_attn_pair_clips_deferred', 'rmem_layernorm256', 'rmem_layernorm', 'rmem_patch_merge_ln',
+             'rmem_window_attn', 'rmem_window_attn_images', 'rmem_patch_merge_ln_images', 'rmem_add16', 'rmem_add16_grouped', 'rmem_layernorm256_pair', 'rmem_lstt_chain_a', 'rmem_lstt_chain_b', 'rmem_lstt_chain_b_merged', 'rmem_lstt_chain_c', 'rmem_conv1x1_dual_nhwc', 'rmem_bneck_chain', 'rmem_label_id_embed', 'rmem_image_ptrs_to_nhwc4p', 'rmem_stem7x7s2', 'rmem_stem7x7s2_pool', 'rmem_conv3x3_c64_direct', 'rmem_conv3x3_direct', 'rmem_linear_grouped',
              'rmem_groupnorm_nhwc', 'rmem_groupnorm_f32_nhwc', 'rmem_groupnorm_nhwc_images', 'rmem_groupnorm_head_nhwc_images',
              'rmem_gn_act_dwconv5x5_nhwc_images', 'rmem_gn_act_dwconv5x5_prestats_nhwc_images', 'rmem_gn_act_dwconv5x5_nhwc', 'rmem_dwconv5x5_nhwc', 'rmem_image_to_nhwc8',
              'rmem_image_to_nhwc8_images', 'rmem_image_ptrs_to_nhwc8', 'rmem_ingest_rgb8', 'rmem_maxpool3x3s2_nhwc', 'rmem_maxpool3x3s2_nhwc_images', 'rmem_bilinear_nhwc',

@@ -733,7 +733,8 @@ static int attn_launch(const void* q, int ldq, const void* k_bank, const void* v
                        const float* pe_cur, const float* pe_mem, int Lq, int heads, void* out, int ldo,
                        float* attn_mass, int T, int nclips, long long q_clip_stride, long long kv_clip_stride,
                        long long out_clip_stride, void* workspace, void* stream,
-                       const void* k2, const void* v2, int lk2, long long kv2_clip_stride, void* out2, long long out2_clip_stride) {
+                       const void* k2, const void* v2, int lk2, long long kv2_clip_stride, void* out2, long long out2_clip_stride,
+                       rmem_attn_merge* defer = nullptr) {
   RMEM_REQUIRE(nclips >= 1 && nclips <= 64, "rmem_mem_read_attn: 1..64 clips");
   RMEM_REQUIRE(q_clip_stride % 8 == 0 && kv_clip_stride % 8 == 0 && out_clip_stride % 8 == 0, "rmem_mem_read_attn: clip strides must be multiples of 8 elements");
   const long long prof_keys = chunks ? (long long)lk_single : 0;   // with a row table lk_single carries the total key count (timing only)
@@ -793,7 +794,12 @@ static int attn_launch(const void* q, int ldq, const void* k_bank, const void* v
   cp.opart = p.opart; cp.mlg = p.mlg; cp.ngroups = p.ngroups; cp.ml = p.ml; cp.chunks = chunks; cp.nchunks = nchunks;
   cp.Lq = Lq; cp.heads = heads; cp.out = (e16*)out; cp.ldo = ldo; cp.mass = attn_mass; cp.T = T;
   cp.out_cs = out_clip_stride; cp.opart_cs = p.opart_cs; cp.mlg_cs = p.mlg_cs; cp.ml_cs = p.ml_cs; cp.mass_cs = (long)Lq * T;
-  if (p.ngroups > 1) hipLaunchKernelGGL(k_attn_combine, dim3((Lq + 63) / 64, 16, nclips), dim3(256), 0, s, cp);
+  if (defer) {
+    // the caller merges the key groups itself (rmem_lstt_chain_b_merged, while it stages its A panels): hand it k_attn_combine's inputs
+    defer->ngroups = p.ngroups; defer->heads = heads; defer->Lq = Lq; defer->reserved = 0;
+    defer->opart = p.opart; defer->mlg = p.mlg; defer->opart_cs = p.opart_cs; defer->mlg_cs = p.mlg_cs;
+  }
+  if (p.ngroups > 1 && !defer) hipLaunchKernelGGL(k_attn_combine, dim3((Lq + 63) / 64, 16, nclips), dim3(256), 0, s, cp);
   if (attn_mass) hipLaunchKernelGGL(k_attn_mass, dim3((Lq + 63) / 64, 1, nclips), dim3(256), 0, s, cp);
   return rmem_check_launch("rmem_mem_read_attn");
 }
@@ -817,6 +823,19 @@ extern "C" int RMEM_API(rmem_lstt_attn_pair_clips)(const void* q, int ldq, const
   return attn_launch(q, ldq, k_bank, v_bank, slot_stride, ldkv, chunks, nchunks, lk_total, pe_cur, pe_mem, Lq, heads, out_long, ldo, attn_mass, T,
                      nclips, q_clip_stride, 0, out_clip_stride, workspace, stream, k_short, v_short, lk_short, kv_short_clip_stride, out_short,
                      out_short_clip_stride);
+}
+
+extern "C" int RMEM_API(rmem_lstt_attn_pair_clips_deferred)(const void* q, int ldq, const void* k_bank, const void* v_bank, long long slot_stride,
+                                                  int ldkv, const rmem_attn_chunk* chunks, int nchunks, int lk_total,
+                                                  const float* pe_cur, const float* pe_mem, int Lq, int heads, void* out_long, int ldo,
+                                                  float* attn_mass, int T, int nclips, long long q_clip_stride, long long out_clip_stride,
+                                                  const void* k_short, const void* v_short, int lk_short, long long kv_short_clip_stride,
+                                                  void* out_short, long long out_short_clip_stride, void* workspace,
+                                                  rmem_attn_merge* merge, void* stream) {
+  RMEM_REQUIRE(chunks && k_short && v_short && out_short && merge, "rmem_lstt_attn_pair_deferred: null argument");
+  return attn_launch(q, ldq, k_bank, v_bank, slot_stride, ldkv, chunks, nchunks, lk_total, pe_cur, pe_mem, Lq, heads, out_long, ldo, attn_mass, T,
+                     nclips, q_clip_stride, 0, out_clip_stride, workspace, stream, k_short, v_short, lk_short, kv_short_clip_stride, out_short,
+                     out_short_clip_stride, merge);
 }
 
 extern "C" int RMEM_API(rmem_mem_read_attn)(const void* q, int ldq, const void* k_bank, const void* v_bank, long long slot_stride,

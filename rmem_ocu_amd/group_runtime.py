@@ -58,6 +58,7 @@ class GroupRuntime:
         self.swin = 'pe.w' in P
         self.chain = not os.environ.get('RMEM_NO_CHAIN')      # 1: the unfused launch list (A/B runs, identity tests)
         self.pair_attn = not os.environ.get('RMEM_NO_PAIR_ATTN')   # 1: memory read and short-term attention as two launches
+        self.merge_fold = not os.environ.get('RMEM_NO_MERGE_FOLD')   # 1: the memory read's key groups merged by a pass of their own
         self.P, self.dev, self.NL, self.B = P, device, num_lstt, clips
         self.dt = P['proj.w'].dtype
         self.align, self.nc = align_corners, num_classes
@@ -355,11 +356,13 @@ class GroupRuntime:
                                       ln2=ln(d + '.ln2'), curr_v=self.curr_V[i], w_q=P[d + '.linear_Q.wf'], b_q=P[d + '.linear_Q.b'], curr_q=cq,
                                       short_k=self.short_K[i], short_v=self.short_V[i], ln4=ln(d + '.ln4'), k4=self.k4, v4=self.v4))
             mass = self.mass if (i == 0 and want_mass) else None
+            # the memory read's key groups are merged by chain B while it stages its rows, not by a pass in between
+            mg = ops.attn_merge() if (self.pair_attn and self.merge_fold) else None
             if self.pair_attn:       # long-term memory read + short-term attention: one launch (same queries, independent keys)
                 o.append(ops.lstt_attn_pair(cq, self.bank_K[i], self.bank_V[i], self.att, self.k4, self.v4, self.att2, self.attn_ws, Lq=L,
                                             heads=HEADS, ldq=C, ldkv=C, ldo=C, slot_stride=L * C, chunks=self.chunks, nchunks=nchunks,
                                             lk_total=T * L, pe_cur=P['pe_cur'], pe_mem=P['pe_mem'], mass=mass, T=T, nclips=B, q_cs=L * C,
-                                            out_cs=L * C, lk_short=L, kv_short_cs=L * C, out_short_cs=L * C))
+                                            out_cs=L * C, lk_short=L, kv_short_cs=L * C, out_short_cs=L * C, merge=mg))
             else:
                 o.append(self._attn(cq, C, self.bank_K[i], self.bank_V[i], C, self.att, slot_stride=L * C, chunks=self.chunks,
                                     nchunks=nchunks, lk_single=T * L, pe_cur=P['pe_cur'], pe_mem=P['pe_mem'], mass=mass, T=T))
@@ -367,7 +370,8 @@ class GroupRuntime:
             o.append(ops.lstt_chain_b(L=L, clips=B, att_long=self.att, att_short=self.att2, x=self.x, w_long=P[d + '.long_proj.wf'],
                                       b_long=P[d + '.long_proj.b'], w_short=P[d + '.short_proj.wf'], b_short=P[d + '.short_proj.b'],
                                       tgt3=self.tgt3[i], ln3=ln(d + '.ln3'), w1=P[d + '.linear1.wf'], b1=P[d + '.linear1.b'], h1=self.h1,
-                                      gn_partial=self.ffn_stats if self.chain_stats else None, gn_splits=64 if self.chain_stats else 0))
+                                      gn_partial=self.ffn_stats if self.chain_stats else None, gn_splits=64 if self.chain_stats else 0,
+                                      merge=mg))
             if self.chain_stats:     # the GroupNorm statistics of the FFN hidden came out of linear1's epilogue (<= 64 row blocks per clip)
                 o.append(ops.gn_act_dwconv5x5_prestats(self.h1, P[d + '.gn.g'], P[d + '.gn.b'], P[d + '.dw.w'], self.h3, self.ffn_stats,
                                                        H=self.H16, W=self.W16, C=FFN, groups=32, act=2, images=B))

@@ -189,15 +189,28 @@ def layernorm256_pair(a0, b0, y0, a1, b1, y1, gamma, beta, *, M, eps=1e-5) -> Op
     return Op(_fn('rmem_layernorm256_pair', dt), args, 'rmem_layernorm256_pair', (a0, b0, y0, a1, b1, y1, gamma, beta))
 
 
-def _chain(name, cls, ints, ptrs, dt):
-    """An rmem_lstt_chain_* launch: ints = (L, clips, eps, third int), ptrs = {field: tensor or None} in the struct's order."""
+def lstt_chain_rows(L: int, clips: int, cus: int) -> int:
+    """Rows per workgroup (32 or 64) the chain launches take for `clips` clips of L tokens on a device with `cus` compute units
+    (include/rmem.h, rmem_lstt_chain_rows; RMEM_CHAIN_ROWS = 32 | 64 overrides it at launch).  Host only: no tensor, no GPU."""
+    return int(_lib.lib().rmem_lstt_chain_rows(int(L), int(clips), int(cus)))
+
+
+def attn_merge():
+    """A host record the deferred-merge memory read (lstt_attn_pair(..., merge=m)) fills at every call and chain B
+    (lstt_chain_b(..., merge=m)) reads at its own: the key-group partials of att_long, merged while chain B stages its rows."""
+    return _lib.AttnMerge()
+
+
+def _chain(name, cls, ints, ptrs, dt, extra=()):
+    """An rmem_lstt_chain_* launch: ints = (L, clips, eps, third int), ptrs = {field: tensor or None} in the struct's order;
+    extra: arguments between the descriptor and the stream."""
     ts = list(ptrs.values())
     _dev(*ts)
     for k, t in ptrs.items():
         if t is not None and t.data_ptr() % 16:
             raise RmemError(f'{name}: {k} must be 16-byte aligned')
     d = cls(int(ints[0]), int(ints[1]), float(ints[2]), int(ints[3]), *[_ptr(t) for t in ts])
-    return Op(_fn(name, dt), (C.byref(d),), name, (d, ts))
+    return Op(_fn(name, dt), (C.byref(d), *[C.byref(e) for e in extra]), name, (d, ts, extra))
 
 
 def lstt_chain_a(*, L, clips, att, x, w_proj, b_proj, ln2, curr_v, w_q, b_q, curr_q, short_k, short_v, ln4, k4, v4, eps=1e-5) -> Op:
@@ -213,17 +226,18 @@ def lstt_chain_a(*, L, clips, att, x, w_proj, b_proj, ln2, curr_v, w_q, b_q, cur
 
 
 def lstt_chain_b(*, L, clips, att_long, att_short, x, w_long, b_long, w_short, b_short, tgt3, ln3, w1, b1, h1, gn_partial=None,
-                 gn_splits=0, eps=1e-5) -> Op:
+                 gn_splits=0, eps=1e-5, merge=None) -> Op:
     """x += att_long @ Wl^T + bl; tgt3 = att_short @ Ws^T + bs; x += tgt3; h1 = LN3(x) @ W1^T + b1 ([rows, 1024])
-    (+ per-row-block GroupNorm partial sums of h1: fp32 [clips, 32, gn_splits, 2])."""
+    (+ per-32-row-block GroupNorm partial sums of h1: fp32 [clips, 32, gn_splits, 2]).  merge (attn_merge()): att_long's rows are
+    merged from the key groups of the deferred-merge memory read that filled it, when that read had more than one group."""
     dt = att_long.dtype
     R = clips * L
     assert x.dtype == F32 and all(t.dtype == dt and t.numel() >= R * 256 for t in (att_long, att_short, tgt3)) and h1.dtype == dt and h1.numel() >= R * 1024
     assert w_long.numel() == 65536 and w_short.numel() == 65536 and w1.numel() == 262144 and b1.numel() == 1024
     assert gn_partial is None or (gn_partial.dtype == F32 and gn_splits * 32 >= L and gn_partial.numel() >= clips * 32 * gn_splits * 2)
-    return _chain('rmem_lstt_chain_b', _lib.ChainB, (L, clips, eps, gn_splits),
+    return _chain('rmem_lstt_chain_b' if merge is None else 'rmem_lstt_chain_b_merged', _lib.ChainB, (L, clips, eps, gn_splits),
                   dict(att_long=att_long, att_short=att_short, x=x, w_long=w_long, b_long=b_long, w_short=w_short, b_short=b_short, tgt3=tgt3,
-                       ln3_g=ln3[0], ln3_b=ln3[1], w1=w1, b1=b1, h1=h1, gn_partial=gn_partial), dt)
+                       ln3_g=ln3[0], ln3_b=ln3[1], w1=w1, b1=b1, h1=h1, gn_partial=gn_partial), dt, () if merge is None else (merge,))
 
 
 def lstt_chain_c(*, L, clips, x, dt, h3=None, w2=None, b2=None, dec_norm=(None, None), dec_out=None, ld_dec=0, ln1=(None, None), w_qkv=None,
@@ -268,8 +282,11 @@ def mem_read_attn(q, k_bank, v_bank, out, workspace, *, Lq, heads=8, ldq, ldkv, 
 
 
 def lstt_attn_pair(q, k_bank, v_bank, out_long, k_short, v_short, out_short, workspace, *, Lq, heads=8, ldq, ldkv, ldo, slot_stride, chunks,
-                   nchunks, lk_total, pe_cur, pe_mem, mass=None, T=0, nclips=1, q_cs=0, out_cs=0, lk_short, kv_short_cs=0, out_short_cs=0) -> Op:
-    """The long-term memory read (mem_read_attn with a chunk table) and the short-term attention of the same queries as one launch."""
+                   nchunks, lk_total, pe_cur, pe_mem, mass=None, T=0, nclips=1, q_cs=0, out_cs=0, lk_short, kv_short_cs=0, out_short_cs=0,
+                   merge=None) -> Op:
+    """The long-term memory read (mem_read_attn with a chunk table) and the short-term attention of the same queries as one launch.
+    merge (attn_merge()): the deferred-merge form -- with more than one key group out_long is NOT written; the record tells
+    lstt_chain_b(..., merge=) where the partials are."""
     _dev(q, k_bank, v_bank, out_long, k_short, v_short, out_short, workspace, chunks, pe_cur, pe_mem, mass)
     dt = q.dtype
     assert all(t.dtype == dt for t in (k_bank, v_bank, out_long, k_short, v_short, out_short))
@@ -280,8 +297,10 @@ def lstt_attn_pair(q, k_bank, v_bank, out_long, k_short, v_short, out_short, wor
     args = (_ptr(q), ldq, _ptr(k_bank), _ptr(v_bank), slot_stride, ldkv, _ptr(chunks), nchunks, lk_total, _ptr(pe_cur), _ptr(pe_mem), Lq, heads,
             _ptr(out_long), ldo, _ptr(mass), T, nclips, q_cs, out_cs, _ptr(k_short), _ptr(v_short), lk_short, kv_short_cs, _ptr(out_short),
             out_short_cs, _ptr(workspace))
-    return Op(_fn('rmem_lstt_attn_pair_clips', dt), args, 'rmem_lstt_attn_pair',
-              (q, k_bank, v_bank, out_long, k_short, v_short, out_short, workspace, chunks, pe_cur, pe_mem, mass))
+    if merge is not None:
+        args += (C.byref(merge),)
+    return Op(_fn('rmem_lstt_attn_pair_clips' if merge is None else 'rmem_lstt_attn_pair_clips_deferred', dt), args, 'rmem_lstt_attn_pair',
+              (q, k_bank, v_bank, out_long, k_short, v_short, out_short, workspace, chunks, pe_cur, pe_mem, mass, merge))
 
 
 def layernorm256(a, gamma, beta, *, M, lda=256, b=None, ldb=256, y=None, ldy=256, pos=None, ypos=None, ldyp=256,
