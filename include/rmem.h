@@ -762,6 +762,39 @@ int rmem_label_nearest(const unsigned char* labels, int n, int H, int W, const u
                        const unsigned int fill_bits[8], int max_d2, int* index, int* dist2, unsigned char* taken, void* workspace,
                        long long workspace_bytes, void* stream);
 
+/* Shape census of uint8 label stacks: raw moments, row extents and convex hulls (shapes.py: label_moments, row_extents,
+ * convex_hulls, region_props; evaluator.object_shapes, object_centroids, rotated_boxes).  Integers only, integer atomics only:
+ * bit-reproducible.  labels: uint8 [n][H][W], contiguous, device, may start at any byte and is only read.  x and y are a pixel's
+ * column and row index.  H and W at most 16384 (and H * W at most 2^26): every sum stays below 2^55.
+ * rmem_label_moments: one pass over the labels by image rows, two outputs, either may be NULL (not both).
+ *   moments int64 [n][256][6] = (m00, m10, m01, m20, m11, m02) = (count, sum x, sum y, sum x^2, sum x y, sum y^2) of the pixels of
+ *     frame f equal to value v; zeros for an absent value.  The call zeroes the table itself.
+ *   extents int32 [n][num][H][2] = (xmin, xmax) of value v = 1..num (entry v - 1) on row y, (W, -1) on a row without it.  Values
+ *     above num are counted in the moments and appear in no extent.  num is read only with extents.
+ *   Every entry of both is written; prior contents do not matter.
+ * The hull is that of the pixel SQUARES, in pixel-corner coordinates (rmem_label_polygons' system): corner level l, 0..H, lies
+ * between rows l - 1 and l; its candidates are L[l] = min(xmin[l-1], xmin[l]) and R[l] = max(xmax[l-1], xmax[l]) + 1 over the rows
+ * that hold the value.  The hull is the convex minorant of L and the concave majorant of R over the levels plus the top and the
+ * bottom edge: at most 2 (h + 1) vertices for an object h rows high.
+ * rmem_label_hull_count: extents as above for n frames; flags uint8 [n][num][H + 1]: bit 0 = level l is a vertex of the left chain,
+ *   bit 1 = of the right chain; counts int32 [n * num]: the object's number of hull vertices, 0 for an absent one (else >= 4).
+ *   Every entry of both is written.  One wave per object, one serial stack walk per chain (O(h)); turns are int32 cross products
+ *   below 2^29; 4 H bytes of LDS.
+ * rmem_label_hull_offsets: counts int32 [objects + 1]: the first `objects` entries become their exclusive prefix sums in place,
+ *   the last one the total V.  One workgroup.
+ * rmem_label_hull_write: extents and flags of n frames as rmem_label_hull_count left them, offsets int32 [n * num + 1] their part
+ *   of the scanned counts; verts int32 [capacity][2] = (x, y) corners, object o's ring at verts[offsets[o] .. offsets[o + 1]):
+ *   strictly convex vertices only, starting at the vertex with the smallest (y, x), the object on the right of the direction of
+ *   travel with y down (east along the top edge first: rmem_label_polygons' outer rings, a positive shoelace sum).  A ring that
+ *   would not fit `capacity` is not written.
+ * Refused (non-zero, nothing launched): null pointers, n outside 1..65535, H or W outside 1..16384, H * W above 2^26, num outside
+ * 1..255 (where it is read), objects outside 1..65535 * 255, capacity outside 1..2^31-1. */
+int rmem_label_moments(const unsigned char* labels, int n, int H, int W, int num, long long* moments, int* extents, void* stream);
+int rmem_label_hull_count(const int* extents, int n, int H, int W, int num, unsigned char* flags, int* counts, void* stream);
+int rmem_label_hull_offsets(int* counts, int objects, void* stream);
+int rmem_label_hull_write(const int* extents, const unsigned char* flags, int n, int H, int W, int num, const int* offsets, int* verts,
+                          long long capacity, void* stream);
+
 /* Surface distances of two label stacks: the surfaces, a distance transform evaluated on chosen pixels only, and the census that
  * reduces every object's surface-to-surface distances to a few integers (surface.py: label_surface, edt_at, surface_census,
  * surface_metrics; evaluator.surface_metrics).  Integers only, integer atomics only: bit-reproducible.  All stacks [n][H][W],

@@ -43,7 +43,11 @@ Mirrors what networks/managers/evaluator.py:330-568 does for one sequence, witho
   * which pixel the nearest site is, not only how far, comes from the same two passes with the site carried along (ties to the
     first site in raster order), and with the label read there objects grow without overlap, void pixels take the nearest real
     value and sparse seeds become a full label map -- rmem_label_nearest, distance.nearest / grow, expand_masks, fill_void,
-    labels_from_seeds.
+    labels_from_seeds;
+  * what shape an object has -- centroid, orientation, axis lengths, solidity, convex hull, VOT's rotated box -- comes from one pass
+    over the labels by image rows (exact 64-bit moments, the x extent of every object on every row) and a hull built from those
+    extents alone -- rmem_label_moments, rmem_label_hull_count / _offsets / _write, shapes.py, object_shapes, object_centroids,
+    rotated_boxes.
 """
 from __future__ import annotations
 
@@ -395,6 +399,40 @@ def object_boxes(labels_u8: torch.Tensor, num_objs: int) -> Tuple[torch.Tensor, 
         raise _lib.RmemError(f'object_boxes: num_objs must be in 1..255 (got {num_objs})')
     area, box = label_census(labels_u8)
     return area[:, 1:int(num_objs) + 1], box[:, 1:int(num_objs) + 1]
+
+
+def object_shapes(labels_u8: torch.Tensor, num_objs: int, squeeze_idx: Optional[Sequence[int]] = None) -> List[Dict]:
+    """What shape every object has: per frame of a predicted stack [n, H, W] (uint8, device) {object id: props} for the ids
+    1..num_objs the frame holds (squeeze_idx: keyed by squeeze_idx[id], save_masks' un-squeeze) -- area, centroid, central moments,
+    orientation, axis lengths, eccentricity, convex hull, solidity, extent, Feret diameter and the minimum-area rectangle;
+    shapes.props_from_tables lists them.  Moments and hulls come from the device (shapes.region_props); the current stream, one
+    4-byte readback and one of the tables."""
+    from .shapes import region_props
+    return region_props(labels_u8, num_objs, squeeze_idx)
+
+
+def object_centroids(labels_u8: torch.Tensor, num_objs: int) -> np.ndarray:
+    """Centre tracks (OTB / LaSOT centre location error): float64 [n, num_objs, 2] = (x, y) of the centroid of the ids 1..num_objs in
+    a predicted stack [n, H, W] (uint8, device), in pixel-index coordinates, NaN where a frame lacks the object.  One call of
+    shapes.label_moments on the current stream and one readback of its table; nothing else is computed."""
+    from .shapes import label_moments
+    K = _labels.int_in('object_centroids', 'num_objs', num_objs, 1, 255)
+    m = label_moments(labels_u8)[:, 1:K + 1, :3].cpu().numpy().astype(np.float64)
+    with np.errstate(invalid='ignore', divide='ignore'):
+        return np.where(m[..., :1] > 0, m[..., 1:3] / m[..., :1], np.nan)
+
+
+def rotated_boxes(labels_u8: torch.Tensor, num_objs: int) -> np.ndarray:
+    """VOT's rotated boxes from masks: float64 [n, num_objs, 8] = x1, y1, ..., x4, y4 of the minimum-area rectangle around the ids
+    1..num_objs in a predicted stack [n, H, W] (uint8, device), in pixel-corner coordinates (a single pixel at (x, y) has the box
+    x..x + 1, y..y + 1), NaN where a frame lacks the object.  shapes.region_props' min_rect."""
+    K = _labels.int_in('rotated_boxes', 'num_objs', num_objs, 1, 255)
+    frames = object_shapes(labels_u8, K)
+    out = np.full((len(frames), K, 8), np.nan, dtype=np.float64)
+    for f, fr in enumerate(frames):
+        for v, props in fr.items():
+            out[f, v - 1] = props['min_rect'].reshape(-1)
+    return out
 
 
 def clean_masks(labels_u8: torch.Tensor, fill_holes: int = 0, remove_specks: int = 0, keep_largest: bool = False,
