@@ -7,6 +7,8 @@ from contextlib import contextmanager
 import pytest
 import torch
 
+from lstt_ref import fill_lstt_state
+
 
 @pytest.fixture(scope='module')
 def dev():
@@ -58,12 +60,7 @@ def run_lstt(dev, dt, hw, *, chain=True, stats=False, slots=None, fold=True):
     rt.chain_stats = stats
     rt.merge_fold = fold
     L = rt.L
-    g = torch.Generator().manual_seed(7)
-    r = lambda *s: torch.randn(*s, generator=g)      # noqa: E731
-    rt.x.copy_(r(B * L, 256))
-    for i in range(3):
-        rt.short_K[i].copy_(r(B * L, 256)); rt.short_V[i].copy_(r(B * L, 256))
-        rt.bank_K[i].copy_(r(*rt.bank_K[i].shape)); rt.bank_V[i].copy_(r(*rt.bank_V[i].shape))
+    fill_lstt_state(rt)
     rt.slots = slots if slots is not None else [[1, 3] for _ in range(B)]
     s = torch.cuda.current_stream().cuda_stream
     rt.prepare_pos(s)

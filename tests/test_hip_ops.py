@@ -1243,6 +1243,7 @@ def test_lstt_chains_are_bit_identical(dev, dt, hw):
     from rmem_ocu_amd import build_vos_model, get_config, ops
     from rmem_ocu_amd.group_runtime import GroupRuntime
     from rmem_ocu_amd.weights import synth_state_dict
+    from lstt_ref import fill_lstt_state
     cfg = get_config('pre_vost', 'test', 'r50_aotl')
     cfg.MODEL_DTYPE = dt
     model = build_vos_model(cfg.MODEL_VOS, cfg).cuda(0)
@@ -1255,12 +1256,7 @@ def test_lstt_chains_are_bit_identical(dev, dt, hw):
         rt.chain = chain
         rt.chain_stats = False        # (the GroupNorm partial sums out of linear1's epilogue add in another order: next test)
         L = rt.L
-        g = torch.Generator().manual_seed(7)
-        r = lambda *s: torch.randn(*s, generator=g)      # noqa: E731
-        rt.x.copy_(r(B * L, 256))
-        for i in range(3):
-            rt.short_K[i].copy_(r(B * L, 256)); rt.short_V[i].copy_(r(B * L, 256))
-            rt.bank_K[i].copy_(r(*rt.bank_K[i].shape)); rt.bank_V[i].copy_(r(*rt.bank_V[i].shape))
+        fill_lstt_state(rt)
         rt.slots = [[1, 3] for _ in range(B)]
         s = torch.cuda.current_stream().cuda_stream
         rt.prepare_pos(s)
@@ -1334,6 +1330,7 @@ def test_lstt_chain_groupnorm_statistics(dev):
     from rmem_ocu_amd import build_vos_model, get_config, ops
     from rmem_ocu_amd.group_runtime import GroupRuntime
     from rmem_ocu_amd.weights import synth_state_dict
+    from lstt_ref import fill_lstt_state
     cfg = get_config('pre_vost', 'test', 'r50_aotl')
     model = build_vos_model(cfg.MODEL_VOS, cfg).cuda(0)
     model.load_state_dict(synth_state_dict(0))
@@ -1344,13 +1341,7 @@ def test_lstt_chain_groupnorm_statistics(dev):
         rt = GroupRuntime(P, (161, 193), 4, dev, B, lookahead=1)
         assert rt.chain and rt.chain_stats
         rt.chain_stats = stats
-        L = rt.L
-        g = torch.Generator().manual_seed(7)
-        r = lambda *s: torch.randn(*s, generator=g)      # noqa: E731
-        rt.x.copy_(r(B * L, 256))
-        for i in range(3):
-            rt.short_K[i].copy_(r(B * L, 256)); rt.short_V[i].copy_(r(B * L, 256))
-            rt.bank_K[i].copy_(r(*rt.bank_K[i].shape)); rt.bank_V[i].copy_(r(*rt.bank_V[i].shape))
+        fill_lstt_state(rt)
         rt.slots = [[1, 3] for _ in range(B)]
         s = torch.cuda.current_stream().cuda_stream
         rt.prepare_pos(s)
