@@ -1029,6 +1029,87 @@ int rmem_polygon_fill_labels(const int* edge_xy, const int* edge_shape, const in
                              const RmemPolyPass* pass /* host */, void* workspace, size_t workspace_bytes,
                              unsigned char* labels /* device [frames][H][W] */, int* status /* device [nshapes] */, void* stream);
 
+/* Strokes drawn into uint8 label maps labels[frames][H][W] (contiguous, device, may start at any byte): scribbles, clicks and
+ * polylines, the way interactive rounds and DAVIS-interactive scribble files enter a run (strokes.py: PackedStrokes,
+ * draw_labels_into, draw_label_stack; evaluator.seeds_from_scribbles, seeds_from_clicks, labels_from_scribbles).  One call on
+ * `stream`, no host sync, no state kept between calls; only the strokes' segments cross to the device.
+ * Coordinates are PIXEL-INDEX coordinates: the centre of pixel (y, x) is the point (x, y) -- what evaluator.next_clicks and
+ * next_scribbles return and the DAVIS toolkit uses, NOT the corner convention of the polygon fill above.  Fixed point is 1/256
+ * pixel: X = rint(256 x), Y = rint(256 y) in float64 (ties to even), |x|, |y| <= 2^20; pixel (py, px) is the point
+ * P = (256 px, 256 py).
+ * A stroke is a value 0..255 (0 erases), a radius r in 0..256 pixels, R = rint(256 r), and a polyline of at least one point (one
+ * point: a click), given as segments A -> B; a lone point is the one segment A -> A.  A frame lists its strokes in painting order:
+ * a pixel covered by several strokes takes the value of the last one, a pixel covered by none is 0, or keeps its byte when `over`
+ * is not zero.
+ * Round brush, R >= 1.  A stroke covers the pixels whose centre lies within R of any of its segments, so joins and caps are round
+ * and a lone point covers a disc.  For a segment A -> B with d = B - A, w = P - A, t = w.d, L = d.d: if t <= 0 the pixel is
+ * covered iff |w|^2 <= R^2; if t >= L iff |P - B|^2 <= R^2; otherwise iff (w x d)^2 <= R^2 L.  Integer arithmetic throughout: every
+ * 64-bit term stays below 2^60, the two products of the last comparison are taken in 128 bits.
+ * Hairline, R == 0: a digital line, 8-connected and independent of direction.  The host orients every segment by its major axis M
+ * (x if |dX| >= |dY|, else y; m is the other one) so that dM > 0; a segment with d = 0 draws only its endpoint's pixel.  Drawn are
+ * the pixel of each endpoint, rounded half up per axis, (X + 128) >> 8 with a floor shift, and for every integer k with
+ * A_M <= 256 k <= B_M the pixel whose major index is k and whose minor index is floor((N + 128 dM) / (256 dM)),
+ * N = A_m dM + (256 k - A_M) d_m: the exact minor coordinate rounded half up.  A path of integer vertices that are 8-neighbours
+ * draws exactly its vertices' pixels.
+ * Anything off the frame is clipped and is no error.  (Equality with the DAVIS toolkit's Bresenham and Bezier code is not claimed.)
+ * Input, all device, built by the host:
+ *   seg_xy       int32 [nsegs][4], 16-byte aligned: (AX, AY, BX, BY) of every segment that has work items, listed stroke by stroke.
+ *   seg_stroke   int32 [nsegs]: the segment's stroke (index into strokes).
+ *   seg_first    int32 [nsegs + 1]: the exclusive prefix of the segments' work items; seg_first[nsegs] is the total, at most
+ *                2^31 - 1.  A segment's box is the pixels it can cover clipped to the frame -- columns ceil((minX - R) / 256) ..
+ *                floor((maxX + R) / 256) for a round brush, (minX + 128) >> 8 .. (maxX + 128) >> 8 for a hairline, rows alike.  A
+ *                segment with an empty box has no work items and is not listed.  Otherwise a round-brush segment has one work item
+ *                per row of its box, a hairline two (its endpoints) plus one per k above with the major index inside the frame.
+ *   strokes      RmemStroke [nstrokes]: frame (non-decreasing along the table), value, R, the union of the boxes of its segments
+ *                (columns x0..x1-1, rows y0..y1-1; all zero when it has none) and slot, the place of its frame in `stroked`.
+ *   frame_stroke int32 [frames + 1]: the first stroke of every frame; frame_stroke[frames] = nstrokes.
+ *   stroked      int32 [nstroked]: the frames that list at least one stroke, ascending.
+ * pass (host): the frames the call draws and what belongs to them -- the strokes listed for those frames, their segments, the work
+ * items of those segments (item0 = seg_first[seg0]) and the stroked frames among them (slot0, slots).
+ * workspace: rmem_stroke_workspace_bytes(slots, H, W) bytes, 16-byte aligned: one int32 owner map [H][W] per STROKED frame of the
+ * pass (frames without strokes have none), cleared by the call itself: a dirty workspace never shows.  A covered pixel takes the
+ * maximum of (the stroke's index within its frame) + 1 by an integer atomic; max commutes, the bytes do not depend on the order of
+ * arrival.  Then, per 16 output bytes: where the owner is not zero the byte is the owning stroke's value; otherwise it is 0, or
+ * untouched when `over` is not zero -- then frames without strokes are not touched at all, while without `over` they are zeroed.
+ * status (device, int32 [nstrokes]) is written for every stroke of the pass, 0 = drawn.  Every index read from device memory is
+ * range-checked before it is used, and a stroke with a non-zero status draws nothing, the others are intact:
+ *   ST_DESC    frame outside the pass or below the frame of the stroke before, the stroke outside its frame's range in
+ *              frame_stroke, value outside 0..255, R outside 0..65536, a box outside the frame, a slot outside the pass's or one
+ *              whose entry in `stroked` is another frame; also set when a segment names a stroke outside the pass (on the pass's
+ *              first or last stroke, whichever is nearer to the name)
+ *   ST_PREFIX  the work-item prefix disagrees with a segment (its difference is not the segment's count, it decreases, or its ends
+ *              are not the pass's item0 and item0 + items)
+ *   ST_SEGMENT a coordinate beyond 2^28, a hairline segment with d != 0 and dM <= 0, or a segment whose box leaves its stroke's box
+ * 5 launches per pass: a memset, one thread per stroke, one per segment (the checks above: all of them precede the first atomic,
+ * because a maximum cannot be taken back), one per work item, one per 16 output bytes.  Every loop is bounded.
+ * Refused (non-zero, nothing launched): null pointers, frames outside 1..65535, non-positive H / W, H * W above 2^26, nstrokes
+ * outside 1..2^30, nsegs outside 0..2^30, nstroked outside 1..frames, a pass whose frames, strokes, segments or slots are no range
+ * of the tables', whose items leave 0..2^31-1 or exist without segments and strokes, whose strokes exist without slots; a
+ * misaligned workspace or seg_xy, a workspace smaller than the query says. */
+typedef struct RmemStroke {
+  int frame;            /* 0..frames-1 */
+  int value;            /* 0..255: the label the stroke draws, 0 erases */
+  int radius;           /* R = rint(256 r), 0..65536; 0: a hairline */
+  int x0, y0, x1, y1;   /* the box, clipped to the frame */
+  int slot;             /* stroked[slot] == frame */
+} RmemStroke;
+typedef struct RmemStrokePass {
+  int frame0, frames;
+  int stroke0, strokes;
+  int seg0, segs;
+  int slot0, slots;
+  long long item0, items;
+} RmemStrokePass;
+#define RMEM_STROKE_ST_DESC 1
+#define RMEM_STROKE_ST_PREFIX 2
+#define RMEM_STROKE_ST_SEGMENT 4
+size_t rmem_stroke_workspace_bytes(int stroked_frames, int H, int W);   /* host only, 0 for refused arguments */
+int rmem_stroke_draw_labels(const int* seg_xy, const int* seg_stroke, const int* seg_first, int nsegs,
+                            const RmemStroke* strokes /* device */, int nstrokes, const int* frame_stroke, const int* stroked,
+                            int nstroked, int frames, int H, int W, const RmemStrokePass* pass /* host */, void* workspace,
+                            size_t workspace_bytes, unsigned char* labels /* device [frames][H][W] */, int over,
+                            int* status /* device [nstrokes] */, void* stream);
+
 /* Region-similarity (Jaccard) counts per object id for one mask pair: counts[2*id] += |pred==id & gt==id|,
  * counts[2*id+1] += |pred==id | gt==id| over the n pixels whose ground truth is not `void_label`; the caller zeroes
  * counts (uint64 [2 * num_ids]).  Replaces evaluation/source/metrics.py:6-37 (db_eval_iou) per object. */

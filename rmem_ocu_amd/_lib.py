@@ -90,6 +90,15 @@ class PolyPass(C.Structure):
                 + [(n, C.c_longlong) for n in ('cross0', 'crossings', 'plane0', 'plane_words')])
 
 
+class Stroke(C.Structure):
+    _fields_ = [(n, C.c_int) for n in ('frame', 'value', 'radius', 'x0', 'y0', 'x1', 'y1', 'slot')]
+
+
+class StrokePass(C.Structure):
+    _fields_ = ([(n, C.c_int) for n in ('frame0', 'frames', 'stroke0', 'strokes', 'seg0', 'segs', 'slot0', 'slots')]
+                + [(n, C.c_longlong) for n in ('item0', 'items')])
+
+
 class LabelRoute(C.Structure):
     _fields_ = [('dst', C.c_void_p), ('overlay', C.c_void_p), ('feed', C.c_void_p), ('twin', C.c_int), ('mode', C.c_int)]
 
@@ -222,6 +231,9 @@ SIGNATURES = {
     'rmem_polygon_simplify': (_i, [_vp, _vp, _vp, _ll, _ll, _i, _vp, C.c_size_t, _vp, _vp, _vp, _vp]),
     'rmem_polygon_fill_workspace_bytes': (C.c_size_t, [_ll]),
     'rmem_polygon_fill_labels': (_i, [_vp, _vp, _vp, _i, _vp, _i, _vp, _i, _i, _i, C.POINTER(PolyPass), _vp, C.c_size_t, _vp, _vp, _vp]),
+    'rmem_stroke_workspace_bytes': (C.c_size_t, [_i, _i, _i]),
+    'rmem_stroke_draw_labels': (_i, [_vp, _vp, _vp, _i, _vp, _i, _vp, _vp, _i, _i, _i, _i, C.POINTER(StrokePass), _vp, C.c_size_t, _vp, _i, _vp,
+                                     _vp]),
     'rmem_mask_iou_counts': (_i, [_vp, _vp, _ll, _i, _i, _vp, _vp]),
     'rmem_clip_score_workspace_bytes': (C.c_size_t, [_i, _i, _i, _i]),
     'rmem_boundary_radius': (_i, [_i, _i, C.c_double]),

@@ -592,6 +592,79 @@ def labels_from_seeds(seeds_u8: torch.Tensor, background: Optional[int] = None, 
     return out if b is None else out.masked_fill_(out == b, 0)
 
 
+def _seed_value(what: str, obj: int, positive: bool, background: Optional[int]) -> int:
+    if positive:
+        return _labels.int_in(what, 'an object id', obj, 1, 255)
+    if background is None:
+        raise _lib.RmemError(f'{what}: object {obj} has a negative seed: give background, labels_from_seeds\' value for negative seeds')
+    return background
+
+
+def seeds_from_scribbles(scribbles: Sequence[Dict[int, dict]], size: Tuple[int, int], device, radius: float = 0,
+                         background: Optional[int] = None) -> torch.Tensor:
+    """The uint8 [n, H, W] seed stack on `device` of next_scribbles' own output (per frame {object id: {'positive', 'path':
+    [k, 2] of (y, x), ...}}): what labels_from_seeds takes.  A positive scribble of object v draws value v, a negative one draws
+    `background` (1..255, labels_from_seeds' value for negative seeds; a negative scribble without it is refused).  Within a frame
+    the strokes are drawn in ascending object id, so where two cross the larger id shows.  radius (pixels, 0..256): 0 draws the
+    path's own pixels, anything larger a round brush.  Drawn on the device (strokes.draw_label_stack): only the paths cross to it."""
+    from . import strokes
+    what = 'evaluator.seeds_from_scribbles'
+    b = None if background is None else _labels.int_in(what, 'background', background, 1, 255, 'None or an integer in')
+    frames = []
+    for fr in scribbles:
+        listed = []
+        for v in sorted(fr):
+            path = np.asarray(fr[v]['path'], dtype=np.float64).reshape(-1, 2)[:, ::-1]          # (y, x) -> (x, y)
+            listed.append({'value': _seed_value(what, v, bool(fr[v]['positive']), b), 'path': path, 'radius': radius})
+        frames.append(listed)
+    return strokes.draw_label_stack(frames, size, device)
+
+
+def seeds_from_clicks(clicks, size: Tuple[int, int], device, radius: float = 0, background: Optional[int] = None) -> torch.Tensor:
+    """seeds_from_scribbles' twin for next_clicks' int32 [n, num_objs, 4] of (y, x, positive, d2): a dot (radius 0) or a disc per
+    click, value = the object id for a positive click and `background` for a negative one; rows of (-1, -1, 0, 0) draw nothing."""
+    from . import strokes
+    what = 'evaluator.seeds_from_clicks'
+    b = None if background is None else _labels.int_in(what, 'background', background, 1, 255, 'None or an integer in')
+    c = np.asarray(clicks)
+    if c.ndim != 3 or c.shape[2] != 4 or c.shape[0] < 1 or not np.issubdtype(c.dtype, np.integer):
+        raise _lib.RmemError(f'{what}: clicks must be an integer array [n, num_objs, 4] of (y, x, positive, d2) (got {c.dtype} {c.shape})')
+    frames = [[{'value': _seed_value(what, i + 1, bool(row[2]), b), 'path': [(int(row[1]), int(row[0]))], 'radius': radius}
+               for i, row in enumerate(fr) if row[0] >= 0 and row[1] >= 0] for fr in c]
+    return strokes.draw_label_stack(frames, size, device)
+
+
+def labels_from_scribbles(doc: Dict, size: Tuple[int, int], device, radius: float = 0, ids: Optional[Sequence] = None) -> torch.Tensor:
+    """The uint8 [n, H, W] stack of a DAVIS-interactive scribble document, {'scribbles': [[{'path': [[x, y], ...], 'object_id': k,
+    ...}, ...] per frame]} with coordinates in [0, 1]: points are scaled by (W - 1, H - 1) and truncated to integer pixels, as
+    the toolkit does; a scribble draws its object_id, or with ids the position of its object_id in ids plus one (scribbles of
+    other objects are left out), in the file's order.  radius as in seeds_from_scribbles.  The toolkit's Bezier smoothing and its
+    Bresenham lines are not reproduced: strokes.py's hairline rule is the specification.  Feeds labels_from_seeds, or with a brush
+    an add_reference_frame."""
+    from . import strokes
+    what = 'evaluator.labels_from_scribbles'
+    if not isinstance(doc, dict) or not isinstance(doc.get('scribbles'), (list, tuple)):
+        raise _lib.RmemError(f'{what}: doc must be a dict whose \'scribbles\' lists the scribbles of every frame')
+    H, W = int(size[0]), int(size[1])
+    value = None if ids is None else {k: i + 1 for i, k in enumerate(ids)}
+    frames = []
+    for f, fr in enumerate(doc['scribbles']):
+        listed = []
+        for s in fr:
+            if not isinstance(s, dict) or 'path' not in s or 'object_id' not in s:
+                raise _lib.RmemError(f'{what}: frame {f}: a scribble is a dict with \'path\' and \'object_id\'')
+            k = s['object_id']
+            if value is not None and k not in value:
+                continue
+            p = np.asarray(s['path'], dtype=np.float64).reshape(-1, 2)
+            if not ((p >= 0) & (p <= 1)).all():                       # also every NaN
+                raise _lib.RmemError(f'{what}: frame {f}, object {k}: path coordinates must lie in [0, 1]')
+            if len(p):
+                listed.append({'value': k if value is None else value[k], 'path': np.trunc(p * (W - 1, H - 1)), 'radius': radius})
+        frames.append(listed)
+    return strokes.draw_label_stack(frames, (H, W), device)
+
+
 def relabel_to_match(pred_u8: torch.Tensor, gt_u8: torch.Tensor, num_pred: int, num_gt: int):
     """Predictions whose ids are not the annotation's (another run, another squeeze order, an identity-free protocol) in the
     annotation's ids: (pred relabelled uint8 like pred_u8, mapping {pred id: gt id}, track IoU float64 [num_pred, num_gt]).
