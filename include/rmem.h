@@ -762,6 +762,55 @@ int rmem_label_nearest(const unsigned char* labels, int n, int H, int W, const u
                        const unsigned int fill_bits[8], int max_d2, int* index, int* dist2, unsigned char* taken, void* workspace,
                        long long workspace_bytes, void* stream);
 
+/* Geodesic nearest-site transform of uint8 label stacks over uint8 frames: rmem_label_nearest's image-aware twin, the same sites
+ * and the same three outputs under another metric (distance.py: geodesic_nearest, geodesic_grow; evaluator.
+ * labels_from_seeds_geodesic, fill_void_geodesic, snap_masks).  Integers only, no float on the device: bit-reproducible and
+ * independent of scheduling.
+ * labels: uint8 [n][H][W]; image: uint8 [n][H][W][C], C = channels = 1 or 3, interleaved (the layout rmem_overlay_rgb8 takes);
+ * both contiguous, device, may start at any byte, only read; frames are independent.  site_bits, fill_bits: HOST arrays of 256
+ * bits as rmem_label_nearest takes them (fill_bits NULL: every value); an empty site set is legal.  spatial in 1..64, colour in
+ * 0..64, max_cost -1 (no limit) or 0..2^30.  H and W at most 16384, H * W at most 2^26, n in 1..65535.
+ * THE GRAPH: the 8-connected pixel grid of a frame; the edge between neighbours p and q costs
+ *   w(p, q) = spatial * s + colour * sum over the channels c of |I_c(p) - I_c(q)|,   s = 5 for an axial step, 7 for a diagonal one
+ * (the 5-7 chamfer; colour = 0 is the plain chamfer distance).  An edge costs at most 64 * 7 + 64 * 765 = 49408; the straight
+ * chamfer path bounds every real cost by 16383 * 49408 < 2^30.
+ * key(p) = the lexicographic minimum over the frame's sites s of (the cost of the cheapest path s -> p, the flat index of s); a
+ * site's cost to itself is 0, so a site maps to itself.  Per pixel p of frame f, each output [n][H][W], each may be NULL (not all):
+ *   index[p] (int32)  the flat index y * W + x of that site; -1 where no site is within max_cost (a cost == max_cost still counts).
+ *   cost[p]  (int32)  its cost, 2^31 - 1 where index is -1.
+ *   taken[p] (uint8)  labels[f][index[p]] if labels[p] is in fill_bits and index[p] >= 0, else labels[p].  Must not overlap labels.
+ * The answer is unique: relaxing (cost, index) with the lexicographic minimum over the eight neighbours is a monotone system whose
+ * fixed point, reached from "no key anywhere but (0, own index) on the sites", is key; it does not depend on the order of
+ * relaxation, the tile or the number of rounds.  A candidate above max_cost is dropped where it arises (a prefix of a cheapest
+ * path is no dearer than the path).
+ * Three calls on one workspace of rmem_label_geodesic_workspace_bytes(n, H, W) bytes (0 for refused geometry), 16-byte aligned:
+ * two planes of 64-bit keys (cost << 32 | index; 2^31 - 1 and all ones: no key) and two sets of one byte per tile:
+ *   begin   writes plane 0 from labels and site_bits.  One launch.
+ *   rounds  runs the rounds first_round .. first_round + count - 1, one launch each; round r reads plane r & 1 and writes the other.
+ *           One workgroup per tile of th x tw pixels (rmem_label_geodesic_tile) and frame relaxes the tile inside LDS to the fixed
+ *           point for its one-pixel halo, or for a bounded number of passes, and writes one byte: its core changed.  changed int32
+ *           [n]: the number of tiles of frame f whose core changed in the call's LAST round (zeroed by the call, one integer atomic
+ *           per such tile).  All zero: plane (first_round + count) & 1 holds key.  A tile whose own byte and whose eight neighbours'
+ *           bytes of the round before are all 0 leaves at once, from round 1 on (RMEM_GEODESIC_SKIP=0 in the environment: never,
+ *           for A/B runs).  The caller continues with first_round + count, with the same image, weights and limit, until changed
+ *           is all zero: a call that reports a change lowered a key, and keys are bounded below.
+ *   finish  unpacks plane rounds & 1 (rounds: how many rounds have run) into the outputs, applying fill_bits and max_cost.  One
+ *           launch.  Before the fixed point the outputs are upper bounds of no further meaning.
+ * Every entry of every non-NULL output is written; prior contents of outputs and workspace do not matter at begin.  No host
+ * sync, no kernel waits for another workgroup.  Refused (non-zero, nothing launched): null labels (begin, finish), image or
+ * changed (rounds), site_bits (begin) or workspace; all three outputs NULL; taken == labels; channels other than 1 or 3; spatial,
+ * colour or max_cost out of range; n outside 1..65535, non-positive H / W, H * W above 2^26, H or W above 16384; negative
+ * first_round or rounds, count below 1, first_round + count beyond 31 bits; a workspace too small or misaligned. */
+int rmem_label_geodesic_tile(int* th, int* tw);   /* host only */
+long long rmem_label_geodesic_workspace_bytes(int n, int H, int W);   /* host only */
+int rmem_label_geodesic_begin(const unsigned char* labels, int n, int H, int W, const unsigned int site_bits[8], void* workspace,
+                              long long workspace_bytes, void* stream);
+int rmem_label_geodesic_rounds(const unsigned char* image, int channels, int n, int H, int W, int spatial, int colour, int max_cost,
+                               int first_round, int count, int* changed, void* workspace, long long workspace_bytes, void* stream);
+int rmem_label_geodesic_finish(const unsigned char* labels, int n, int H, int W, const unsigned int fill_bits[8], int max_cost, int rounds,
+                               int* index, int* cost, unsigned char* taken, const void* workspace, long long workspace_bytes,
+                               void* stream);
+
 /* Shape census of uint8 label stacks: raw moments, row extents and convex hulls (shapes.py: label_moments, row_extents,
  * convex_hulls, region_props; evaluator.object_shapes, object_centroids, rotated_boxes).  Integers only, integer atomics only:
  * bit-reproducible.  labels: uint8 [n][H][W], contiguous, device, may start at any byte and is only read.  x and y are a pixel's

@@ -208,6 +208,11 @@ SIGNATURES = {
     'rmem_label_edt_peaks': (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _ll, _vp]),
     'rmem_label_nearest_workspace_bytes': (_ll, [_i, _i, _i]),
     'rmem_label_nearest': (_i, [_vp, _i, _i, _i, C.POINTER(C.c_uint), C.POINTER(C.c_uint), _i, _vp, _vp, _vp, _vp, _ll, _vp]),
+    'rmem_label_geodesic_tile': (_i, [C.POINTER(_i), C.POINTER(_i)]),
+    'rmem_label_geodesic_workspace_bytes': (_ll, [_i, _i, _i]),
+    'rmem_label_geodesic_begin': (_i, [_vp, _i, _i, _i, C.POINTER(C.c_uint), _vp, _ll, _vp]),
+    'rmem_label_geodesic_rounds': (_i, [_vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _ll, _vp]),
+    'rmem_label_geodesic_finish': (_i, [_vp, _i, _i, _i, C.POINTER(C.c_uint), _i, _i, _vp, _vp, _vp, _vp, _ll, _vp]),
     'rmem_label_moments': (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp]),
     'rmem_label_hull_count': (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp]),
     'rmem_label_hull_offsets': (_i, [_vp, _i, _vp]),

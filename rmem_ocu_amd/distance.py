@@ -1,10 +1,11 @@
 """Exact Euclidean distance transform of label stacks on the device, and what is built on it: the peaks of a distance map per
 key value, and the Hausdorff distance of every object of two stacks (include/rmem.h: rmem_label_edt, rmem_label_edt_peaks); and
 the nearest-site feature transform, which says WHICH pixel the nearest site is and reads the label there (rmem_label_nearest:
-nearest, grow).
+nearest, grow), with its image-aware twin, whose metric is the cheapest path through the frame's pixel grid
+(rmem_label_geodesic_*: geodesic_nearest, geodesic_grow).
 
-All distances are SQUARED distances between pixel centres as int32: exact, no float anywhere on the device.  2^31 - 1 (SENTINEL)
-stands where there is nothing to measure a distance to.  Everything runs on the current stream; the stacks never leave the device.
+All distances are SQUARED distances between pixel centres as int32 (the geodesic twin's are integer path costs): exact, no float
+anywhere on the device.  2^31 - 1 (SENTINEL) stands where there is nothing to measure a distance to.  Everything runs on the current stream; the stacks never leave the device.
 """
 from __future__ import annotations
 
@@ -231,4 +232,137 @@ def grow(labels_u8: torch.Tensor, fill=(0,), sites=None, max_distance: Optional[
         if out.data_ptr() == a.data_ptr():
             raise RmemError(f'{what}: out must not be the labels (they are read at the nearest site while out is written)')
     _nearest(a, s, f, d2max, None, None, taken, torch.cuda.current_stream(a.device))
+    return taken.view(labels_u8.shape) if out is None else out
+
+
+# ------------------------------------------------------------------------------------------------- geodesic nearest site, grow
+MAX_COST = 2 ** 30                           # csrc/label_geodesic.hip: kMaxCost, above every real path cost
+
+
+def geodesic_tile() -> Tuple[int, int]:
+    """(th, tw): the core tile of a round of the geodesic transform"""
+    th, tw = C.c_int(), C.c_int()
+    _lib.check(_lib.lib().rmem_label_geodesic_tile(C.byref(th), C.byref(tw)), 'rmem_label_geodesic_tile')
+    return th.value, tw.value
+
+
+def _image(what: str, image_u8, labels_u8: torch.Tensor, a: torch.Tensor) -> Tuple[torch.Tensor, int]:
+    """(the frames as [n, H, W, C], C) of the image that goes with labels_u8 (whose stack view is a): [n, H, W] grey or
+    [n, H, W, C] with stacked labels, [H, W] or [H, W, C] with 2-D ones; C is 1 or 3"""
+    if not isinstance(image_u8, torch.Tensor) or image_u8.dtype != torch.uint8:
+        raise RmemError(f'{what}: image must be a uint8 tensor')
+    if image_u8.device != a.device:
+        raise RmemError(f'{what}: image must be on the labels\' device (got {image_u8.device} and {a.device})')
+    ls = tuple(labels_u8.shape)
+    if tuple(image_u8.shape) == ls:
+        channels = 1
+    elif image_u8.dim() == len(ls) + 1 and tuple(image_u8.shape[:-1]) == ls and image_u8.shape[-1] in (1, 3):
+        channels = int(image_u8.shape[-1])
+    else:
+        raise RmemError(f'{what}: image must have the labels\' shape {ls}, grey, or that with 1 or 3 interleaved channels after it '
+                        f'(got {tuple(image_u8.shape)})')
+    if not image_u8.is_contiguous():
+        raise RmemError(f'{what}: image must be contiguous')
+    return image_u8.view(a.shape + (channels,)), channels
+
+
+def _cost_limit(what: str, max_cost) -> int:
+    return -1 if max_cost is None else int_in(what, 'max_cost', max_cost, 0, MAX_COST, 'None or an integer in')
+
+
+def _geodesic(what, a, img, channels, sites, fill, spatial, colour, limit, index, cost, taken, batch, workspace_bytes, info):
+    """begin, calls of `batch` rounds until no tile of a call's last round changed, finish; in passes of as many frames as fit"""
+    n, H, W = a.shape
+    L = _lib.lib()
+    per_frame = int(L.rmem_label_geodesic_workspace_bytes(1, H, W))
+    k = frames_per_pass(what, n, per_frame, workspace_bytes, 'one frame\'s need')[1]
+    stream = torch.cuda.current_stream(a.device)
+    ws = workspace('geodesic', a.device, stream, int(L.rmem_label_geodesic_workspace_bytes(k, H, W)))
+    changed = torch.empty(k, dtype=torch.int32, device=a.device)
+    sbits, fbits = _bits(sites), None if fill is None else _bits(fill)
+    if isinstance(info, dict):
+        info.update(rounds=0, calls=0, passes=[])
+    for f0 in range(0, n, k):
+        la, im = a[f0:f0 + k], img[f0:f0 + k]
+        m = la.shape[0]
+        need = int(L.rmem_label_geodesic_workspace_bytes(m, H, W))
+        _lib.check(L.rmem_label_geodesic_begin(la.data_ptr(), m, H, W, sbits, ws.data_ptr(), need, stream.cuda_stream), 'rmem_label_geodesic_begin')
+        rounds = calls = 0
+        while True:
+            _lib.check(L.rmem_label_geodesic_rounds(im.data_ptr(), channels, m, H, W, spatial, colour, limit, rounds, batch, changed.data_ptr(),
+                                                    ws.data_ptr(), need, stream.cuda_stream), 'rmem_label_geodesic_rounds')
+            rounds, calls = rounds + batch, calls + 1
+            if not changed[:m].cpu().any():                                # the one readback of the call
+                break
+            if rounds > H * W + batch:                                     # every round that changes something makes a pixel final
+                raise RmemError(f'{what}: the rounds did not come to rest after {rounds} rounds on frames of {H} x {W}')
+        out = [None if t is None else t[f0:f0 + k].data_ptr() for t in (index, cost, taken)]
+        _lib.check(L.rmem_label_geodesic_finish(la.data_ptr(), m, H, W, fbits, limit, rounds, out[0], out[1], out[2], ws.data_ptr(), need,
+                                                stream.cuda_stream), 'rmem_label_geodesic_finish')
+        if isinstance(info, dict):
+            info['rounds'] += rounds
+            info['calls'] += calls
+            info['passes'].append({'frames': m, 'rounds': rounds, 'calls': calls})
+    for t in (a, img, index, cost, taken):
+        if t is not None:
+            t.record_stream(stream)
+
+
+def _geodesic_args(what, labels_u8, image_u8, spatial, colour, max_cost, batch):
+    sp, co = int_in(what, 'spatial', spatial, 1, 64), int_in(what, 'colour', colour, 0, 64)
+    limit = _cost_limit(what, max_cost)
+    b = int_in(what, 'batch', batch, 1, 2 ** 20)
+    a = _frames(what, labels_u8)
+    geometry(what, a)
+    img, channels = _image(what, image_u8, labels_u8, a)
+    return a, img, channels, sp, co, limit, b
+
+
+def geodesic_nearest(labels_u8: torch.Tensor, image_u8: torch.Tensor, sites, spatial: int = 1, colour: int = 1, max_cost: Optional[int] = None,
+                     return_cost: bool = True, batch: int = 8, workspace_bytes: Optional[int] = None,
+                     info: Optional[dict] = None) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
+    """(index, cost), both int32 on the device and shaped like labels_u8 ([n, H, W] or [H, W]); cost is None with
+    return_cost=False.  nearest's image-aware twin: the SITES are the pixels whose value is in `sites`, but the nearest one is the
+    site with the cheapest path through the 8-connected pixel grid, where the step between neighbours p and q costs
+        spatial * s + colour * sum over the channels of |I(p) - I(q)|,   s = 5 for an axial step, 7 for a diagonal one
+    (integers: spatial in 1..64, colour in 0..64; colour = 0 is the 5-7 chamfer distance).
+      index  the flat index y * W + x, within its frame, of the site with the smallest (cost, index); -1 where no site is within
+             max_cost.  A site maps to itself.
+      cost   that cost, SENTINEL where index is -1.
+    image_u8: uint8, contiguous, on the labels' device: the labels' shape (grey) or that with 1 or 3 interleaved channels after it
+    ([n, H, W, 3]: what jpeg.overlay takes).  max_cost: None or an integer in 0..2^30; a cost == max_cost still counts, and tiles
+    no front reaches do no work.  The transform runs in rounds over tiles (geodesic_tile): calls of `batch` rounds until no tile
+    changed in a call's last round, one readback of 4 bytes per frame per call; a call that reports a change lowered a key and
+    keys are bounded below, so the loop ends.  The result does not depend on batch.  The two key planes (16 bytes per pixel)
+    live in a workspace per (device, stream) of as many frames as fit workspace_bytes (default: 256 MiB, or one frame's need
+    where that is larger); a longer stack goes through in passes.  info, a dict, receives {'rounds': rounds launched, 'calls':
+    calls of rounds, 'passes': [per pass]}.  H and W at most 16384.  The current stream."""
+    what = 'distance.geodesic_nearest'
+    s = _value_set(what, 'sites', sites)
+    a, img, channels, sp, co, limit, b = _geodesic_args(what, labels_u8, image_u8, spatial, colour, max_cost, batch)
+    index = torch.empty(a.shape, dtype=torch.int32, device=a.device)
+    cost = torch.empty(a.shape, dtype=torch.int32, device=a.device) if return_cost else None
+    _geodesic(what, a, img, channels, s, None, sp, co, limit, index, cost, None, b, workspace_bytes, info)
+    return index.view(labels_u8.shape), None if cost is None else cost.view(labels_u8.shape)
+
+
+def geodesic_grow(labels_u8: torch.Tensor, image_u8: torch.Tensor, fill=(0,), sites=None, spatial: int = 1, colour: int = 1,
+                  max_cost: Optional[int] = None, out: Optional[torch.Tensor] = None, batch: int = 8, workspace_bytes: Optional[int] = None,
+                  info: Optional[dict] = None) -> torch.Tensor:
+    """uint8 stack like labels_u8 on the device: grow under geodesic_nearest's metric.  Every pixel whose value is in `fill` takes
+    the value of the site with the smallest (cost, index) if one is within max_cost; every other pixel keeps its value.  sites:
+    None: every value not in `fill`.  A region grown from a seed stops where the frame changes, not halfway to the next seed.
+    out: None allocates; a contiguous uint8 device tensor of the labels' shape that is not the labels is written.  image_u8,
+    spatial, colour, max_cost, batch, workspace_bytes, info: as geodesic_nearest."""
+    what = 'distance.geodesic_grow'
+    f = _value_set(what, 'fill', fill)
+    s = frozenset(range(256)) - f if sites is None else _value_set(what, 'sites', sites)
+    a, img, channels, sp, co, limit, b = _geodesic_args(what, labels_u8, image_u8, spatial, colour, max_cost, batch)
+    if out is None:
+        taken = torch.empty(a.shape, dtype=torch.uint8, device=a.device)
+    else:
+        taken = like_labels(what, out, 'out', torch.uint8, labels_u8, a)
+        if out.data_ptr() == a.data_ptr():
+            raise RmemError(f'{what}: out must not be the labels (they are read at the winning site while out is written)')
+    _geodesic(what, a, img, channels, s, f, sp, co, limit, None, None, taken, b, workspace_bytes, info)
     return taken.view(labels_u8.shape) if out is None else out

@@ -44,6 +44,10 @@ Mirrors what networks/managers/evaluator.py:330-568 does for one sequence, witho
     first site in raster order), and with the label read there objects grow without overlap, void pixels take the nearest real
     value and sparse seeds become a full label map -- rmem_label_nearest, distance.nearest / grow, expand_masks, fill_void,
     labels_from_seeds;
+  * the same with the frame in view: the nearest site by the cheapest path through the pixel grid, whose steps cost by how much
+    the picture changes (integers, bit-identical to a host Dijkstra), so seeds grow up to an object's edge, a void rim is split
+    along it and the boundaries of delivered labels snap to it -- rmem_label_geodesic_begin / _rounds / _finish,
+    distance.geodesic_nearest / geodesic_grow, labels_from_seeds_geodesic, fill_void_geodesic, snap_masks;
   * what shape an object has -- centroid, orientation, axis lengths, solidity, convex hull, VOT's rotated box -- comes from one pass
     over the labels by image rows (exact 64-bit moments, the x extent of every object on every row) and a hull built from those
     extents alone -- rmem_label_moments, rmem_label_hull_count / _offsets / _write, shapes.py, object_shapes, object_centroids,
@@ -590,6 +594,54 @@ def labels_from_seeds(seeds_u8: torch.Tensor, background: Optional[int] = None, 
     b = None if background is None else _labels.int_in(what, 'background', background, 1, 255, 'None or an integer in')
     out = grow(seeds_u8, fill=(0,), sites=None, max_distance=max_distance)
     return out if b is None else out.masked_fill_(out == b, 0)
+
+
+def labels_from_seeds_geodesic(seeds_u8: torch.Tensor, image_u8: torch.Tensor, spatial: int = 1, colour: int = 1,
+                               background: Optional[int] = None, max_cost: Optional[int] = None) -> torch.Tensor:
+    """labels_from_seeds with the image-aware partition: every pixel of value 0 takes the value of the seed with the CHEAPEST PATH
+    to it through the frame (distance.geodesic_grow: a step costs spatial * (5 or 7) + colour * the summed absolute difference of
+    the two pixels), ties to the seed that comes first in raster order.  A click inside an object claims the object up to its
+    edge, not everything nearer to it than to the next click.  image_u8: the frames, uint8 on the seeds' device, the seeds' shape
+    (grey) or that with 1 or 3 interleaved channels after it.  background: as labels_from_seeds, negative seeds claim their region
+    and are then written as 0.  max_cost: pixels no seed reaches within it stay 0.  A frame without seeds is returned as it is."""
+    from .distance import geodesic_grow
+    what = 'evaluator.labels_from_seeds_geodesic'
+    b = None if background is None else _labels.int_in(what, 'background', background, 1, 255, 'None or an integer in')
+    out = geodesic_grow(seeds_u8, image_u8, fill=(0,), sites=None, spatial=spatial, colour=colour, max_cost=max_cost)
+    return out if b is None else out.masked_fill_(out == b, 0)
+
+
+def fill_void_geodesic(labels_u8: torch.Tensor, image_u8: torch.Tensor, void: int = 255, spatial: int = 1, colour: int = 1,
+                       max_cost: Optional[int] = None) -> torch.Tensor:
+    """fill_void's image-aware twin: every pixel of value `void` becomes the other value, background included, with the cheapest
+    path to it through the frame (distance.geodesic_grow), so a void rim round an object is split along the frame's edge inside
+    it, not down its middle.  max_cost: void pixels nothing reaches within it stay void; a frame of nothing but void stays as it
+    is."""
+    from .distance import geodesic_grow
+    v = _labels.int_in('evaluator.fill_void_geodesic', 'void', void, 0, 255)
+    return geodesic_grow(labels_u8, image_u8, fill=(v,), sites=None, spatial=spatial, colour=colour, max_cost=max_cost)
+
+
+def snap_masks(labels_u8: torch.Tensor, image_u8: torch.Tensor, band: float, unknown: int = 255, keep_thin: bool = True, spatial: int = 1,
+               colour: int = 1) -> torch.Tensor:
+    """A new uint8 stack like labels_u8 whose boundaries have moved to the frame's edges within a band: every pixel whose squared
+    distance to the nearest pixel of another value (distance.label_edt(labels, border=False)) is at most int(band^2) becomes
+    `unknown`, pixels already `unknown` stay so, and distance.geodesic_grow(fill=(unknown,), sites=None) regrows the band from what
+    is left.  keep_thin: the pixels of skeleton.thin(labels) keep their value, so an object thinner than the band keeps a core
+    and does not vanish.  band: 1..63 pixels.  Like clean_masks, something the caller applies to the labels a run delivered:
+    nothing here feeds it back into a memory bank.  image_u8, spatial, colour: as distance.geodesic_grow."""
+    from .distance import geodesic_grow, label_edt
+    from .skeleton import thin
+    what = 'evaluator.snap_masks'
+    if isinstance(band, bool) or not isinstance(band, (int, float, np.integer, np.floating)) or not 1 <= band <= 63:
+        raise _lib.RmemError(f'{what}: band must be a number in 1..63 (got {band!r})')
+    u = _labels.int_in(what, 'unknown', unknown, 0, 255)
+    a = _labels.stack(what, labels_u8)
+    near = label_edt(a, border=False) <= int(float(band) * float(band))
+    if keep_thin:
+        near &= thin(a) == 0
+    cut = a.masked_fill(near, u).view(labels_u8.shape)
+    return geodesic_grow(cut, image_u8, fill=(u,), sites=None, spatial=spatial, colour=colour)
 
 
 def _seed_value(what: str, obj: int, positive: bool, background: Optional[int]) -> int:
