@@ -127,6 +127,20 @@ typedef struct rmem_bneck_chain_desc { int batch, Ho, Wo, K1, Cout, N2, H2, W2, 
 int rmem_bneck_chain(const rmem_bneck_chain_desc* desc, const void* b, const void* x2, const void* w3, const float* bias3, const void* res,
                      void* y, const void* w1, const float* bias1, void* a2, void* stream);
 
+/* A whole ResNet bottleneck with planes = 64 and stride 1 (layer 1) in one launch, NHWC (csrc/bneck_block.hip):
+ *   a = relu(conv1x1(x; w1, bias1)), b = relu(conv3x3(a; w2, bias2)) with pad 1 (a is padded with zeros),
+ *   Cin = 256, identity form:   y = relu(b . w3^T + bias3 + x), w3 [256][64];
+ *   Cin = 64, projection form:  y = relu([b | x] . w3^T + bias3), w3 the packed [256][64 + 64] of rmem_conv1x1_dual_nhwc;
+ *   N2 = 128 (identity form only), tail: a_next = relu(y . w1n^T + bias1n), w1n [128][256], y rounded as stored; N2 = 0: w1n,
+ *   bias1n and a_next are NULL.
+ * x [images][H][W][Cin], w1 [64][Cin], w2 [64][3][3][64], y [images][H][W][256], a_next [images][H][W][128].  It replaces the
+ * launch list rmem_conv2d_nhwc (1x1) + rmem_conv3x3_direct + rmem_conv2d_nhwc with residual / rmem_conv1x1_dual_nhwc
+ * (+ rmem_conv2d_nhwc for the tail), or the rmem_bneck_chain form of it (encoder_batch.py), and is bit-identical to both.
+ * The environment variable RMEM_BNECK_ROWS forces the rows a workgroup walks down (tests); results do not depend on it. */
+typedef struct rmem_bneck_block_desc { int images, H, W, Cin, N2; } rmem_bneck_block_desc;
+int rmem_bneck_block64(const rmem_bneck_block_desc* desc, const void* x, const void* w1, const float* bias1, const void* w2, const float* bias2,
+                       const void* w3, const float* bias3, void* y, const void* w1n, const float* bias1n, void* a_next, void* stream);
+
 /* ------------------------------------------------------------------ memory-read attention
  * out[q, 32h:32h+32] = softmax_k( (Q[q,h]+pe_cur[h]) . (K[k,h]+pe_mem[slot(k),h]) / sqrt(32) ) V[k,h]
  * over the keys named by the chunk table, plus (optionally) the per-memory-frame probability mass
@@ -1433,6 +1447,7 @@ int rmem_lstt_chain_b_f16(const rmem_chain_b_desc* d, void* stream);
 int rmem_lstt_chain_b_merged_f16(const rmem_chain_b_desc* d, const rmem_attn_merge* merge, void* stream);
 int rmem_lstt_chain_c_f16(const rmem_chain_c_desc* d, void* stream);
 int rmem_layernorm256_pair_f16(const void* a0, const void* b0, void* y0, const void* a1, const void* b1, void* y1, const float* gamma, const float* beta, float eps, int M, void* stream);
+int rmem_bneck_block64_f16(const rmem_bneck_block_desc* desc, const void* x, const void* w1, const float* bias1, const void* w2, const float* bias2, const void* w3, const float* bias3, void* y, const void* w1n, const float* bias1n, void* a_next, void* stream);
 int rmem_bneck_chain_f16(const rmem_bneck_chain_desc* desc, const void* b, const void* x2, const void* w3, const float* bias3, const void* res, void* y, const void* w1, const float* bias1, void* a2, void* stream);
 int rmem_conv1x1_dual_nhwc_f16(const rmem_conv_desc* desc, const void* x, const void* x2, int H2, int W2, int Cin2, int stride2, const void* w_cat, const float* bias, void* y, void* stream);
 int rmem_linear_grouped_f16(const rmem_conv_desc* desc, int n, const void* const* x, const void* const* w, const float* const* bias, const void* const* residual, void* const* y, void* stream);

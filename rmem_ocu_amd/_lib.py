@@ -37,6 +37,10 @@ class BneckChainDesc(C.Structure):
     _fields_ = [(n, C.c_int) for n in ('batch', 'Ho', 'Wo', 'K1', 'Cout', 'N2', 'H2', 'W2', 'Cin2', 'stride2')]
 
 
+class BneckBlockDesc(C.Structure):
+    _fields_ = [(n, C.c_int) for n in ('images', 'H', 'W', 'Cin', 'N2')]
+
+
 class AttnChunk(C.Structure):
     _fields_ = [('slot', C.c_int), ('key_begin', C.c_int), ('key_count', C.c_int), ('pe_slot', C.c_int),
                 ('t', C.c_int), ('reserved', C.c_int * 3)]
@@ -152,6 +156,7 @@ SIGNATURES = {
     'rmem_lstt_chain_c': (_i, [C.POINTER(ChainC), _vp]),
     'rmem_conv1x1_dual_nhwc': (_i, [C.POINTER(ConvDesc), _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
     'rmem_bneck_chain': (_i, [C.POINTER(BneckChainDesc), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    'rmem_bneck_block64': (_i, [C.POINTER(BneckBlockDesc), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     'rmem_linear_grouped': (_i, [C.POINTER(ConvDesc), _i, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), _vp]),
     'rmem_groupnorm_workspace_bytes': (C.c_size_t, [_i]),
     'rmem_groupnorm_nhwc': (_i, [_vp, _i, _i, _i, _vp, _vp, _f, _i, _vp, _vp, _vp]),
@@ -287,7 +292,7 @@ SIGNATURES = {
 
 # entry points with 16-bit operands exist twice: <name> (bfloat16) and <name>_f16 (IEEE half), same signature (include/rmem.h)
 F16_TWINS = ('rmem_conv2d_nhwc', 'rmem_mem_read_attn', 'rmem_mem_read_attn_clips', 'rmem_lstt_attn_pair_clips', 'rmem_lstt_attn_pair_clips_deferred', 'rmem_layernorm256', 'rmem_layernorm', 'rmem_patch_merge_ln',
-             'rmem_window_attn', 'rmem_window_attn_images', 'rmem_patch_merge_ln_images', 'rmem_add16', 'rmem_add16_grouped', 'rmem_layernorm256_pair', 'rmem_lstt_chain_a', 'rmem_lstt_chain_b', 'rmem_lstt_chain_b_merged', 'rmem_lstt_chain_c', 'rmem_conv1x1_dual_nhwc', 'rmem_bneck_chain', 'rmem_label_id_embed', 'rmem_image_ptrs_to_nhwc4p', 'rmem_stem7x7s2', 'rmem_stem7x7s2_pool', 'rmem_conv3x3_c64_direct', 'rmem_conv3x3_direct', 'rmem_linear_grouped',
+             'rmem_window_attn', 'rmem_window_attn_images', 'rmem_patch_merge_ln_images', 'rmem_add16', 'rmem_add16_grouped', 'rmem_layernorm256_pair', 'rmem_lstt_chain_a', 'rmem_lstt_chain_b', 'rmem_lstt_chain_b_merged', 'rmem_lstt_chain_c', 'rmem_conv1x1_dual_nhwc', 'rmem_bneck_chain', 'rmem_bneck_block64', 'rmem_label_id_embed', 'rmem_image_ptrs_to_nhwc4p', 'rmem_stem7x7s2', 'rmem_stem7x7s2_pool', 'rmem_conv3x3_c64_direct', 'rmem_conv3x3_direct', 'rmem_linear_grouped',
              'rmem_groupnorm_nhwc', 'rmem_groupnorm_f32_nhwc', 'rmem_groupnorm_nhwc_images', 'rmem_groupnorm_head_nhwc_images',
              'rmem_gn_act_dwconv5x5_nhwc_images', 'rmem_gn_act_dwconv5x5_prestats_nhwc_images', 'rmem_gn_act_dwconv5x5_nhwc', 'rmem_dwconv5x5_nhwc', 'rmem_image_to_nhwc8',
              'rmem_image_to_nhwc8_images', 'rmem_image_ptrs_to_nhwc8', 'rmem_ingest_rgb8', 'rmem_maxpool3x3s2_nhwc', 'rmem_maxpool3x3s2_nhwc_images', 'rmem_bilinear_nhwc',

@@ -99,6 +99,9 @@ class BatchEncoder(_PtrInput):
         if nsplit < 1 or B % nsplit:
             nsplit = 1
         chain_on = os.environ.get('RMEM_NO_BNECK_CHAIN', '0') != '1'
+        # layer 1: every bottleneck is ONE launch (rmem_bneck_block64: the block's input read once, its output written once, the 64-channel
+        # maps never leave the CU), the last one with layer 2's first conv1 as its tail; RMEM_NO_BNECK_BLOCK=1 restores the chained list
+        block_on = chain_on and os.environ.get('RMEM_NO_BNECK_BLOCK', '0') != '1'
         # layer 1 (64 channels); the 128-channel form (layer 2) is faster alone (57.3 -> 43.5 us) but takes a whole CU's LDS per workgroup
         # and measured neutral in the pipeline: opt-in (RMEM_DIRECT_CONV3_128=1)
         direct3 = () if os.environ.get('RMEM_NO_DIRECT_CONV3', '0') == '1' else ((64, 128) if os.environ.get('RMEM_DIRECT_CONV3_128') == '1' else (64,))
@@ -152,6 +155,20 @@ class BatchEncoder(_PtrInput):
                 abuf = self.mid_a128 if (nsplit > 1 and li == 2 and bi == 0) else self.mid_a
                 a = sub(abuf, h * w * planes, b0, nb)
                 bb = sub(self.mid_b, ho * wo * planes, b0, nb)
+                dual = (p + '.c3ds.w') in P
+                nxt = blocks[idx + 1] if idx + 1 < len(blocks) else None
+                if block_on and li == 1 and s == 1 and not conv1_done and cin == (64 if dual else 256):
+                    kw = {}
+                    if nxt == (2, 0):      # the tail: layer 2's first conv1 (128 planes) reads the y tile in place
+                        pn = 'encoder.layer2.0'
+                        nbuf = self.mid_a128 if nsplit > 1 else self.mid_a
+                        kw = dict(w1n=P[pn + '.conv1.w'], bias1n=P[pn + '.conv1.b'], a_next=sub(nbuf, ho * wo * 128, b0, nb))
+                        conv1_done = True
+                    q.append(ops.bneck_block64(xs, P[p + '.conv1.w'], P[p + '.conv1.b'], P[p + '.conv2.w'], P[p + '.conv2.b'],
+                                               P[p + ('.c3ds.w' if dual else '.conv3.w')], P[p + ('.c3ds.b' if dual else '.conv3.b')], y,
+                                               H=h, W=w, Cin=cin, images=nb, **kw))
+                    x, (h, w), cin = outs[li - 1][bi % 2], (ho, wo), planes * 4
+                    continue
                 if not conv1_done:
                     q.append(conv(xs, P[p + '.conv1.w'], P[p + '.conv1.b'], a, H=h, W=w, Cin=cin, Cout=planes, relu=True))
                 conv1_done = False
@@ -160,8 +177,6 @@ class BatchEncoder(_PtrInput):
                 else:
                     q.append(conv(a, P[p + '.conv2.w'], P[p + '.conv2.b'], bb, H=h, W=w, Cin=planes, Cout=planes, KH=3, KW=3, stride=s, pad=1,
                                   relu=True))
-                dual = (p + '.c3ds.w') in P
-                nxt = blocks[idx + 1] if idx + 1 < len(blocks) else None
                 if chain_on and li == 1 and nxt is not None:
                     # layer 1 (256-channel maps at stride 4: HBM-bound at these batch sizes): a block's conv3 + shortcut is chained into the
                     # NEXT block's conv1 in one launch (rmem_bneck_chain): the 256-channel map is written once, not read back by that conv1

@@ -143,6 +143,28 @@ def bneck_chain(b, w3, bias3, y, w1, bias1, a2, *, H, W, K1, N2, residual=None, 
     return Op(_fn('rmem_bneck_chain', dt), args, 'rmem_bneck_chain', (d, b, x2, w3, bias3, residual, y, w1, bias1, a2))
 
 
+def bneck_block64(x, w1, bias1, w2, bias2, w3, bias3, y, *, H, W, Cin, images, w1n=None, bias1n=None, a_next=None) -> Op:
+    """A whole planes = 64, stride 1 bottleneck in one launch: a = relu(conv1x1(x)), b = relu(conv3x3(a)), then
+    Cin = 256: y = relu(b @ w3^T + bias3 + x) (w3 [256, 64]); Cin = 64: y = relu([b | x] @ w3^T + bias3) (w3 the packed [256, 128]).
+    With w1n [128, 256], bias1n and a_next (Cin = 256 only) also a_next = relu(y @ w1n^T + bias1n).  x [images*H*W, Cin], y [.., 256]."""
+    _dev(x, w1, bias1, w2, bias2, w3, bias3, y, w1n, bias1n, a_next)
+    dt = w1.dtype
+    M = images * H * W
+    tail = w1n is not None
+    assert Cin in (64, 256) and (not tail or Cin == 256) and (bias1n is not None) == tail and (a_next is not None) == tail
+    assert all(t.dtype == dt for t in (x, w2, w3, y)) and all(t.dtype == F32 for t in (bias1, bias2, bias3))
+    assert w1.is_contiguous() and w2.is_contiguous() and w3.is_contiguous()
+    assert w1.numel() == 64 * Cin and w2.numel() == 64 * 9 * 64 and w3.numel() == 256 * (64 if Cin == 256 else 128)
+    assert bias1.numel() == 64 and bias2.numel() == 64 and bias3.numel() == 256
+    assert x.numel() >= M * Cin and y.numel() >= M * 256
+    if tail:
+        assert w1n.dtype == dt and a_next.dtype == dt and bias1n.dtype == F32 and w1n.is_contiguous()
+        assert w1n.numel() == 128 * 256 and bias1n.numel() == 128 and a_next.numel() >= M * 128
+    d = _lib.BneckBlockDesc(images, H, W, Cin, 128 if tail else 0)
+    args = (C.byref(d), _ptr(x), _ptr(w1), _ptr(bias1), _ptr(w2), _ptr(bias2), _ptr(w3), _ptr(bias3), _ptr(y), _ptr(w1n), _ptr(bias1n), _ptr(a_next))
+    return Op(_fn('rmem_bneck_block64', dt), args, 'rmem_bneck_block64', (d, x, w1, bias1, w2, bias2, w3, bias3, y, w1n, bias1n, a_next))
+
+
 def linear(x, w, bias, y, *, M, K, N, residual=None, y2=None, relu=False, ldo=None, ldr=None, ld2=None, ws=None, ldx=0,
            act_begin=0) -> Op:
     """y[M, N] = x[M, K] @ w[N, K]^T + bias: the 1x1 case of conv2d (x rows of stride ldx, default K)."""
