@@ -117,11 +117,11 @@ int rmem_conv1x1_dual_nhwc(const rmem_conv_desc* desc, const void* x, const void
 
 /* The tail of a ResNet bottleneck chained into the FIRST 1x1 convolution of the following block, one launch
  * (encoders/resnet.py:62-68 of block i, then :48-50 of block i + 1 -- or of the next layer's first block):
- *   y  = relu(b . w3^T + bias3 + res)      b [M][K1] (the 3x3 conv's output), w3 [Cout = 256][K1], res / y [M][256], M = batch * Ho * Wo
- *   a2 = relu(y . w1^T + bias1)            w1 [N2][256], a2 [M][N2], N2 = 64 or 128
+ *   y  = relu(b . w3^T + bias3 + res)      b [M][K1] (the 3x3 conv's output), w3 [Cout][K1], res / y [M][Cout], M = batch * Ho * Wo
+ *   a2 = relu(y . w1^T + bias1)            w1 [N2][Cout], a2 [M][N2]; Cout = 256 with N2 = 64 or 128, or Cout = 512 with N2 = 128 or 256
  * y is stored (later blocks need it as their shortcut) but never read back: its 64-row tile stays in LDS, rounded as stored, as the
- * A operand of the second GEMM.  Dual form (x2 != NULL, res == NULL; the block with the strided 1x1 shortcut, as
- * rmem_conv1x1_dual_nhwc): y = relu([b | x2 sampled at stride2] . w3^T + bias3) with w3 [256][K1 + Cin2], x2 NHWC [batch][H2][W2][Cin2].
+ * A operand of the second GEMM (Cout = 512: in two column chunks of 256, the second GEMM's accumulators persisting).  Dual form (x2 != NULL, res == NULL; the block with the strided 1x1 shortcut, as
+ * rmem_conv1x1_dual_nhwc): y = relu([b | x2 sampled at stride2] . w3^T + bias3) with w3 [Cout][K1 + Cin2], x2 NHWC [batch][H2][W2][Cin2].
  * Bit-identical to rmem_conv2d_nhwc (or rmem_conv1x1_dual_nhwc) followed by rmem_conv2d_nhwc.  K1, Cin2 multiples of 64. */
 typedef struct rmem_bneck_chain_desc { int batch, Ho, Wo, K1, Cout, N2, H2, W2, Cin2, stride2; } rmem_bneck_chain_desc;
 int rmem_bneck_chain(const rmem_bneck_chain_desc* desc, const void* b, const void* x2, const void* w3, const float* bias3, const void* res,

@@ -102,6 +102,9 @@ class BatchEncoder(_PtrInput):
         # layer 1: every bottleneck is ONE launch (rmem_bneck_block64: the block's input read once, its output written once, the 64-channel
         # maps never leave the CU), the last one with layer 2's first conv1 as its tail; RMEM_NO_BNECK_BLOCK=1 restores the chained list
         block_on = chain_on and os.environ.get('RMEM_NO_BNECK_BLOCK', '0') != '1'
+        # layer 2 (512-channel maps at stride 8, 107 MB each at 16 frames): its four links 2.0 -> 2.1 ... 2.3 -> 3.0 are chained like
+        # layer 1's were; RMEM_NO_BNECK_CHAIN2=1 restores the separate launches
+        chain2_on = chain_on and os.environ.get('RMEM_NO_BNECK_CHAIN2', '0') != '1'
         # layer 1 (64 channels); the 128-channel form (layer 2) is faster alone (57.3 -> 43.5 us) but takes a whole CU's LDS per workgroup
         # and measured neutral in the pipeline: opt-in (RMEM_DIRECT_CONV3_128=1)
         direct3 = () if os.environ.get('RMEM_NO_DIRECT_CONV3', '0') == '1' else ((64, 128) if os.environ.get('RMEM_DIRECT_CONV3_128') == '1' else (64,))
@@ -177,16 +180,17 @@ class BatchEncoder(_PtrInput):
                 else:
                     q.append(conv(a, P[p + '.conv2.w'], P[p + '.conv2.b'], bb, H=h, W=w, Cin=planes, Cout=planes, KH=3, KW=3, stride=s, pad=1,
                                   relu=True))
-                if chain_on and li == 1 and nxt is not None:
-                    # layer 1 (256-channel maps at stride 4: HBM-bound at these batch sizes): a block's conv3 + shortcut is chained into the
-                    # NEXT block's conv1 in one launch (rmem_bneck_chain): the 256-channel map is written once, not read back by that conv1
+                if ((chain_on and li == 1) or (chain2_on and li == 2)) and nxt is not None:
+                    # layers 1 and 2 (256-channel maps at stride 4, 512-channel maps at stride 8: HBM-bound at these batch sizes): a block's
+                    # conv3 + shortcut is chained into the NEXT block's conv1 in one launch (rmem_bneck_chain): the wide map is written once,
+                    # not read back by that conv1
                     pn = f'encoder.layer{nxt[0]}.{nxt[1]}'
                     n2 = 64 * 2 ** (nxt[0] - 1)
                     nbuf = self.mid_a128 if (nsplit > 1 and nxt == (2, 0)) else self.mid_a
                     a_next = sub(nbuf, ho * wo * n2, b0, nb)
                     kw = dict(x2=xs, H2=h, W2=w, Cin2=cin, stride2=s) if dual else dict(residual=xs)
                     q.append(ops.bneck_chain(bb, P[p + ('.c3ds.w' if dual else '.conv3.w')], P[p + ('.c3ds.b' if dual else '.conv3.b')], y,
-                                             P[pn + '.conv1.w'], P[pn + '.conv1.b'], a_next, H=ho, W=wo, K1=planes, N2=n2, batch=nb, **kw))
+                                             P[pn + '.conv1.w'], P[pn + '.conv1.b'], a_next, H=ho, W=wo, K1=planes, N2=n2, batch=nb, Cout=planes * 4, **kw))
                     conv1_done = True
                 elif dual:     # conv3 + strided 1x1 shortcut as one GEMM: the shortcut tensor never exists
                     q.append(ops.conv1x1_dual(bb, xs, P[p + '.c3ds.w'], P[p + '.c3ds.b'], y, H=ho, W=wo, Cin=planes, Cout=planes * 4,
