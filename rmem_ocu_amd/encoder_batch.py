@@ -9,7 +9,9 @@ results do not depend on B: the same kernel computes every output row from the s
 from __future__ import annotations
 
 import os
-from typing import Dict, Tuple
+from dataclasses import dataclass, replace
+from types import SimpleNamespace
+from typing import Dict, Optional, Tuple
 
 import torch
 
@@ -48,14 +50,69 @@ class _PtrInput:
             self._ptrs_set = False
 
 
+@dataclass(frozen=True)
+class EncoderRoutes:
+    """Which launches BatchEncoder builds its list from.  Every route computes the same maps, bit for bit, except stem='rowrun'
+    (another summation order) and front_split > 1 (split-K plans follow the GEMM's row count)."""
+    # 'pool': stem + max-pool in one pass (the half-resolution map is never written) | 'direct': stem and max-pool as two launches |
+    # 'rowrun': the 8-channel input layout and the generic row-run GEMM form (experiments; the only form of a pack without stem.w4)
+    stem: str = 'pool'
+    # n (experiment): stem and layer 1 run depth-first over n sub-batches of B / n frames (their maps are 211 MB per 16 frames: a
+    # sub-batch's maps may stay in the Infinity Cache between producer and consumer), layers 2-3 over all B frames; 1 unless n divides B
+    front_split: int = 1
+    # layer 1: every bottleneck is ONE launch (rmem_bneck_block64: the block's input read once, its output written once, the 64-channel
+    # maps never leave the CU), the last one with layer 2's first conv1 as its tail; off: the chained list.  Needs layer 1 in `chain`
+    block1: bool = True
+    # layers 1 and 2 (256-channel maps at stride 4, 512-channel maps at stride 8, 107 MB each at 16 frames: HBM-bound at these batch
+    # sizes): a block's conv3 + shortcut is chained into the NEXT block's conv1 in one launch (rmem_bneck_chain): the wide map is
+    # written once, not read back by that conv1.  A layer that is not listed takes separate launches
+    chain: Tuple[int, ...] = (1, 2)
+    # planes whose stride-1 3x3 is rmem_conv3x3_direct: layer 1 (64 channels); the 128-channel form (layer 2) is faster alone
+    # (57.3 -> 43.5 us) but takes a whole CU's LDS per workgroup and measured neutral in the pipeline: opt-in
+    direct3: Tuple[int, ...] = (64,)
+
+    @classmethod
+    def from_env(cls, env=os.environ) -> 'EncoderRoutes':
+        """The RMEM_* switches of the batch encoder; the on / off ones act at the value '1' only."""
+        on = lambda k: env.get(k, '0') == '1'       # noqa: E731
+        stem = env.get('RMEM_STEM', 'pool')
+        chain = () if on('RMEM_NO_BNECK_CHAIN') else (1,) if on('RMEM_NO_BNECK_CHAIN2') else (1, 2)
+        return cls(stem=stem if stem in ('pool', 'rowrun') else 'direct', front_split=int(env.get('RMEM_ENC_FRONT_SPLIT', '1')),
+                   block1=bool(chain) and not on('RMEM_NO_BNECK_BLOCK'), chain=chain,
+                   direct3=() if on('RMEM_NO_DIRECT_CONV3') else (64, 128) if on('RMEM_DIRECT_CONV3_128') else (64,))
+
+
+def r50_steps(routes: EncoderRoutes, blocks=R50_BLOCKS) -> list:
+    """The launches of the bottleneck stack in order, i counting the blocks through the layers: ('block', i, tail) the whole block
+    (tail: with block i + 1's conv1), ('conv1', i), ('conv2', i, direct), ('chain', i) conv3 + shortcut with block i + 1's conv1,
+    ('conv3', i) conv3 + shortcut alone.  Block i's conv1 is a step of its own unless the step before it was a chain or a tail."""
+    layer = [li for li, n in enumerate(blocks, start=1) for _ in range(n)]
+    steps, fed = [], False
+    for i, li in enumerate(layer):
+        last = i + 1 == len(layer)
+        if routes.block1 and li == 1:
+            fed = not last and layer[i + 1] != li
+            steps.append(('block', i, fed))
+            continue
+        if not fed:
+            steps.append(('conv1', i))
+        stride = R50_STRIDES[li - 1] if i == 0 or layer[i - 1] != li else 1
+        steps.append(('conv2', i, 64 * 2 ** (li - 1) in routes.direct3 and stride == 1))
+        fed = li in routes.chain and not last
+        steps.append(('chain' if fed else 'conv3', i))
+    return steps
+
+
 class BatchEncoder(_PtrInput):
-    def __init__(self, P: Dict[str, torch.Tensor], in_hw: Tuple[int, int], batch: int, device):
+    def __init__(self, P: Dict[str, torch.Tensor], in_hw: Tuple[int, int], batch: int, device, routes: Optional[EncoderRoutes] = None):
         if 'pe.w' in P:
             raise ops.RmemError('BatchEncoder covers the ResNet-50 encoder')
         self.P, self.B, self.dev = P, batch, device
-        H, W = in_hw
+        r = EncoderRoutes.from_env() if routes is None else routes
+        self.routes = r = replace(r, stem=r.stem if 'stem.w4' in P else 'rowrun', block1=r.block1 and 1 in r.chain,
+                                  front_split=r.front_split if r.front_split >= 1 and batch % r.front_split == 0 else 1)
+        B, (H, W) = batch, in_hw
         self.H, self.W = H, W
-        B = batch
         self.H2, self.W2 = _out(H, 7, 2, 3), _out(W, 7, 2, 3)
         self.H4, self.W4 = _out(self.H2, 3, 2, 1), _out(self.W2, 3, 2, 1)
         self.H8, self.W8 = _out(self.H4, 3, 2, 1), _out(self.W4, 3, 2, 1)
@@ -65,151 +122,95 @@ class BatchEncoder(_PtrInput):
         e = lambda *shape, dt=None: torch.empty(*shape, dtype=dt or dt16, device=device)  # noqa: E731
         self.img_in = e(B, 3, H, W, dt=F32)
         self._init_ptrs(B, device)
-        # stem input: NHWC4 frames inside the zero border rmem_stem7x7s2 reads (zeroed once here, only the interior is ever written);
-        # RMEM_STEM=rowrun keeps the 8-channel layout and the generic row-run GEMM form (experiments)
-        self.stem4 = os.environ.get('RMEM_STEM', 'pool') != 'rowrun' and 'stem.w4' in P          # RMEM_STEM = pool (default) | direct | rowrun
-        if self.stem4:
+        # stem input: NHWC4 frames inside the zero border rmem_stem7x7s2 reads (zeroed once here, only the interior is ever written)
+        if r.stem != 'rowrun':
             hp, wp = ops.stem_padded_size(H, W)
             self.img4 = torch.zeros(B, hp, wp, 4, dtype=dt16, device=device)
-        else:
+        else:      # the row-run form keeps the 8-channel layout
             self.img8 = e(B, H * W, 8)
-        self.stem_pool = self.stem4 and os.environ.get('RMEM_STEM', 'pool') == 'pool'
-        self.stem = None if self.stem_pool else e(B, self.H2 * self.W2, 64)      # (stem + max-pool in one pass: the half-resolution map does not exist)
+        self.stem = None if r.stem == 'pool' else e(B, self.H2 * self.W2, 64)      # (stem + max-pool in one pass: the half-resolution map does not exist)
         self.pool = e(B, M4, 64)
         self.x4 = [e(B, M4, 256), e(B, M4, 256)]
         self.x8 = [e(B, M8, 512), e(B, M8, 512)]
         self.x16 = [e(B, L, 1024), e(B, L, 1024)]
         self.mid_a = e(B * M4 * 128)
         self.mid_b = e(B * M4 * 64)
+        # layer 2's first conv1 output lives in its own buffer when the front is split: written per sub-batch while layer 1 still runs, its
+        # 128-channel rows of sub-batch 0 would overlap the 64-channel rows of sub-batch 1 in mid_a
+        self.mid_a128 = e(B * M4 * 128) if r.front_split > 1 else None
         self.conv_ws = torch.empty(16 * B * L * 256, dtype=F32, device=device)
         self._prog = None
+        # the bottleneck blocks in order (nxt: the one after): geometry, weight keys (c3: conv3, or conv3 and the projection shortcut packed as
+        # one GEMM) and the maps x (input), a, b (conv1's and conv2's outputs) and y as [image][elements] views of the whole-batch buffers
+        rows = lambda t, n: t.reshape(-1)[:B * n].view(B, n)       # noqa: E731
+        self.blocks, x, h, w, cin = [], rows(self.pool, M4 * 64), self.H4, self.W4, 64
+        for li, (nblk, outs) in enumerate(zip(R50_BLOCKS, (self.x4, self.x8, self.x16)), start=1):
+            for bi in range(nblk):
+                p, planes, stride = f'encoder.layer{li}.{bi}', 64 * 2 ** (li - 1), R50_STRIDES[li - 1] if bi == 0 else 1
+                ho, wo, dual = _out(h, 3, stride, 1), _out(w, 3, stride, 1), (p + '.c3ds.w') in P
+                a = self.mid_a128 if (r.front_split > 1 and (li, bi) == (2, 0)) else self.mid_a
+                self.blocks.append(SimpleNamespace(
+                    li=li, bi=bi, c1=p + '.conv1', c2=p + '.conv2', c3=p + ('.c3ds' if dual else '.conv3'), planes=planes, cin=cin, stride=stride,
+                    h=h, w=w, ho=ho, wo=wo, dual=dual, x=x, a=rows(a, h * w * planes), b=rows(self.mid_b, ho * wo * planes),
+                    y=rows(outs[bi % 2], ho * wo * planes * 4), nxt=None))
+                x, h, w, cin = self.blocks[-1].y, ho, wo, planes * 4
+        for blk, nxt in zip(self.blocks, self.blocks[1:]):
+            blk.nxt = nxt
         # stage outputs = the last block's buffer of every layer (block count - 1) % 2
         self.enc_out = (self.x4[(R50_BLOCKS[0] - 1) % 2], self.x8[(R50_BLOCKS[1] - 1) % 2], self.x16[(R50_BLOCKS[2] - 1) % 2])
 
-    def _conv(self, *a, **kw):
-        return ops.conv2d(*a, ws=self.conv_ws, batch=self.B, **kw)
+    def _conv(self, nb, *a, **kw):
+        return ops.conv2d(*a, ws=self.conv_ws, batch=nb, **kw)
+
+    def _wb(self, key):
+        return self.P[key + '.w'], self.P[key + '.b']
 
     def prog(self) -> list:
-        if self._prog is not None:
-            return self._prog
-        P, B, o = self.P, self.B, []
-        # RMEM_ENC_FRONT_SPLIT = n (experiment): stem and layer 1 run depth-first over n sub-batches of B / n frames (their maps are 211 MB
-        # per 16 frames: a sub-batch's maps may stay in the Infinity Cache between producer and consumer), layers 2-3 over all B frames
-        nsplit = int(os.environ.get('RMEM_ENC_FRONT_SPLIT', '1'))
-        if nsplit < 1 or B % nsplit:
-            nsplit = 1
-        chain_on = os.environ.get('RMEM_NO_BNECK_CHAIN', '0') != '1'
-        # layer 1: every bottleneck is ONE launch (rmem_bneck_block64: the block's input read once, its output written once, the 64-channel
-        # maps never leave the CU), the last one with layer 2's first conv1 as its tail; RMEM_NO_BNECK_BLOCK=1 restores the chained list
-        block_on = chain_on and os.environ.get('RMEM_NO_BNECK_BLOCK', '0') != '1'
-        # layer 2 (512-channel maps at stride 8, 107 MB each at 16 frames): its four links 2.0 -> 2.1 ... 2.3 -> 3.0 are chained like
-        # layer 1's were; RMEM_NO_BNECK_CHAIN2=1 restores the separate launches
-        chain2_on = chain_on and os.environ.get('RMEM_NO_BNECK_CHAIN2', '0') != '1'
-        # layer 1 (64 channels); the 128-channel form (layer 2) is faster alone (57.3 -> 43.5 us) but takes a whole CU's LDS per workgroup
-        # and measured neutral in the pipeline: opt-in (RMEM_DIRECT_CONV3_128=1)
-        direct3 = () if os.environ.get('RMEM_NO_DIRECT_CONV3', '0') == '1' else ((64, 128) if os.environ.get('RMEM_DIRECT_CONV3_128') == '1' else (64,))
-        blocks = [(li, bi) for li, nblk in enumerate(R50_BLOCKS, start=1) for bi in range(nblk)]
-        outs = [self.x4, self.x8, self.x16]
-        M4 = self.H4 * self.W4
-        if nsplit > 1 and getattr(self, 'mid_a128', None) is None:
-            self.mid_a128 = torch.empty(B * M4 * 128, dtype=self.pool.dtype, device=self.dev)     # layer 2's first conv1 output (see below)
+        if self._prog is None:
+            steps = [(getattr(self, '_' + kind), self.blocks[i], flag) for kind, i, *flag in r50_steps(self.routes)]
+            front = [s for s in steps if s[1].li == 1]
+            o, nb = [], self.B // self.routes.front_split
+            for b0 in range(0, self.B, nb):      # stem and layer 1, one sub-batch after the other
+                o += self._stem(b0, nb) + [f(r, slice(b0, b0 + nb), nb, *flag) for f, r, flag in front]
+            self._prog = o + [f(r, slice(0, self.B), self.B, *flag) for f, r, flag in steps[len(front):]]
+        return self._prog
 
-        def sub(t, per_image, b0, nb):            # images b0 .. b0 + nb of a [B, ...] buffer stored image-major
-            return t.reshape(-1)[b0 * per_image:(b0 + nb) * per_image]
+    def _stem(self, b0, nb) -> list:
+        P, s, H, W = self.P, slice(b0, b0 + nb), self.H, self.W
+        if self.routes.stem == 'rowrun':
+            return [ops.image_ptrs_to_nhwc8(self.img_ptrs[b0:], self.img8[s], H=H, W=W, images=nb),
+                    self._conv(nb, self.img8[s], P['stem.w'], P['stem.b'], self.stem[s], H=H, W=W, Cin=8, Cout=64, KH=7, KW=7, stride=2, pad=3, relu=True),
+                    ops.maxpool3x3s2(self.stem[s], self.pool[s], H=self.H2, W=self.W2, C=64, images=nb)]
+        q = [ops.image_ptrs_to_nhwc4p(self.img_ptrs[b0:], self.img4[s], H=H, W=W, images=nb)]
+        if self.routes.stem == 'pool':     # stem + max-pool in one pass: the half-resolution map is never written
+            return q + [ops.stem7x7s2_pool(self.img4[s], P['stem.w4'], P['stem.b'], self.pool[s], H=H, W=W, images=nb)]
+        return q + [ops.stem7x7s2(self.img4[s], P['stem.w4'], P['stem.b'], self.stem[s], H=H, W=W, images=nb),
+                    ops.maxpool3x3s2(self.stem[s], self.pool[s], H=self.H2, W=self.W2, C=64, images=nb)]
 
-        def stem(b0, nb):
-            q = []
-            conv = lambda *a_, **kw: ops.conv2d(*a_, ws=self.conv_ws, batch=nb, **kw)       # noqa: E731
-            pool = sub(self.pool, M4 * 64, b0, nb)
-            if self.stem4:
-                hp, wp = ops.stem_padded_size(self.H, self.W)
-                img4 = sub(self.img4, hp * wp * 4, b0, nb)
-                q.append(ops.image_ptrs_to_nhwc4p(self.img_ptrs[b0:], img4, H=self.H, W=self.W, images=nb))
-                if self.stem_pool:     # stem + max-pool in one pass: the half-resolution map is never written
-                    q.append(ops.stem7x7s2_pool(img4, P['stem.w4'], P['stem.b'], pool, H=self.H, W=self.W, images=nb))
-                else:
-                    st = sub(self.stem, self.H2 * self.W2 * 64, b0, nb)
-                    q.append(ops.stem7x7s2(img4, P['stem.w4'], P['stem.b'], st, H=self.H, W=self.W, images=nb))
-                    q.append(ops.maxpool3x3s2(st, pool, H=self.H2, W=self.W2, C=64, images=nb))
-            else:
-                img8 = sub(self.img8, self.H * self.W * 8, b0, nb)
-                st = sub(self.stem, self.H2 * self.W2 * 64, b0, nb)
-                q.append(ops.image_ptrs_to_nhwc8(self.img_ptrs[b0:], img8, H=self.H, W=self.W, images=nb))
-                q.append(conv(img8, P['stem.w'], P['stem.b'], st, H=self.H, W=self.W, Cin=8, Cout=64, KH=7, KW=7, stride=2, pad=3, relu=True))
-                q.append(ops.maxpool3x3s2(st, pool, H=self.H2, W=self.W2, C=64, images=nb))
-            return q
+    # one launch per step kind of r50_steps: block r over the nb images s (a slice) of the batch
+    def _block(self, r, s, nb, tail):
+        # the tail: the next layer's first conv1 (128 planes) reads the y tile in place
+        kw = dict(w1n=self.P[r.nxt.c1 + '.w'], bias1n=self.P[r.nxt.c1 + '.b'], a_next=r.nxt.a[s]) if tail else {}
+        return ops.bneck_block64(r.x[s], *self._wb(r.c1), *self._wb(r.c2), *self._wb(r.c3), r.y[s], H=r.h, W=r.w, Cin=r.cin, images=nb, **kw)
 
-        def run_blocks(idxs, b0, nb, x, hw, cin, conv1_done):
-            """the bottleneck blocks blocks[i], i in idxs, over images b0 .. b0 + nb; x: their input map (whole-batch buffer)"""
-            q = []
-            conv = lambda *a_, **kw: ops.conv2d(*a_, ws=self.conv_ws, batch=nb, **kw)       # noqa: E731
-            h, w = hw
-            for idx in idxs:
-                li, bi = blocks[idx]
-                stride = R50_STRIDES[li - 1]
-                planes = 64 * 2 ** (li - 1)
-                p = f'encoder.layer{li}.{bi}'
-                s = stride if bi == 0 else 1
-                ho, wo = _out(h, 3, s, 1), _out(w, 3, s, 1)
-                xs = sub(x, h * w * cin, b0, nb)
-                y = sub(outs[li - 1][bi % 2], ho * wo * planes * 4, b0, nb)
-                # (layer 2's first conv1 output lives in its own buffer when the front is split: the 128-channel rows of sub-batch 0
-                # would overlap the 64-channel rows of sub-batch 1 in mid_a)
-                abuf = self.mid_a128 if (nsplit > 1 and li == 2 and bi == 0) else self.mid_a
-                a = sub(abuf, h * w * planes, b0, nb)
-                bb = sub(self.mid_b, ho * wo * planes, b0, nb)
-                dual = (p + '.c3ds.w') in P
-                nxt = blocks[idx + 1] if idx + 1 < len(blocks) else None
-                if block_on and li == 1 and s == 1 and not conv1_done and cin == (64 if dual else 256):
-                    kw = {}
-                    if nxt == (2, 0):      # the tail: layer 2's first conv1 (128 planes) reads the y tile in place
-                        pn = 'encoder.layer2.0'
-                        nbuf = self.mid_a128 if nsplit > 1 else self.mid_a
-                        kw = dict(w1n=P[pn + '.conv1.w'], bias1n=P[pn + '.conv1.b'], a_next=sub(nbuf, ho * wo * 128, b0, nb))
-                        conv1_done = True
-                    q.append(ops.bneck_block64(xs, P[p + '.conv1.w'], P[p + '.conv1.b'], P[p + '.conv2.w'], P[p + '.conv2.b'],
-                                               P[p + ('.c3ds.w' if dual else '.conv3.w')], P[p + ('.c3ds.b' if dual else '.conv3.b')], y,
-                                               H=h, W=w, Cin=cin, images=nb, **kw))
-                    x, (h, w), cin = outs[li - 1][bi % 2], (ho, wo), planes * 4
-                    continue
-                if not conv1_done:
-                    q.append(conv(xs, P[p + '.conv1.w'], P[p + '.conv1.b'], a, H=h, W=w, Cin=cin, Cout=planes, relu=True))
-                conv1_done = False
-                if planes in direct3 and s == 1:     # read in place from rows kept in LDS, weights in registers (bit-identical)
-                    q.append(ops.conv3x3_direct(a, P[p + '.conv2.w'], P[p + '.conv2.b'], bb, H=h, W=w, C=planes, images=nb, relu=True))
-                else:
-                    q.append(conv(a, P[p + '.conv2.w'], P[p + '.conv2.b'], bb, H=h, W=w, Cin=planes, Cout=planes, KH=3, KW=3, stride=s, pad=1,
-                                  relu=True))
-                if ((chain_on and li == 1) or (chain2_on and li == 2)) and nxt is not None:
-                    # layers 1 and 2 (256-channel maps at stride 4, 512-channel maps at stride 8: HBM-bound at these batch sizes): a block's
-                    # conv3 + shortcut is chained into the NEXT block's conv1 in one launch (rmem_bneck_chain): the wide map is written once,
-                    # not read back by that conv1
-                    pn = f'encoder.layer{nxt[0]}.{nxt[1]}'
-                    n2 = 64 * 2 ** (nxt[0] - 1)
-                    nbuf = self.mid_a128 if (nsplit > 1 and nxt == (2, 0)) else self.mid_a
-                    a_next = sub(nbuf, ho * wo * n2, b0, nb)
-                    kw = dict(x2=xs, H2=h, W2=w, Cin2=cin, stride2=s) if dual else dict(residual=xs)
-                    q.append(ops.bneck_chain(bb, P[p + ('.c3ds.w' if dual else '.conv3.w')], P[p + ('.c3ds.b' if dual else '.conv3.b')], y,
-                                             P[pn + '.conv1.w'], P[pn + '.conv1.b'], a_next, H=ho, W=wo, K1=planes, N2=n2, batch=nb, Cout=planes * 4, **kw))
-                    conv1_done = True
-                elif dual:     # conv3 + strided 1x1 shortcut as one GEMM: the shortcut tensor never exists
-                    q.append(ops.conv1x1_dual(bb, xs, P[p + '.c3ds.w'], P[p + '.c3ds.b'], y, H=ho, W=wo, Cin=planes, Cout=planes * 4,
-                                              H2=h, W2=w, Cin2=cin, stride2=s, relu=True, batch=nb))
-                else:
-                    q.append(conv(bb, P[p + '.conv3.w'], P[p + '.conv3.b'], y, H=ho, W=wo, Cin=planes, Cout=planes * 4, residual=xs, relu=True))
-                x, (h, w), cin = outs[li - 1][bi % 2], (ho, wo), planes * 4
-            return q, x, (h, w), cin, conv1_done
+    def _conv1(self, r, s, nb):
+        return self._conv(nb, r.x[s], *self._wb(r.c1), r.a[s], H=r.h, W=r.w, Cin=r.cin, Cout=r.planes, relu=True)
 
-        n1 = R50_BLOCKS[0]
-        nb = B // nsplit
-        for k in range(nsplit):
-            o += stem(k * nb, nb)
-            q, x, hw, cin, c1 = run_blocks(range(n1), k * nb, nb, self.pool, (self.H4, self.W4), 64, False)
-            o += q
-        q, x, hw, cin, c1 = run_blocks(range(n1, len(blocks)), 0, B, x, hw, cin, c1)
-        o += q
-        self._prog = o
-        return o
+    def _conv2(self, r, s, nb, direct):
+        if direct:     # read in place from rows kept in LDS, weights in registers (bit-identical)
+            return ops.conv3x3_direct(r.a[s], *self._wb(r.c2), r.b[s], H=r.h, W=r.w, C=r.planes, images=nb, relu=True)
+        return self._conv(nb, r.a[s], *self._wb(r.c2), r.b[s], H=r.h, W=r.w, Cin=r.planes, Cout=r.planes, KH=3, KW=3, stride=r.stride, pad=1, relu=True)
+
+    def _chain(self, r, s, nb):
+        kw = dict(x2=r.x[s], H2=r.h, W2=r.w, Cin2=r.cin, stride2=r.stride) if r.dual else dict(residual=r.x[s])
+        return ops.bneck_chain(r.b[s], *self._wb(r.c3), r.y[s], *self._wb(r.nxt.c1), r.nxt.a[s],
+                               H=r.ho, W=r.wo, K1=r.planes, N2=r.nxt.planes, batch=nb, Cout=r.planes * 4, **kw)
+
+    def _conv3(self, r, s, nb):
+        if r.dual:     # conv3 + strided 1x1 shortcut as one GEMM: the shortcut tensor never exists
+            return ops.conv1x1_dual(r.b[s], r.x[s], *self._wb(r.c3), r.y[s], H=r.ho, W=r.wo, Cin=r.planes, Cout=r.planes * 4,
+                                    H2=r.h, W2=r.w, Cin2=r.cin, stride2=r.stride, relu=True, batch=nb)
+        return self._conv(nb, r.b[s], *self._wb(r.c3), r.y[s], H=r.ho, W=r.wo, Cin=r.planes, Cout=r.planes * 4, residual=r.x[s], relu=True)
 
 
 class SwinBatchEncoder(_PtrInput):

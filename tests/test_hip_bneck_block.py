@@ -1,5 +1,5 @@
 """rmem_bneck_block64 (csrc/bneck_block.hip): a whole planes = 64 ResNet bottleneck in one launch against the separate launches it
-replaces, bit for bit, and the encoder's layer-1 launch list built from it against the previous list (RMEM_NO_BNECK_BLOCK=1)."""
+replaces, bit for bit (the encoder's layer-1 launch list built from it against the chained list: tests/test_hip_encoder_routes.py)."""
 import numpy as np
 import pytest
 import torch
@@ -96,33 +96,3 @@ def test_block_is_bit_identical_to_separate_launches(dev, monkeypatch, B, H, W, 
         assert torch.equal(yi, y_def[0][i * hw:(i + 1) * hw]), f'image {i} of the batch differs from its single-image launch'
         if tail:
             assert torch.equal(ani, y_def[1][i * hw:(i + 1) * hw]), f'a_next of image {i} differs from its single-image launch'
-
-
-@pytest.mark.parametrize('dtype', ['bf16', 'fp16'])
-def test_encoder_layer1_blocks_equal_previous_list(dev, monkeypatch, dtype):
-    """BatchEncoder at 2 images of 97 x 129: x4, x8 and x16 of the default launch list (layer 1 as three one-launch bottlenecks, the last
-    with the tail into layer 2's conv1) equal those of the previous list (RMEM_NO_BNECK_BLOCK=1) bit for bit."""
-    from rmem_ocu_amd import build_vos_model, get_config, ops
-    from rmem_ocu_amd.encoder_batch import BatchEncoder
-    from rmem_ocu_amd.weights import synth_state_dict
-    cfg = get_config('pre_vost', 'test', 'r50_aotl')
-    cfg.MODEL_DTYPE = dtype
-    model = build_vos_model(cfg.MODEL_VOS, cfg).cuda(0)
-    model.load_state_dict(synth_state_dict(0, model='aot'))
-    P = model.packed()
-    img = seeded(20, (2, 3, 97, 129)).to(dev)
-    outs, names = [], []
-    for off in ('1', '0'):
-        monkeypatch.setenv('RMEM_NO_BNECK_BLOCK', off)
-        enc = BatchEncoder(P, (97, 129), 2, dev)
-        enc.img_in.copy_(img)
-        prog = enc.prog()
-        names.append([o.name for o in prog])
-        ops.run(prog)
-        torch.cuda.synchronize()
-        outs.append([t.clone() for t in enc.enc_out])
-    assert 'rmem_bneck_block64' not in names[0] and names[1].count('rmem_bneck_block64') == 3
-    assert len(names[0]) - len(names[1]) == 4          # 7 launches became 3
-    for name, t0, t1 in zip(('x4', 'x8', 'x16'), outs[0], outs[1]):
-        assert t0.float().abs().max().item() > 0
-        assert torch.equal(t0, t1), f'{name} differs in {(t0 != t1).sum().item()} elements'

@@ -1,6 +1,6 @@
 """rmem_bneck_chain with a 512-channel y (csrc/bottleneck.hip, two column chunks of 256): layer 2's conv3 + shortcut chained into the next
-block's conv1, bit for bit against the launches it replaces, and the encoder's launch list with the four layer-2 links chained
-against the list with separate launches (RMEM_NO_BNECK_CHAIN2=1)."""
+block's conv1, bit for bit against the launches it replaces (the encoder's launch list with the four layer-2 links chained against
+the list with separate launches: tests/test_hip_encoder_routes.py)."""
 import numpy as np
 import pytest
 import torch
@@ -61,33 +61,3 @@ def test_wide_chain_is_bit_identical_to_separate_launches(dev, N2, dual, B, Ho, 
     print(f'N2 {N2} dual {dual} M {M} {dt}: y differs in {(yc != y0).sum().item()}, a2 in {(ac != a0).sum().item()} elements')
     assert torch.equal(yc, y0), f'y differs in {(yc != y0).sum().item()} of {y0.numel()} elements'
     assert torch.equal(ac, a0), f'a2 differs in {(ac != a0).sum().item()} of {a0.numel()} elements'
-
-
-@pytest.mark.parametrize('dtype', ['bf16', 'fp16'])
-def test_encoder_layer2_links_equal_separate_launches(dev, monkeypatch, dtype):
-    """BatchEncoder at 2 images of 97 x 129: x4, x8 and x16 of the default launch list (links 2.0 -> 2.1, 2.1 -> 2.2, 2.2 -> 2.3 and
-    2.3 -> 3.0 chained) equal those of the list with separate launches (RMEM_NO_BNECK_CHAIN2=1) bit for bit, with 4 launches fewer."""
-    from rmem_ocu_amd import build_vos_model, get_config, ops
-    from rmem_ocu_amd.encoder_batch import BatchEncoder
-    from rmem_ocu_amd.weights import synth_state_dict
-    cfg = get_config('pre_vost', 'test', 'r50_aotl')
-    cfg.MODEL_DTYPE = dtype
-    model = build_vos_model(cfg.MODEL_VOS, cfg).cuda(0)
-    model.load_state_dict(synth_state_dict(0, model='aot'))
-    P = model.packed()
-    img = seeded(20, (2, 3, 97, 129)).to(dev)
-    outs, names = [], []
-    for off in ('1', '0'):
-        monkeypatch.setenv('RMEM_NO_BNECK_CHAIN2', off)
-        enc = BatchEncoder(P, (97, 129), 2, dev)
-        enc.img_in.copy_(img)
-        prog = enc.prog()
-        names.append([o.name for o in prog])
-        ops.run(prog)
-        torch.cuda.synchronize()
-        outs.append([t.clone() for t in enc.enc_out])
-    assert names[1].count('rmem_bneck_chain') - names[0].count('rmem_bneck_chain') == 4
-    assert len(names[0]) - len(names[1]) == 4
-    for name, t0, t1 in zip(('x4', 'x8', 'x16'), outs[0], outs[1]):
-        assert t0.float().abs().max().item() > 0
-        assert torch.equal(t0, t1), f'{name} differs in {(t0 != t1).sum().item()} elements'
