@@ -10,14 +10,14 @@
 // each (52.8 MB per map at 16 images of 121 x 213) and the chain kernel re-streams 64 KB of weights per 64 pixels.  Here the block's
 // input is read once and its output written once; a and b never leave the CU.
 //
-// Shape: that of conv3x3_direct.hip and stem.hip.  A workgroup owns a column strip (64 pixels computed, 62 delivered) and walks down a
+// Shape: a strip kernel (strip_conv.h).  A workgroup owns a column strip (64 pixels computed, 62 delivered) and walks down a
 // run of rows.  A step takes input row r = y + 1:
 //   A  the row piece of x (64 pixels, columns x0 - 1 .. x0 + 62, zero fill outside the image) has arrived by LDS-DMA as k-step panels
 //      [64 pixels][64 k]; conv1 (W1 in REGISTERS, the A operand) turns it into row r of a in a ring of four row slots in the layout
-//      of conv3x3_direct.hip.  Where the pixel lies outside the image a is ZERO (the 3x3 pads a, not x: conv1 of a zero pixel would
+//      of ring_slot_off.  Where the pixel lies outside the image a is ZERO (the 3x3 pads a, not x: conv1 of a zero pixel would
 //      be relu(b1));
-//   B  the 3x3 of output row y reads ring rows y - 1 .. y + 1 with W2 in registers (the loop of conv3x3_direct.hip) and leaves b as
-//      a [64 pixels][64 k] panel;
+//   B  the 3x3 of output row y reads ring rows y - 1 .. y + 1 with W2 in registers (the loop of ring3x3_mfma, written out here: see
+//      step B) and leaves b as a [64 pixels][64 k] panel;
 //   C  conv3 against W3 resident in LDS (loaded once per workgroup), W3 as the A operand: a lane's accumulators are 4 consecutive
 //      channels of a pixel, and the epilogue (+ bias, + shortcut, ReLU, one rounding) runs in registers, without staging or barriers.
 //      The identity shortcut is the x row again, fetched by LDS-DMA into the y tile one step after conv1 read it (measured: most of
@@ -33,6 +33,7 @@
 // 256 threads = 4 waves, one workgroup per CU (LDS 136 KB, projection form 160 KB); registers: W2 144, W1 8 / 32, W1' 64.
 #include "common.h"
 #include "lds_dma.h"
+#include "strip_conv.h"
 #include "../../include/rmem.h"
 #include <stdlib.h>
 
@@ -143,7 +144,7 @@ __global__ __launch_bounds__(256) void k_bneck_block(BbParams p) {
 #pragma unroll
   for (int ks = 0; ks < KS1; ++ks) w1f[ks] = *reinterpret_cast<const e16x8*>(p.w1 + (16 * wave + fr) * CIN + ks * 32 + fc * 8);
   const f32x4 bv1 = *reinterpret_cast<const f32x4*>(p.b1 + 16 * wave + fc * 4);
-  // W2 [64][3][3][64], the A operand of the 3x3 (conv3x3_direct.hip): 2 x 18 fragments of this wave's 32 output channels
+  // W2 [64][3][3][64], the A operand of the 3x3: 2 x 18 fragments of this wave's 32 output channels
   e16x8 wf[2][18];
 #pragma unroll
   for (int ct = 0; ct < 2; ++ct)
@@ -168,22 +169,20 @@ __global__ __launch_bounds__(256) void k_bneck_block(BbParams p) {
 #pragma unroll
   for (int j = 0; j < 8; ++j) bias3[j] = *reinterpret_cast<const f32x4*>(p.b3 + wn * 128 + j * 16 + fc * 4);
 
-  // byte offset of this lane's (pixel, chunk fc) inside a ring slot under horizontal tap dx, channel slice 0 (conv3x3_direct.hip)
+  // byte offset of this lane's (pixel, chunk fc) inside a ring slot under horizontal tap dx, channel slice 0
   int coff[2][3];
 #pragma unroll
   for (int pt = 0; pt < 2; ++pt)
 #pragma unroll
-    for (int dx = 0; dx < 3; ++dx) {
-      const int col = (wp * 2 + pt) * 16 + fr + dx;
-      coff[pt][dx] = (((col >> 4) * 8 + fc) * 16 + (col & 15)) * 16;
-    }
-  // where conv1 puts its 4 channels (16 wave + 4 fc ..) of pixel 16 pt + fr in a ring slot, and whether that pixel is inside the image
+    for (int dx = 0; dx < 3; ++dx) coff[pt][dx] = ring_slot_off<8>((wp * 2 + pt) * 16 + fr + dx, fc);
+  // where conv1 puts its 4 channels (16 wave + 4 fc ..: chunk 2 wave + (fc >> 1), a chunk being 256 bytes on from the one before, and
+  // the half fc & 1 of it) of pixel 16 pt + fr in a ring slot, and whether that pixel is inside the image
   int aoff[4];
   bool acol[4];
 #pragma unroll
   for (int pt = 0; pt < 4; ++pt) {
     const int col = pt * 16 + fr;
-    aoff[pt] = (((col >> 4) * 8 + 2 * wave + (fc >> 1)) * 16 + (col & 15)) * 16 + (fc & 1) * 8;
+    aoff[pt] = ring_slot_off<8>(col, 2 * wave) + (fc >> 1) * 256 + (fc & 1) * 8;
     acol[pt] = (unsigned)(x0 + col - 1) < (unsigned)p.W;
   }
   __builtin_amdgcn_sched_barrier(0);
@@ -238,7 +237,9 @@ __global__ __launch_bounds__(256) void k_bneck_block(BbParams p) {
     e16* const Yt = reinterpret_cast<e16*>(YTb);
     if constexpr (!PROJ) issue_sc(y, YTb);
 
-    // ---- B: b = relu(conv3x3(a) + b2) of output row y: the loop of conv3x3_direct.hip ----
+    // ---- B: b = relu(conv3x3(a) + b2) of output row y: the loop of ring3x3_mfma<2, 2, 2> (strip_conv.h) ----
+    // (written out: called as that function the identity forms of this kernel compile to 4 more registers and another order of
+    // waits, profiles/strip_conv_isa.txt; a kernel that calls ring3x3_mfma from the start has no such parity to keep)
     {
       f32x4 acc[2][2];
 #pragma unroll
@@ -395,8 +396,6 @@ __global__ __launch_bounds__(256) void k_bneck_block(BbParams p) {
   }
 }
 
-bool al16(const void* q) { return ((uintptr_t)q % 16) == 0; }
-
 }  // namespace
 
 extern "C" int RMEM_API(rmem_bneck_block64)(const rmem_bneck_block_desc* d, const void* x, const void* w1, const float* bias1, const void* w2,
@@ -408,27 +407,22 @@ extern "C" int RMEM_API(rmem_bneck_block64)(const rmem_bneck_block_desc* d, cons
   RMEM_REQUIRE(d->N2 == 0 || (d->N2 == 128 && d->Cin == 256), "rmem_bneck_block64: the tail needs N2 = 128 and the identity form");
   RMEM_REQUIRE((d->N2 != 0) == (w1n != nullptr) && (d->N2 != 0) == (bias1n != nullptr) && (d->N2 != 0) == (a_next != nullptr),
                "rmem_bneck_block64: w1n, bias1n and a_next go with N2 != 0");
-  RMEM_REQUIRE(al16(x) && al16(w1) && al16(bias1) && al16(w2) && al16(bias2) && al16(w3) && al16(bias3) && al16(y) && al16(w1n) && al16(bias1n) &&
-               al16(a_next), "rmem_bneck_block64: operands must be 16-byte aligned");
+  RMEM_REQUIRE(rmem_al16(x) && rmem_al16(w1) && rmem_al16(bias1) && rmem_al16(w2) && rmem_al16(bias2) && rmem_al16(w3) && rmem_al16(bias3) &&
+               rmem_al16(y) && rmem_al16(w1n) && rmem_al16(bias1n) && rmem_al16(a_next), "rmem_bneck_block64: operands must be 16-byte aligned");
   BbParams p;
   p.x = (const e16*)x; p.w1 = (const e16*)w1; p.b1 = bias1; p.w2 = (const e16*)w2; p.b2 = bias2; p.w3 = (const e16*)w3; p.b3 = bias3;
   p.y = (e16*)y; p.w1n = (const e16*)w1n; p.b1n = bias1n; p.an = (e16*)a_next;
   p.images = d->images; p.H = d->H; p.W = d->W;
   p.tiles_x = (d->W + TPV - 1) / TPV;
   p.x_bytes = (long)d->images * d->H * d->W * d->Cin * 2;
-  RMEM_REQUIRE(p.x_bytes + (long)(d->W + TP + 2) * d->Cin * 2 < (1L << 31) - (1L << 22),
-               "rmem_bneck_block64: the input exceeds the 2 GB a buffer descriptor addresses");
+  RMEM_REQUIRE(p.x_bytes + (long)(d->W + TP + 2) * d->Cin * 2 < kRsrcLimit, "rmem_bneck_block64: the input exceeds the 2 GB a buffer descriptor addresses");
   // runs of output rows per column strip: one workgroup per CU, rows per run as long as that allows (every run recomputes 2 rows of a
   // and re-loads the weights); RMEM_BNECK_ROWS forces the rows per run (tests: 1, 2, or >= H for the whole image)
   const int wgs = rmem_env_int("RMEM_BNECK_WGS", 256);
   const int forced = rmem_env_int("RMEM_BNECK_ROWS", 0);
   const long strips = (long)d->images * p.tiles_x;
-  long nruns = (wgs + strips - 1) / strips;
-  if (nruns < 1) nruns = 1;
-  if (nruns > d->H) nruns = d->H;
-  p.run_len = (int)((d->H + nruns - 1) / nruns);
-  if (forced > 0) p.run_len = forced < d->H ? forced : d->H;
-  p.nruns = (d->H + p.run_len - 1) / p.run_len;
+  const StripRuns runs = strip_runs(wgs, strips, d->H, forced);
+  p.nruns = runs.nruns; p.run_len = runs.run_len;
   const long grid = strips * p.nruns;
   RMEM_REQUIRE(grid < (1L << 30), "rmem_bneck_block64: too many workgroups");
   hipStream_t s = (hipStream_t)stream;

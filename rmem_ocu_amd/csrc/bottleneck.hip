@@ -314,8 +314,6 @@ __global__ __launch_bounds__(256, NCH) void k_bneck_chain(BnParams p) {
   }
 }
 
-bool al16(const void* q) { return ((uintptr_t)q % 16) == 0; }
-
 }  // namespace
 
 extern "C" int RMEM_API(rmem_bneck_chain)(const rmem_bneck_chain_desc* d, const void* b, const void* x2, const void* w3, const float* bias3,
@@ -327,8 +325,8 @@ extern "C" int RMEM_API(rmem_bneck_chain)(const rmem_bneck_chain_desc* d, const 
   RMEM_REQUIRE((x2 != nullptr) != (res != nullptr), "rmem_bneck_chain: exactly one of res (identity shortcut) and x2 (1x1 shortcut) must be given");
   RMEM_REQUIRE(!x2 || (d->Cin2 > 0 && d->Cin2 % 64 == 0 && d->stride2 >= 1 && d->H2 >= (d->Ho - 1) * d->stride2 + 1 && d->W2 >= (d->Wo - 1) * d->stride2 + 1),
                "rmem_bneck_chain: the 1x1 shortcut needs Cin2 % 64 == 0 and an H2 x W2 map that covers the strided samples");
-  RMEM_REQUIRE(al16(b) && al16(x2) && al16(w3) && al16(bias3) && al16(res) && al16(y) && al16(w1) && al16(bias1) && al16(a2),
-               "rmem_bneck_chain: operands must be 16-byte aligned");
+  RMEM_REQUIRE(rmem_al16(b) && rmem_al16(x2) && rmem_al16(w3) && rmem_al16(bias3) && rmem_al16(res) && rmem_al16(y) && rmem_al16(w1) &&
+               rmem_al16(bias1) && rmem_al16(a2), "rmem_bneck_chain: operands must be 16-byte aligned");
   BnParams p;
   p.b = (const e16*)b; p.x2 = (const e16*)x2; p.w3 = (const e16*)w3; p.b3 = bias3; p.res = (const e16*)res; p.y = (e16*)y;
   p.w1 = (const e16*)w1; p.b1 = bias1; p.a2 = (e16*)a2;
@@ -338,8 +336,7 @@ extern "C" int RMEM_API(rmem_bneck_chain)(const rmem_bneck_chain_desc* d, const 
   p.H2 = d->H2; p.W2 = d->W2; p.Cin2 = d->Cin2; p.stride2 = d->stride2;
   p.b_bytes = M * d->K1 * 2;
   p.x2_bytes = x2 ? (long)d->batch * d->H2 * d->W2 * d->Cin2 * 2 : 0;
-  const long lim = (1L << 31) - (1L << 22);
-  RMEM_REQUIRE(M * d->Cout < (1L << 31) && p.b_bytes < lim && p.x2_bytes < lim, "rmem_bneck_chain: an operand exceeds the 2 GB a buffer descriptor addresses");
+  RMEM_REQUIRE(M * d->Cout < (1L << 31) && p.b_bytes < kRsrcLimit && p.x2_bytes < kRsrcLimit, "rmem_bneck_chain: an operand exceeds the 2 GB a buffer descriptor addresses");
   p.M = (int)M;
   const dim3 grid((unsigned)((M + BM - 1) / BM));
   hipStream_t s = (hipStream_t)stream;

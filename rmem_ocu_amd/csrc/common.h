@@ -139,6 +139,9 @@ enum { RMEM_PROF_MEM_READ = 0, RMEM_PROF_GATED_PV = 1 };
 int rmem_prof_begin(int channel, void* stream, double flops);
 void rmem_prof_end(int channel, int slot, void* stream);
 
+// the alignment every entry point asks of operands that kernels read or write in 16-byte pieces (a null optional operand passes)
+inline bool rmem_al16(const void* q) { return ((uintptr_t)q % 16) == 0; }
+
 #define RMEM_REQUIRE(cond, msg)        \
   do {                                 \
     if (!(cond)) {                     \

@@ -2,7 +2,7 @@
 // the second conv of the ResNet layer-1 / layer-2 bottlenecks (encoders/resnet.py:52-56; 121 x 213 and 61 x 107 pixels x 16 frames per
 // launch in the bench) and the decoder's conv_4x (decoders/fpn.py:54-58, 121 x 213 x 8 clips).
 //
-// Same idea as stem.hip.  The implicit-GEMM form (gemm_conv.hip) copies every activation byte through LDS-DMA once per filter tap
+// Same idea as stem.hip (what the strip kernels share is in strip_conv.h).  The implicit-GEMM form (gemm_conv.hip) copies every activation byte through LDS-DMA once per filter tap
 // (9 x) plus a weight panel per k-step, and is bound by that copy.  Here a workgroup takes a strip of 64 output columns and walks down it:
 //   * each input row of the strip (66 pixels x 64 channels, 8.4 KB) goes to LDS ONCE, into a ring of four row slots, with zero fill
 //     outside the image (out-of-range offsets) and the 16-byte pieces permuted at the SOURCE into a column-interleaved layout, so
@@ -15,6 +15,7 @@
 // behind a counted vmcnt, one shared object and raw barriers (see stem.hip for why).
 #include "common.h"
 #include "lds_dma.h"
+#include "strip_conv.h"
 #include "../../include/rmem.h"
 #include <stdlib.h>
 
@@ -64,16 +65,13 @@ __global__ __launch_bounds__(C * 4) void k_conv3x3_direct(C3Params p) {
   // descriptor base = one pixel before image 0, so that column x0 - 1 has a non-negative offset
   const rsrc_t rs = make_rsrc(reinterpret_cast<const char*>(p.x) - PIXB, p.x_bytes + PIXB);
 
-  // this thread's pieces of a row.  A slot is laid out [column block of 16][channel chunk][column in block] x 16 B: the 16 lanes
-  // of a ds_read_b128 group read 16 CONSECUTIVE columns (whatever the tap shift, whatever the chunk), which then fall on 16 distinct
-  // 16-byte bank slots -- no conflicts at any alignment (the GEMM panels' XOR swizzle is conflict-free only for aligned column
-  // groups: 41 % of this kernel's LDS cycles were conflicts with it).  LDS-DMA fills a slot linearly, so the permutation is applied
-  // to the SOURCE: piece q = tid + NT i is column (q / (16 KC)) * 16 + (q & 15), chunk (q >> 4) % KC.
+  // this thread's pieces of a row.  A slot has the column-interleaved layout of ring_slot_off (strip_conv.h); LDS-DMA fills it linearly,
+  // so the permutation is applied to the SOURCE: piece q = tid + NT i is what belongs at byte 16 q of the slot.
   int poff[NDMA];
 #pragma unroll
   for (int i = 0; i < NDMA; ++i) {
     const int q = tid + NT * i;
-    const int col = (q / (16 * KC)) * 16 + (q & 15), kc = (q >> 4) % KC;
+    const int col = ring_slot_col<KC>(q), kc = ring_slot_chunk<KC>(q);
     poff[i] = (unsigned)(x0 + col - 1) < (unsigned)p.W ? col * PIXB + kc * 16 : OOB;
   }
   auto issue_row = [&](int row) {               // input row `row` of the strip -> slot row & 7 (rows outside the image: zero fill)
@@ -105,7 +103,7 @@ __global__ __launch_bounds__(C * 4) void k_conv3x3_direct(C3Params p) {
 #pragma unroll
     for (int dx = 0; dx < 3; ++dx) {
       const int col = (wp * PT + pt) * 16 + fr + dx;       // (columns 64, 65 -- outputs 62, 63, never stored -- read the next slot)
-      coff[pt][dx] = (((col >> 4) * KC + fc) * 16 + (col & 15)) * 16;
+      coff[pt][dx] = ring_slot_off<KC>(col, fc);
     }
   const int npix = min(TPV, p.W - x0);
   const float lo = p.relu ? 0.f : -3.0e38f;     // ReLU as a clamp from below (a select, not a branch)
@@ -126,28 +124,10 @@ __global__ __launch_bounds__(C * 4) void k_conv3x3_direct(C3Params p) {
     for (int ct = 0; ct < CT; ++ct)
 #pragma unroll
       for (int pt = 0; pt < PT; ++pt) acc[ct][pt] = f32x4{0.f, 0.f, 0.f, 0.f};
-    // k-slices (tap, channel slice), software-pipelined: the B fragments of slice k + 1 are requested before the MFMAs of slice k
-    // (at two waves per SIMD an exposed LDS round trip per slice is most of the tile otherwise)
     const char* rb[3];
 #pragma unroll
     for (int dy = 0; dy < 3; ++dy) rb[dy] = smem + ((y - 1 + dy) & (NSLOT - 1)) * ROW_BYTES;
-    e16x8 bf[2][PT];
-#pragma unroll
-    for (int pt = 0; pt < PT; ++pt) bf[0][pt] = *reinterpret_cast<const e16x8*>(rb[0] + coff[pt][0]);
-#pragma unroll
-    for (int k = 0; k < KS; ++k) {
-      if (k + 1 < KS) {
-        const int tap = (k + 1) / SPT, s = (k + 1) % SPT, dy = tap / 3, dx = tap - dy * 3;
-#pragma unroll
-        for (int pt = 0; pt < PT; ++pt) bf[(k + 1) & 1][pt] = *reinterpret_cast<const e16x8*>(rb[dy] + coff[pt][dx] + s * 1024);
-      }
-      __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-      for (int ct = 0; ct < CT; ++ct)
-#pragma unroll
-        for (int pt = 0; pt < PT; ++pt) acc[ct][pt] = RMEM_MFMA_16x16x32(wf[ct][k], bf[k & 1][pt], acc[ct][pt], 0, 0, 0);
-      __builtin_amdgcn_sched_barrier(0);
-    }
+    ring3x3_mfma<CT, PT, SPT>(wf, rb, coff, acc);
 #pragma unroll
     for (int ct = 0; ct < CT; ++ct)
 #pragma unroll
@@ -173,25 +153,21 @@ __global__ __launch_bounds__(C * 4) void k_conv3x3_direct(C3Params p) {
 extern "C" int RMEM_API(rmem_conv3x3_direct)(const void* x, int images, int H, int W, int C, const void* w, const float* bias, int relu, void* y,
                                              void* stream) {
   RMEM_REQUIRE(x && w && bias && y && images >= 1 && H >= 1 && W >= 1 && (C == 64 || C == 128), "rmem_conv3x3_direct: bad argument (C must be 64 or 128)");
-  RMEM_REQUIRE(((uintptr_t)x % 16) == 0 && ((uintptr_t)w % 16) == 0 && ((uintptr_t)bias % 16) == 0 && ((uintptr_t)y % 16) == 0,
-               "rmem_conv3x3_direct: operands must be 16-byte aligned");
+  RMEM_REQUIRE(rmem_al16(x) && rmem_al16(w) && rmem_al16(bias) && rmem_al16(y), "rmem_conv3x3_direct: operands must be 16-byte aligned");
   C3Params p;
   p.x = (const e16*)x; p.w = (const e16*)w; p.bias = bias; p.y = (e16*)y;
   p.images = images; p.H = H; p.W = W; p.relu = relu ? 1 : 0;
   p.tiles_x = (W + TPV - 1) / TPV;
   p.x_bytes = (long)images * H * W * C * 2;
-  RMEM_REQUIRE(p.x_bytes + (long)(W + TP + 2) * C * 2 < (1L << 31) - (1L << 22), "rmem_conv3x3_direct: the input exceeds the 2 GB a buffer descriptor addresses");
+  RMEM_REQUIRE(p.x_bytes + (long)(W + TP + 2) * C * 2 < kRsrcLimit, "rmem_conv3x3_direct: the input exceeds the 2 GB a buffer descriptor addresses");
   // runs of output rows per column strip: enough workgroups for two (C = 64) / one (C = 128) per CU, rows per run as long as that allows
   // (every run re-reads 2 rows and re-loads the weights)
   static const int wgs64 = rmem_env_int("RMEM_CONV3_WGS", 512);
   static const int wgs128 = rmem_env_int("RMEM_CONV3_WGS128", 256);
   const int wgs = C == 64 ? wgs64 : wgs128;
   const long strips = (long)images * p.tiles_x;
-  long nruns = (wgs + strips - 1) / strips;
-  if (nruns < 1) nruns = 1;
-  if (nruns > H) nruns = H;
-  p.run_len = (int)((H + nruns - 1) / nruns);
-  p.nruns = (H + p.run_len - 1) / p.run_len;
+  const StripRuns runs = strip_runs(wgs, strips, H);
+  p.nruns = runs.nruns; p.run_len = runs.run_len;
   const long grid = strips * p.nruns;
   RMEM_REQUIRE(grid < (1L << 30), "rmem_conv3x3_direct: too many workgroups");
   if (C == 64) hipLaunchKernelGGL(k_conv3x3_direct<64>, dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream, p);

@@ -1,6 +1,7 @@
-// What the compute kernels that stage through LDS-DMA share (gemm_conv.hip, bottleneck.hip, stem.hip, conv3x3_direct.hip,
-// idbank.hip, rowchain.hip): the address-space pointer types, the buffer descriptor and its 16-byte load into LDS, the offset
-// beyond every buffer, and the XOR swizzle of a 64-element tile row.  Helpers only: no kernel lives here.
+// What the compute kernels that stage through LDS-DMA share (gemm_conv.hip, bottleneck.hip, bneck_block.hip, stem.hip,
+// conv3x3_direct.hip, idbank.hip, rowchain.hip): the address-space pointer types, the buffer descriptor and its 16-byte load into
+// LDS, the offset beyond every buffer and the size limit that goes with it, and the XOR swizzle of a 64-element tile row.  Helpers
+// only: no kernel lives here.  (The strip kernels among them share more: strip_conv.h.)
 //
 // attention.hip keeps a private copy of the descriptor block (with make_rsrc(const void*, int)): bench.py ties the committed
 // counter summary of that kernel to the sha256 of its source, so any edit there marks the roofline traffic stale until the
@@ -34,6 +35,8 @@ __device__ inline void buf_load_lds16(rsrc_t, lptr_t, int, int) {}
 // a zero fill on loads -- a lane whose tap is padding, or whose row is past the last one, passes it instead of branching -- and
 // into a dropped store on stores.
 constexpr int OOB = (int)0x80000000;
+// ... which entry points enforce: the bytes a descriptor spans, slack for a kernel's overshoot included, stay below this
+constexpr long kRsrcLimit = (1L << 31) - (1L << 22);
 
 // Element index of (row, 16-byte chunk) in a [rows][64] e16 panel.  Rows are 128 B (8 chunks of 16 B); physical chunk =
 // chunk ^ ((row >> 1) & 7): the 16 lanes of every ds_read_b128 lane group (rows r..r+3, r+12..r+15 at chunk c and rows

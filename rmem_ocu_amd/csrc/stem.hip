@@ -17,6 +17,7 @@
 // copy is in flight behind the MFMAs and the stores of the current one (counted vmcnt: stores count too on CDNA4).
 #include "common.h"
 #include "lds_dma.h"
+#include "strip_conv.h"
 #include "../../include/rmem.h"
 #include <stdlib.h>
 
@@ -144,7 +145,7 @@ __global__ __launch_bounds__(256) void k_stem7x7s2(StemParams p) {
 // Stem + 3x3 stride-2 max-pool in one pass (encoders/resnet.py:131-136: conv1, bn1, relu, maxpool): the 64-channel map at half
 // resolution (210 MB per 16 frames) is never written.  A workgroup owns a strip of 27 pooled columns = 55 conv columns (61 are
 // computed: their windows are then 128 input pixels = ONE LDS-DMA instruction per input row) and walks DOWN a run of pooled rows,
-// two conv rows per iteration:
+// two conv rows per iteration (the runs: strip_runs, strip_conv.h):
 //   * input rows live in a ring of 32 one-KB slots; an iteration needs 10 of them, 4 are new: each of the four waves requests
 //     exactly one row per iteration, five iterations ahead (counted vmcnt: one request + one store per wave and iteration);
 //   * conv rows (+ bias, ReLU, rounded as stem7x7s2 stores them; columns / rows outside the map as zeros, which is what the pool's
@@ -308,8 +309,7 @@ extern "C" int RMEM_API(rmem_image_ptrs_to_nhwc4p)(const float* const* img_ptrs,
 extern "C" int RMEM_API(rmem_stem7x7s2_pool)(const void* x_padded, int images, int H, int W, const void* w, const float* bias, void* y_pooled,
                                              void* stream) {
   RMEM_REQUIRE(x_padded && w && bias && y_pooled && images >= 1 && H >= 7 && W >= 7, "rmem_stem7x7s2_pool: bad argument");
-  RMEM_REQUIRE(((uintptr_t)x_padded % 16) == 0 && ((uintptr_t)w % 16) == 0 && ((uintptr_t)bias % 16) == 0 && ((uintptr_t)y_pooled % 16) == 0,
-               "rmem_stem7x7s2_pool: operands must be 16-byte aligned");
+  RMEM_REQUIRE(rmem_al16(x_padded) && rmem_al16(w) && rmem_al16(bias) && rmem_al16(y_pooled), "rmem_stem7x7s2_pool: operands must be 16-byte aligned");
   StemPoolParams p;
   p.x = (const e16*)x_padded; p.w = (const e16*)w; p.bias = bias; p.y = (e16*)y_pooled;
   p.images = images;
@@ -318,22 +318,18 @@ extern "C" int RMEM_API(rmem_stem7x7s2_pool)(const void* x_padded, int images, i
   p.HP = (p.H2 - 1) / 2 + 1; p.WP = (p.W2 - 1) / 2 + 1;
   p.strips = (p.WP + SP_PV - 1) / SP_PV;
   p.x_bytes = (long)images * p.Hp * p.Wp * 8;
-  RMEM_REQUIRE(p.x_bytes < (1L << 31) - (1L << 22), "rmem_stem7x7s2_pool: the padded frames exceed the 2 GB a buffer descriptor addresses");
+  RMEM_REQUIRE(p.x_bytes < kRsrcLimit, "rmem_stem7x7s2_pool: the padded frames exceed the 2 GB a buffer descriptor addresses");
   static const int wgs = rmem_env_int("RMEM_STEM_POOL_WGS", 1024);     // 91.5 us at 640, 81 at 1024, 88 at 2048 (16 frames)
   const long cols = (long)images * p.strips;
-  long nruns = (wgs + cols - 1) / cols;
-  if (nruns < 1) nruns = 1;
-  if (nruns > p.HP) nruns = p.HP;
-  p.run_len = (int)((p.HP + nruns - 1) / nruns);
-  p.nruns = (p.HP + p.run_len - 1) / p.run_len;
+  const StripRuns runs = strip_runs(wgs, cols, p.HP);
+  p.nruns = runs.nruns; p.run_len = runs.run_len;
   hipLaunchKernelGGL(k_stem_pool, dim3((unsigned)(cols * p.nruns)), dim3(256), 0, (hipStream_t)stream, p);
   return rmem_check_launch("rmem_stem7x7s2_pool");
 }
 
 extern "C" int RMEM_API(rmem_stem7x7s2)(const void* x_padded, int images, int H, int W, const void* w, const float* bias, void* y, void* stream) {
   RMEM_REQUIRE(x_padded && w && bias && y && images >= 1 && H >= 7 && W >= 7, "rmem_stem7x7s2: bad argument");
-  RMEM_REQUIRE(((uintptr_t)x_padded % 16) == 0 && ((uintptr_t)w % 16) == 0 && ((uintptr_t)bias % 16) == 0 && ((uintptr_t)y % 16) == 0,
-               "rmem_stem7x7s2: operands must be 16-byte aligned");
+  RMEM_REQUIRE(rmem_al16(x_padded) && rmem_al16(w) && rmem_al16(bias) && rmem_al16(y), "rmem_stem7x7s2: operands must be 16-byte aligned");
   StemParams p;
   p.x = (const e16*)x_padded; p.w = (const e16*)w; p.bias = bias; p.y = (e16*)y;
   p.images = images;
@@ -342,7 +338,7 @@ extern "C" int RMEM_API(rmem_stem7x7s2)(const void* x_padded, int images, int H,
   p.tiles_x = (p.Wo + TP - 1) / TP;
   const long nt = (long)images * p.Ho * p.tiles_x;
   p.x_bytes = (long)images * p.Hp * p.Wp * 8;
-  RMEM_REQUIRE(p.x_bytes < (1L << 31) - (1L << 22) && nt < (1L << 30), "rmem_stem7x7s2: the padded frames exceed the 2 GB a buffer descriptor addresses");
+  RMEM_REQUIRE(p.x_bytes < kRsrcLimit && nt < (1L << 30), "rmem_stem7x7s2: the padded frames exceed the 2 GB a buffer descriptor addresses");
   p.ntiles = (int)nt;
   static const int wgs = rmem_env_int("RMEM_STEM_WGS", 1024);      // persistent workgroups (4 per CU)
   const unsigned grid = (unsigned)(nt < wgs ? nt : wgs);
