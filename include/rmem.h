@@ -722,6 +722,55 @@ int rmem_label_component_stats(const unsigned char* labels, const int* roots, in
 int rmem_label_clean(const unsigned char* src, unsigned char* dst, const int* roots, const int* stats, const int* table, int n, int H,
                      int W, int max_hole_area, int max_sprinkle_area, int keep_largest, void* stream);
 
+/* Label pieces through time (tubes.py: label_tubes, lineage, piece_events, tube_table, clean_tubes) -- the components above know
+ * the pieces of one frame, this knows which piece of frame f goes on in which piece of frame f + 1.
+ * labels: uint8 [n][H][W], contiguous, device, may start at any byte; every value 0..255 is treated alike.  roots / stats: what
+ * rmem_label_components / rmem_label_component_stats wrote for the WHOLE stack (their connectivity is the pieces').  Two pieces of
+ * one value on consecutive frames are linked when a pixel (y, x) of the one and a pixel (y', x') of the other satisfy
+ * (y', x') == (y, x) under temporal = 1, |y' - y| <= 1 and |x' - x| <= 1 under temporal = 9.  A tube is a connected set of pieces
+ * under links: what scipy.ndimage.label gives for labels == v under the 3-D structure whose centre plane is the pieces'
+ * connectivity and whose two outer planes hold the centre voxel (1) or the full 3 x 3 (9).  A tube is contiguous in time.
+ * A voxel's global index is g = f * H * W + y * W + x; tubes cross any boundary a pass would draw, so every entry point takes the
+ * stack whole: n in 1..65535, H * W <= 2^26, n * H * W <= 2^31 - 1.
+ *   tubes  int32 [n][H][W]: the global index of the tube's FIRST VOXEL in frame-major raster order.  rmem_label_tubes writes every
+ *          entry (three launches: parents from roots, links united with atomicMin in which the smaller index wins, flatten).
+ *   status int32 [1]: OR-ed into, never cleared; bit 0 = a union, bit 1 = a find ran into its bound (n * H * W steps).  A bug, not
+ *          a condition.
+ *   links  int32 [n][H * W][4]: at a piece's root (prev_min, prev_max, next_min, next_max), the smallest and largest root among
+ *          the linked pieces on frame f - 1 and on frame f + 1, (H * W, -1) where there is none; (H * W, -1, H * W, -1) anywhere
+ *          else.  Equal min and max: exactly one neighbour in time.  rmem_label_tube_lineage writes every entry.
+ *   events int32 [n][256][4]: per frame f and value v the number of pieces of v on f that are born (f >= 1, no predecessor), ended
+ *          (f <= n - 2, no successor), splitting (several successors: next_max >= 0 and next_min != next_max) and merging (several
+ *          predecessors).  rmem_label_tube_events writes every entry from the links of the same stack.
+ *   rank   int32 [n][H][W]: at a tube's first voxel its position among all tubes in ascending id, -1 elsewhere; total int32 [1]:
+ *          the number of tubes.  rmem_label_tube_index writes every entry of both (count, scan, write; the counts of the chunks
+ *          pass through rank itself).
+ *   table  int32 [rows][10]: row rank = (first = the tube id, value, voxels, pieces, f_first, f_last, nb_min, nb_max, border,
+ *          peak_area): nb_min / nb_max the extrema of its pieces' nb_min / nb_max, (256, -1) if no piece has a neighbour; border 1
+ *          if a piece touches its frame's edge; peak_area its largest piece.  rmem_label_tube_table writes every row below
+ *          min(rows, total) completely and nothing else: a tube whose rank is >= rows is left out, rows = 0 launches nothing.
+ * rmem_label_tube_clean is one pass, every decision from the pieces and tubes of src; table must hold every tube (rows >= total).
+ * With life = f_last - f_first + 1 and closed = f_first >= 1 and f_last <= n - 2 (frame 0 is the given annotation; a tube alive on
+ * the last frame has a life nobody has seen the end of) a voxel of value v becomes
+ *   v != 0, closed, life < min_frames: its PIECE's nb_min where the piece's nb_min == nb_max, else 0 (rmem_label_clean's rule);
+ *   v == 0, closed, life <= max_hole_frames, the tube's border == 0 and nb_min == nb_max: the tube's nb_min;
+ *   and stays v otherwise.  min_frames <= 1 with max_hole_frames = 0 is the identity.  dst == src is allowed; both may start at
+ * any byte.  rmem_label_tubes_workspace_bytes: the bytes of roots, stats, tubes and rank for the whole stack (28 per voxel), 0 for
+ * refused geometry.  No state between calls, no host sync, everything on the caller's stream, integer atomics only:
+ * bit-reproducible.  Refused (non-zero, nothing launched): a null pointer, n outside 1..65535, non-positive H / W, H * W above
+ * 2^26, n * H * W above 2^31 - 1, a temporal other than 1 or 9, negative rows, min_frames or max_hole_frames. */
+long long rmem_label_tubes_workspace_bytes(int n, int H, int W);   /* host only */
+int rmem_label_tubes(const unsigned char* labels, const int* roots, int n, int H, int W, int temporal, int* tubes, int* status,
+                     void* stream);
+int rmem_label_tube_lineage(const unsigned char* labels, const int* roots, int n, int H, int W, int temporal, int* links, void* stream);
+int rmem_label_tube_events(const unsigned char* labels, const int* roots, const int* links, int n, int H, int W, int* events,
+                           void* stream);
+int rmem_label_tube_index(const int* tubes, int n, int H, int W, int* rank, int* total, void* stream);
+int rmem_label_tube_table(const unsigned char* labels, const int* roots, const int* stats, const int* tubes, const int* rank, int n,
+                          int H, int W, int rows, int* table, void* stream);
+int rmem_label_tube_clean(const unsigned char* src, unsigned char* dst, const int* roots, const int* stats, const int* tubes,
+                          const int* rank, const int* table, int n, int H, int W, int min_frames, int max_hole_frames, void* stream);
+
 /* Exact Euclidean distance transform of uint8 label stacks and the peaks of a distance map (distance.py: label_edt, peaks,
  * hausdorff2, hausdorff; evaluator.surface_distance, next_clicks).  Squared distances between pixel centres as int32; integers
  * only, no float anywhere.  labels: uint8 [n][H][W], contiguous, device, may start at any byte; frames are independent; every

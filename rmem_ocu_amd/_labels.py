@@ -1,4 +1,4 @@
-"""Argument checks and small rules the modules on uint8 label stacks share (pairs, components, polygons, rle, the label part of
+"""Argument checks and small rules the modules on uint8 label stacks share (pairs, components, tubes, polygons, rle, the label part of
 evaluator, distance, surface, skeleton, shapes): integers in a range, connectivity, the stack and its limits, the sides the separable
 transforms take, a tensor that goes with a stack, a pair of stacks, the workspace budget of a call that
 passes over a stack, the keys of un-squeezed objects, the boundary P / R / F.  Streams, workspaces and packed files are _codec's."""

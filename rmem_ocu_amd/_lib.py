@@ -207,6 +207,13 @@ SIGNATURES = {
     'rmem_label_components': (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp]),
     'rmem_label_component_stats': (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp]),
     'rmem_label_clean': (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
+    'rmem_label_tubes_workspace_bytes': (_ll, [_i, _i, _i]),
+    'rmem_label_tubes': (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp]),
+    'rmem_label_tube_lineage': (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp]),
+    'rmem_label_tube_events': (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp]),
+    'rmem_label_tube_index': (_i, [_vp, _i, _i, _i, _vp, _vp, _vp]),
+    'rmem_label_tube_table': (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp]),
+    'rmem_label_tube_clean': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
     'rmem_label_edt_workspace_bytes': (_ll, [_i, _i, _i]),
     'rmem_label_edt': (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp, _ll, _vp]),
     'rmem_label_edt_peaks_workspace_bytes': (_ll, [_i]),

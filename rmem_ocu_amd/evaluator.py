@@ -460,6 +460,43 @@ def object_fragments(labels_u8: torch.Tensor, num_objs: int, connectivity: int =
     return fragments(labels_u8, num_objs, connectivity)
 
 
+def remove_flicker(labels_u8: torch.Tensor, min_frames: int = 3, fill_frames: int = 0, connectivity: int = 8,
+                   temporal: int = 1) -> torch.Tensor:
+    """Delivered labels without their flicker, on the device: a new uint8 stack like labels_u8 ([n, H, W], device) in which every
+    space-time piece of an object that begins after frame 0, ends before the last frame and lives for fewer than min_frames
+    frames is replaced by the one value around it (else background) -- the false blob of a frame or two, whatever its area, which
+    clean_masks(remove_specks=...) cannot tell from a small real object -- and, with fill_frames, a gap inside one object that is
+    open for at most fill_frames frames is filled with it (tubes.clean_tubes, whose docstring has the rule).  The stack is taken
+    whole.  Like clean_masks, something the caller applies to the labels a run delivered: nothing here feeds it back into a memory
+    bank.  The current stream; one 8-byte readback."""
+    from .tubes import clean_tubes
+    return clean_tubes(labels_u8, min_frames=min_frames, max_hole_frames=fill_frames, connectivity=connectivity, temporal=temporal)
+
+
+def object_events(labels_u8: torch.Tensor, num_objs: int, connectivity: int = 8, temporal: int = 1) -> torch.Tensor:
+    """int32 [n, num_objs + 1, 4] on the device: per frame and value 0..num_objs the number of its pieces that are (born, ended,
+    splitting, merging) there (tubes.piece_events).  object_fragments says that an object has 1 piece on frame 40 and 2 on frame
+    41; this says whether a piece was cut in two (splitting 1 on frame 40) or an unrelated blob appeared beside it (born 1 on
+    frame 41).  The current stream, no host sync."""
+    from .tubes import piece_events
+    K = _labels.int_in('evaluator.object_events', 'num_objs', num_objs, 1, 255)
+    return piece_events(labels_u8, connectivity, temporal)[:, :K + 1].contiguous()
+
+
+def object_tracks(labels_u8: torch.Tensor, num_objs: int, connectivity: int = 8, temporal: int = 1) -> Dict[int, List[Dict[str, int]]]:
+    """{object id: [{'first_frame', 'last_frame', 'voxels', 'pieces', 'peak_area'}, ...]} on the host, for the ids 1..num_objs: the
+    space-time pieces (tubes.tube_table) of every object, each list in order of first voxel.  One entry: the object is one track.
+    Two: it left and came back, or was never in one piece.  None: it is absent.  One readback of the table."""
+    from .tubes import tube_table
+    K = _labels.int_in('evaluator.object_tracks', 'num_objs', num_objs, 1, 255)
+    table, _ = tube_table(labels_u8, connectivity, temporal)
+    tracks: Dict[int, List[Dict[str, int]]] = {k: [] for k in range(1, K + 1)}
+    for first, value, voxels, pieces, f_first, f_last, _lo, _hi, _border, peak in table.cpu().tolist():
+        if 1 <= value <= K:
+            tracks[value].append({'first_frame': f_first, 'last_frame': f_last, 'voxels': voxels, 'pieces': pieces, 'peak_area': peak})
+    return tracks
+
+
 def surface_distance(pred_u8: torch.Tensor, gt_u8: torch.Tensor, num_objs: int) -> np.ndarray:
     """float64 numpy [n, num_objs]: the Hausdorff distance in pixels between the predicted and the annotated mask of object
     1..num_objs on every frame (distance.hausdorff): 0 where both are empty, inf where exactly one is.  The third number reported
